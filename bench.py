@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Groth16 proofs/s on the SHA-256 fixture circuit (BASELINE.json metric), MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c4|c2|c3|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload c4|c2|c3|c5] [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Default workload = BASELINE configs[3] ("c4"), the reference's own run of the fixture
@@ -10,13 +10,20 @@ Default workload = BASELINE configs[3] ("c4"), the reference's own run of the fi
 sampled and used online as sha256.rs:226-291 does (6 FftMask, 1 DegRedMask, 5 MsmMask), every share (QAP, witness,
 packed CRS, masks) already resident in HBM: circom_h (3 d_ifft + 3 d_fft + deg_red) and the five d_msm, ending with
 the parties' (A, B, C) shares on the host.  The headline runs with the fixed-base tables of the CRS a prover service
-builds once per circuit (zk_msm_precompute); the same K steps WITHOUT tables -- the like-for-like figure, the
-reference has no such precomputation -- are timed right after and reported as `table_free`.
+builds once per circuit (zk_msm_precompute).
 
-Rank 0 prints ONE JSON line.  `roofline` is the slot with the largest share of the timed region (HIP events on the
-launching stream, zk_profile_*): algorithmic bytes per launch (SURVEY.md 8d) over its average launch duration;
-`cpu_baseline` is the plain-C restatement of the reference's CPU path (oracle/c, kind "port") timed on this host on
-the same shares with 1 thread, one thread per party and all cores, its proof compared with the GPU's.
+A plain run sets up, runs W warm-up proofs, times K proofs once and prints ONE JSON line (rank 0): `value` = K over
+that loop's wall time, `ms_per_step` = the loop's time / K.  The inputs (witness and mask shares) are dealt on the
+replayable share-randomness stream, so they are the same in every run with the same arguments; the timed proofs run
+on the production stream.  --dump-outputs DIR writes what the last timed proof returned (dump_outputs).
+
+--full adds everything else, after the headline loop: the K-step loop timed four more times (`repetitions`, the last
+one with the HIP-event slots on: `roofline`, `proof_alu`, `kernels`, `host_us_per_proof`), the same K steps WITHOUT
+tables -- the like-for-like figure, the reference has no such precomputation -- as `table_free`, two proofs in flight,
+batches, the primitives at 2^20, and `cpu_baseline`: the plain-C restatement of the reference's CPU path (oracle/c,
+kind "port") timed on this host on the same shares with 1 thread, one thread per party and all cores, its proof
+compared with the GPU's.  `roofline` is the slot with the largest share of the timed region (HIP events on the
+launching stream, zk_profile_*): algorithmic bytes per launch over its average launch duration.
 """
 import argparse
 import ctypes as C
@@ -555,36 +562,60 @@ def cpu_baseline_c5(pp, zk, log_m_full):
 REPS = 5
 
 
-def timed(pp, zg, crs, wit, r, s, masks, steps, warmup, torch, reps=REPS):
-    """W warm-up proofs, then the K-step loop `reps` times (each bracketed by a device synchronise): returns the MEDIAN
-    loop time, the min / max, the per-kernel slot times of the median-adjacent last repetition, the MSM work counters
-    of that repetition and the last proof."""
+def timed(pp, zg, crs, wit, r, s, masks, steps, warmup, torch, reps=REPS, profile=True):
+    """W warm-up proofs, then the K-step loop `reps` times (each bracketed by a device synchronise): returns the time of
+    the FIRST loop and its last proof (the headline: K timed proofs, no slots on), the MEDIAN loop time, the min / max,
+    the last proof and, with `profile` (reps > 1), the per-kernel slot times of the last repetition and the MSM work
+    counters of that repetition."""
     for i in range(warmup):
         proof = zg.prove(pp, crs, wit, r, s, masks=masks, seed=1000 + i)
     torch.cuda.synchronize()
     dts = []
-    prof = adds = offered = None
+    prof = adds = offered = first = None
     for rep_i in range(reps):
-        last = rep_i == reps - 1
+        last = profile and rep_i == reps - 1 and rep_i > 0
         if last:
             pp._check(pp.lib.zk_profile_enable(pp.h, 1))
-        st0 = msm_stats(pp)
+            st0 = msm_stats(pp)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(steps):
             proof = zg.prove(pp, crs, wit, r, s, masks=masks, seed=2000 + i)      # fresh share randomness per proof
         torch.cuda.synchronize()
         dts.append(time.perf_counter() - t0)
-        st1 = msm_stats(pp)
+        if rep_i == 0:
+            first = proof
         if last:
+            st1 = msm_stats(pp)
             prof = read_profile(pp)
             pp._check(pp.lib.zk_profile_enable(pp.h, 0))
             adds = {"g1": st1[0] - st0[0], "g2": st1[1] - st0[1]}
             offered = {"g1": st1[2] - st0[2], "g2": st1[3] - st0[3]}
     srt = sorted(dts)
     med = srt[len(srt) // 2]
-    return {"dt": med, "dt_last": dts[-1], "min": srt[0], "max": srt[-1], "prof": prof, "adds": adds, "offered": offered,
-            "proof": proof}
+    return {"dt_first": dts[0], "proof_first": first, "dt": med, "dt_last": dts[-1], "min": srt[0], "max": srt[-1],
+            "prof": prof, "adds": adds, "offered": offered, "proof": proof}
+
+
+def dump_outputs(pp, proof, out_dir):
+    """--dump-outputs: what the timed path returned in its last step -- every party's share of the proof's A (G1), B (G2)
+    and C (G1) -- as DIR/proof_{a,b,c}_shares.npy, float64 [parties][coordinates][16]: the canonical affine coordinates
+    (A, C: x, y; B: x.c0, x.c1, y.c0, y.c1) of the point each returned Jacobian share stands for (the Jacobian limbs of a
+    point are not unique), split into 16-bit limbs, least significant first (exact in float64).  An identity share is
+    all zeros.  The shares do not depend on the timed proofs' share randomness (same_shares)."""
+    from zksaas_amd import wire
+    os.makedirs(out_dir, exist_ok=True)
+    nlimbs = -(-pp.fq.p.bit_length() // 16)
+    for name, shares, g2 in (("a", proof[0], False), ("b", proof[1], True), ("c", proof[2], False)):
+        rows = []
+        for q in range(pp.n):
+            pt = wire.jacobian_to_affine(pp, shares[q], g2)
+            if pt is None:
+                coords = [0] * (4 if g2 else 2)
+            else:
+                coords = [pt[0][0], pt[0][1], pt[1][0], pt[1][1]] if g2 else [pt[0], pt[1]]
+            rows.append([[(c >> (16 * k)) & 0xFFFF for k in range(nlimbs)] for c in coords])
+        np.save(os.path.join(out_dir, "proof_%s_shares.npy" % name), np.asarray(rows, dtype=np.float64))
 
 
 def batched(pp, zg, crs, wits, r, s, masks, nb, nbatches, torch, ref_proofs, inflight=1):
@@ -705,17 +736,26 @@ def main():
                     help="N > 1: how a king round runs -- the reference's star through rank 0 (king on GPU 0, RCCL gather / "
                          "scatter: north_star's topology, the default; the same run then also times the all-to-all king and "
                          "reports it as `alltoall`) or every rank king of a chunk range (two all-to-all exchanges)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="c4 on one GPU: after the headline loop also run the repeated and profiled K-step loops "
+                         "(repetitions, roofline, proof_alu, kernels), the CPU baselines and the table-free / two in flight "
+                         "/ batched / primitives legs; a plain run times the K steps once and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="c4 on one GPU: write what the last timed proof returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--aux-timeout", type=float, default=300.0,
-                    help="seconds the legs after the timed K steps (table-free, two in flight, batches, primitives) may take "
-                         "together before the line is printed without the unfinished ones (they normally take ~30 s)")
+                    help="with --full: seconds the legs after the timed K steps (table-free, two in flight, batches, "
+                         "primitives) may take together before the line is printed without the unfinished ones (they "
+                         "normally take ~30 s)")
     ap.add_argument("--no-masks", action="store_true", help="zero masks (the *::zero() variants the reference's "
                     "micro-benchmarks use); default: all twelve masks sampled, as groth16/examples/sha256.rs")
     ap.add_argument("--no-tables", action="store_true", help="headline without the fixed-base tables of the CRS")
-    ap.add_argument("--no-primitives", action="store_true", help="skip the d_fft / d_msm side measurements and the "
-                    "table-free / pipelined legs (used for the rocprofv3 runs so that every profiled launch belongs to "
-                    "the headline proof loop)")
+    ap.add_argument("--no-primitives", action="store_true", help="with --full: skip the d_fft / d_msm side measurements "
+                    "and the table-free / pipelined legs (used for the rocprofv3 runs so that every profiled launch belongs "
+                    "to the headline proof loop)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -738,6 +778,9 @@ def main():
         local_rank = 0           # debugging mode: every rank drives GPU 0
     torch.cuda.set_device(local_rank)
 
+    sharded = world > 1 or args.workload != "c4" or os.environ.get("ZK_BENCH_FORCE_SHARDED")
+    if args.dump_outputs and sharded:
+        raise SystemExit("--dump-outputs: the single-GPU c4 line only")
     if args.workload == "dealer":
         # not a BASELINE config and not a proof rate -- one line of per-kernel timings
         if rank == 0:
@@ -745,7 +788,7 @@ def main():
             import dealer_bench
             dealer_bench.main(["--reps", str(max(3, min(args.steps, 10)))])
         return
-    if world > 1 or args.workload != "c4" or os.environ.get("ZK_BENCH_FORCE_SHARDED"):
+    if sharded:
         from zksaas_amd import multigpu
         res = multigpu.bench(args, rank, local_rank, world)
         if rank == 0:
@@ -755,19 +798,26 @@ def main():
     pp = zk.PackedSharingParams("bn254", 2, device=local_rank)
     for kv in filter(None, os.environ.get("ZK_BENCH_OPTIONS", "").split(",")):     # A/B runs: name=value context options
         pp.set_option(kv.split("=")[0], int(kv.split("=")[1]))
+    # the dealing (witness and mask shares) runs on the replayable stream, so every run with the same arguments proves
+    # from the same inputs (as multigpu.bench deals); the timed proofs run on the production stream again
+    from zksaas_amd import api
+    pp.set_option("rng_replay", 1)
     r1, w, setup, crs, wit, r, s = build_inputs(pp, zk)
     masks = None if args.no_masks else zg.ProofMasks(pp, wit.log_m, seed=77)
+    if not api.DEFAULT_OPTIONS.get("rng_replay"):
+        pp.set_option("rng_replay", 0)
     table_windows = None
-    table_windows_by_group = None
     if not args.no_tables:
-        from zksaas_amd import api
         if os.environ.get("ZK_TABLE_C"):
             pp.set_option("msm_table_c", int(os.environ["ZK_TABLE_C"]))
         crs.precompute()
         table_windows = api.msm_table_info(pp, api.ZK_G1, crs.s)["windows"]
-        table_windows_by_group = {"g1": table_windows, "g2": api.msm_table_info(pp, api.ZK_G2, crs.v)["windows"]}
-    tm = timed(pp, zg, crs, wit, r, s, masks, args.steps, args.warmup, torch)
-    dt, prof, proof = tm["dt"], tm["prof"], tm["proof"]
+    # the headline is the first K-step loop; --full times it REPS times, the last repetition with the slots on
+    tm = timed(pp, zg, crs, wit, r, s, masks, args.steps, args.warmup, torch, reps=REPS if args.full else 1,
+               profile=args.full)
+    dt, prof, proof = tm["dt_first"], tm["prof"], tm["proof_first"]
+    if args.dump_outputs:
+        dump_outputs(pp, proof, args.dump_outputs)
 
     proofs_per_s = args.steps / dt
     res = {
@@ -782,19 +832,24 @@ def main():
                    "masks": masks is not None, "constraints": r1.num_constraints,
                    "wires": r1.num_variables, "domain": 1 << wit.log_m, "len_a": crs.len_a, "len_w": crs.len_w,
                    "len_u": crs.len_u, "parties": pp.n, "packing_factor": pp.l,
-                   "fixed_base_tables": not args.no_tables,
-                   "crs_identity_fraction": identity_fractions(pp, crs)},
+                   "fixed_base_tables": not args.no_tables},
         "constraints_per_sec": round(proofs_per_s * r1.num_constraints, 1),
-        "repetitions": {"count": REPS, "ms_per_step_median": round(dt / args.steps * 1e3, 4),
+    }
+    if not args.full:
+        print(json.dumps(res))
+        return
+    res["config"]["crs_identity_fraction"] = identity_fractions(pp, crs)
+    res.update({
+        "repetitions": {"count": REPS, "ms_per_step_median": round(tm["dt"] / args.steps * 1e3, 4),
                         "ms_per_step_min": round(tm["min"] / args.steps * 1e3, 4),
                         "ms_per_step_max": round(tm["max"] / args.steps * 1e3, 4),
                         "note": "the K-step loop is timed %d times after the warm-up; value and ms_per_step are the "
-                                "median repetition, roofline / kernels the last one" % REPS},
+                                "first repetition, roofline / kernels the last one" % REPS},
         "roofline": roofline_of(prof, ntt_passes=2, masks_on=masks is not None, pp=pp, table_windows=table_windows,
                                 adds=tm["adds"]),
         "proof_alu": proof_alu(tm["adds"], tm["offered"], args.steps, tm["dt_last"]),
         "kernels": [{**e, "total_ms": round(e["total_ms"], 3)} for e in prof if e["launches"]],
-    }
+    })
     host = {e["kernel"][5:]: e["total_ms"] / e["launches"] * 1e3 for e in prof if e["launches"] and e["kernel"].startswith("host:")}
     if host:
         # where the host is during one zk_groth16_prove of the last repetition (steady_clock spans inside the library:
@@ -813,7 +868,6 @@ def main():
         if not args.no_tables:
             guard.leg = "table_free"
             # the like-for-like figure: the same K steps without the fixed-base tables (dropped, then rebuilt)
-            from zksaas_amd import api
             for buf in (crs.s, crs.h, crs.v, crs.w, crs.u):
                 api.msm_forget(pp, buf)
             tm2 = timed(pp, zg, crs, wit, r, s, masks, args.steps, max(2, args.warmup // 2), torch, reps=3)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Same-box A/B of two builds of the library: tools/ab.sh <other.so> <rounds> <bench.py args...>
-# prints value / table-free / batched figures of every run (A = the in-tree build, B = the other one)
+# prints value / table-free / batched figures of every run (A = the in-tree build, B = the other one; the table-free,
+# two-in-flight, batched and primitives figures come with bench.py --full)
 OTHER=$1; N=$2; shift 2
 for i in $(seq 1 $N); do
   for v in A B; do

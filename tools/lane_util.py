@@ -20,7 +20,7 @@ for k, v in sorted(agg.items(), key=lambda kv: -kv[1].get("SQ_INSTS_VALU", 0))[:
     n = cnt[k] or 1
     out.append({"kernel": k, "launches": n, "valu_instructions_per_launch": round(v["SQ_INSTS_VALU"] / n),
                 "lane_utilisation": round(v["SQ_THREAD_CYCLES_VALU"] / (v["SQ_INSTS_VALU"] * 64), 3)})
-json.dump({"command": "rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU SQ_WAVES -- python3 bench.py --no-cpu-baseline "
-                      "--no-primitives --steps 10 --warmup 3",
+json.dump({"command": "rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU SQ_WAVES -- python3 bench.py --full "
+                      "--no-cpu-baseline --no-primitives --steps 10 --warmup 3",
            "note": "lane utilisation = SQ_THREAD_CYCLES_VALU / (64 x SQ_INSTS_VALU)", "kernels": out},
           open(sys.argv[2], "w"), indent=1)

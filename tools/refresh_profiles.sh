@@ -17,7 +17,7 @@ if has calib; then
   rm -rf $O/calf $O/calw
 fi
 if has bench; then
-  python bench.py > $O/r06_bench_c4.json 2> $O/r06_bench_c4.err
+  python bench.py --full > $O/r06_bench_c4.json 2> $O/r06_bench_c4.err
   python bench.py --workload c2 > $O/r06_bench_c2.json 2> $O/r06_bench_c2.err
   python bench.py --workload c3 --no-tables > $O/r06_bench_c3.json 2> $O/r06_bench_c3.err     # table-free, as the c3 profile passes below
 fi
@@ -26,8 +26,8 @@ for v in c4 c4tf c2 c3 dpp dealer c5; do
   has $v || { [ $v = c4tf ] && has c4; } || continue
   P=bench.py
   case $v in
-    c4) A="--no-cpu-baseline --no-primitives --steps 20 --warmup 5";;
-    c4tf) A="--no-cpu-baseline --no-primitives --no-tables --steps 20 --warmup 5";;
+    c4) A="--full --no-cpu-baseline --no-primitives --steps 20 --warmup 5";;
+    c4tf) A="--full --no-cpu-baseline --no-primitives --no-tables --steps 20 --warmup 5";;
     c2) A="--workload c2 --no-cpu-baseline --steps 10 --warmup 3";;
     c3) A="--workload c3 --no-cpu-baseline --no-tables --steps 5 --warmup 2";;
     dpp) P=tools/dpp_bench.py; A="bn254 20 10 bls12_381 24 3";;
@@ -46,7 +46,7 @@ for v in c4 c4tf c2 c3 dpp dealer c5; do
 done
 if has c4; then
   rm -rf $O/pmc_u
-  rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU SQ_WAVES --output-format csv -d $O/pmc_u -o p -- python3 $R/bench.py --no-cpu-baseline --no-primitives --steps 10 --warmup 3 > $O/pmc_u.log 2>&1
+  rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU SQ_WAVES --output-format csv -d $O/pmc_u -o p -- python3 $R/bench.py --full --no-cpu-baseline --no-primitives --steps 10 --warmup 3 > $O/pmc_u.log 2>&1
 fi
 if has c2; then
   rm -rf $O/pmc_c2a $O/pmc_c2b

@@ -8,7 +8,7 @@ case " $PARTS " in *" c4 "*)
     for c in 13 14 15 16; do TAG="c4 msm_table_c(g1)=$c g2=15"; ZK_BENCH_OPTIONS="msm_table_c=$c,msm_table_c_g2=15" run python bench.py --no-cpu-baseline --no-primitives; done
   done
   for c in 14 15 16; do TAG="c4 g1=15 msm_table_c_g2=$c"; ZK_BENCH_OPTIONS="msm_table_c=15,msm_table_c_g2=$c" run python bench.py --no-cpu-baseline --no-primitives; done
-  for c in 15 16; do TAG="c4 full msm_table_c(g1)=$c g2=15"; ZK_BENCH_OPTIONS="msm_table_c=$c,msm_table_c_g2=15" run python bench.py --no-cpu-baseline; done;;
+  for c in 15 16; do TAG="c4 full msm_table_c(g1)=$c g2=15"; ZK_BENCH_OPTIONS="msm_table_c=$c,msm_table_c_g2=15" run python bench.py --full --no-cpu-baseline; done;;
 esac
 case " $PARTS " in *" c3 "*)
   for c in 0 14 15 16 17 18; do TAG="c3 msm_c=$c"; ZK_BENCH_OPTIONS="msm_c=$c" run python bench.py --workload c3 --no-cpu-baseline --no-tables; done;;
