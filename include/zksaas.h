@@ -246,7 +246,7 @@ int zk_msm_precompute(zk_ctx* ctx, int group, const void* bases_d, size_t len, v
 int zk_msm_forget(zk_ctx* ctx, const void* bases_d);
 int zk_msm_table_info(zk_ctx* ctx, int group, const void* bases_d, int info[2]);
 /* Tunables of this context (no reference counterpart).  "rng_replay": see "share randomness".  "msm_bigsort_min": point count from which zk_msm sorts with
- * the two-level LDS counting sort instead of global atomics (default 196608: below that the tiles of the two-level sort are too few to fill the chip; tests force both paths with it).
+ * the two-level LDS counting sort instead of global atomics (default 16384 = 2^14; tests force both paths with it).
  * "msm_table_c": window bits (8..22, 0 = default; "msm_table_c_g2" sets G2 alone) of tables built by later zk_msm_precompute calls.
  *   Default: by the vector's length -- G1 15 bits up to 2^17 points, 16 below 2^19, 17 below 2^22, 20 from there; G2 15 below 2^20, 19 from
  *   there (a table folds all windows into one bucket set: too few buckets for a long vector sends every bucket through the
@@ -266,12 +266,6 @@ int zk_msm_table_info(zk_ctx* ctx, int group, const void* bases_d, int info[2]);
  * "pack_glv": 0 = zk_pss_pack_points at two points per chunk walks the parties' full-length scalars; 1 (default) = the
  *   scalars are split by the curve's endomorphism phi(x, y) = (beta x, y) = lambda (x, y) into two half-length parts (half
  *   the doubling chain; the same points).  Before the first zk_pss_pack_points of the context.
- * "msm_skip_kernel": 1 = identity bases are found by a mask kernel of its own ahead of every sort (round 5's form) instead of
- *   by the first sort kernel looking at the bases (default 0; same results, measured equal: profiles/r06_skipfold_ab.txt).
- * "msm_sort_lo_tab": low bucket bits per bin (4..10, 0 = the default 7) of a small sort over a fixed-base table, i.e. 2^(c-1-value)
- *   bins / bin-sort workgroups (A/B only; 6 and 8 measured against 7 on the SHA-256 proof: no gain, profiles/r06_sort_bins_ab.txt).
- * "msm_acc_lds": dynamic LDS bytes (0..65536, default 0) launched with every accumulate workgroup, which caps how many of
- *   them a CU holds (measured on the SHA-256 proof: a loss at every size, profiles/r06_acc_lds_sweep.txt; kept for A/B runs).
  * Nothing is read from the environment.  Unknown name or value out of range -> ZK_ERR_BAD_INPUT. */
 int zk_ctx_set_option(zk_ctx* ctx, const char* name, long long value);
 /* Memory-model note (csrc/msm.hpp msm_hist): the last workgroup of a sort's histogram finds out that it is the last through a

@@ -104,9 +104,11 @@ def test_context_options_are_validated():
                 with pytest.raises(zk.ZkError) as e:
                     pp.set_option(name, bad)
                 assert e.value.code == 4, name
-        with pytest.raises(zk.ZkError) as e:
-            pp.set_option("no_such_option", 1)
-        assert e.value.code == 4
+        # (the last three are A/B options of round 6, removed: unknown names now)
+        for name in ("no_such_option", "msm_skip_kernel", "msm_sort_lo_tab", "msm_acc_lds"):
+            with pytest.raises(zk.ZkError) as e:
+                pp.set_option(name, 1)
+            assert e.value.code == 4, name
     finally:
         pp.close()
 
@@ -231,10 +233,11 @@ def test_deg_red_and_d_msm_with_dropout():
 
 
 @pytest.mark.parametrize("curve,group", [("bn254", ZK_G1), ("bn254", ZK_G2), ("bls12_381", ZK_G1)])
-def test_msm_both_sort_paths_agree_and_match_oracle(curve, group):
-    """The two-level LDS counting sort (default from 2^16 points) and the global-atomics sort are forced in turn on the
+def test_msm_sort_paths_agree_and_match_oracle(curve, group):
+    """The two-level LDS counting sort (default from 2^14 points) and the global-atomics sort are forced in turn on the
     same inputs through zk_ctx_set_option: random scalars (exact against the oracle), ragged length (not a multiple
-    of the 4096-point tile), zeros, r-1, all ones (one heavy bucket per window) and a duplicated base."""
+    of the 4096-point tile), zeros, r-1, all ones (one heavy bucket per window), a duplicated base and identity bases
+    (left out by the first sort kernel of either path)."""
     c = CURVES[curve]
     pp = zk.PackedSharingParams(curve, 2)          # own context: the option must not leak into other tests
     is2 = group == ZK_G2
@@ -254,10 +257,8 @@ def test_msm_both_sort_paths_agree_and_match_oracle(curve, group):
     for name, sc in cases.items():
         sc_d = up(pp, sc)
         outs = []
-        # both sorts, and the identity bases found by the histogram kernel itself (default) or by round 5's mask kernel
-        for big_min, skip_kernel in ((0, 0), (1 << 40, 0), (0, 1), (1 << 40, 1)):
+        for big_min in (0, 1 << 40):                     # the two-level sort, then the global-atomics one
             pp.set_option("msm_bigsort_min", big_min)
-            pp.set_option("msm_skip_kernel", skip_kernel)
             outs.append(dec_jacobian(pp, msm(pp, group, bases, sc_d, n), is2))
         assert all(G.eq(outs[0], o) for o in outs[1:]), name
         agg = [0] * 48                                   # sum_i s_i * P_(i mod 48), identity bases skipped

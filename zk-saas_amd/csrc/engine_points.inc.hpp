@@ -274,20 +274,6 @@
       msm_.bigsort_min = (size_t)value;
       return ZK_OK;
     }
-    if (!strcmp(name, "msm_sort_lo_tab")) {        // A/B only: low bucket bits per bin of a small sort over a fixed-base table
-      if (value != 0 && (value < 4 || value > 10)) return fail(ZK_ERR_BAD_INPUT, "msm_sort_lo_tab must be 0 or in 4..10");
-      msm_.sort_lo_tab = (int)value;
-      return ZK_OK;
-    }
-    if (!strcmp(name, "msm_skip_kernel")) {        // A/B only: identity bases through a mask kernel of its own (round 5's form)
-      msm_.skip_kernel = value != 0;
-      return ZK_OK;
-    }
-    if (!strcmp(name, "msm_acc_lds")) {            // dynamic LDS per accumulate workgroup (MsmTuning::acc_lds); 0 = none
-      if (value < 0 || value > 65536) return fail(ZK_ERR_BAD_INPUT, "msm_acc_lds must be in 0..65536");
-      msm_.acc_lds = (unsigned)value;
-      return ZK_OK;
-    }
     if (!strcmp(name, "pack_glv")) {                // det_pack over points: split the scalars by the curve's endomorphism
       std::lock_guard<std::mutex> lk(mu_);
       if (pjsf_) return fail(ZK_ERR_BAD_INPUT, "pack_glv must be set before the first zk_pss_pack_points");

@@ -81,14 +81,12 @@ struct MsmScalars {
 // Until round 6 a kernel of its own wrote a bit mask first (msm_skip_mask_kernel): 4 us alone, but on the chain of the
 // table-free U-MSM inside a proof its span read 166-195 us (its 512 four-wave workgroups waiting for wave slots among the
 // bulk accumulate waves: profiles/r06_c4tf_timeline.txt).  One launch, one dependent boundary and one buffer less now --
-// and NO change in proofs/s (same-box A/B against the mask kernel, option "msm_skip_kernel": table-free 450-452 vs 434-456,
-// with tables 645-652 vs 645-651, profiles/r06_skipfold_ab.txt): the chain waits for the chip elsewhere instead.
+// and NO change in proofs/s (same-box A/B against the mask kernel: table-free 450-452 vs 434-456, with tables 645-652 vs
+// 645-651, profiles/r06_skipfold_ab.txt): the chain waits for the chip elsewhere instead.
 struct MsmBaseId {
   const void* b0 = nullptr;   // nullptr: no base of the launch is the identity (registered vectors know: zk_msm_precompute)
   const void* b1 = nullptr;   // second base vector of the launch (own sort when ys != 0: blockIdx.y picks the vector)
   uint32_t elem16 = 0;        // bytes per affine point / 16
-  const uint32_t* skip = nullptr;   // A/B only (zk_ctx_set_option "msm_skip_kernel"): round 5's bit mask, written by a kernel of its own
-  size_t skip_ys = 0;               // ... its stride between the two sorts, in words
 };
 ZK_D bool msm_base_zero(const void* bases, uint32_t elem16, uint32_t i) {
   const uint4* p = reinterpret_cast<const uint4*>(bases) + (size_t)i * elem16;
@@ -102,7 +100,6 @@ ZK_D bool msm_base_zero(const void* bases, uint32_t elem16, uint32_t i) {
 // ys != 0 (grid.y = 2): one sort per base vector, each skips its own identities; ys == 0: one sort, a point is skipped when
 // EVERY vector holds the identity there
 ZK_D bool msm_base_is_identity(const MsmBaseId& id, uint32_t i, size_t ys) {
-  if (id.skip) return ((id.skip[(size_t)blockIdx.y * id.skip_ys + (i >> 5)] >> (i & 31)) & 1u) != 0;
   if (!id.b0) return false;
   if (ys) return msm_base_zero(blockIdx.y ? id.b1 : id.b0, id.elem16, i);
   return msm_base_zero(id.b0, id.elem16, i) && (!id.b1 || msm_base_zero(id.b1, id.elem16, i));
@@ -209,22 +206,11 @@ inline hipError_t msm_lds_attr(const void* fn, size_t bytes, int device) {
 // registered vector, to learn whether the vector holds an identity AT ALL (MsmTable::any_identity); the sorts look at the
 // bases themselves (MsmBaseId above).
 template <class Fld>
-__global__ __launch_bounds__(256) void msm_skip_mask_kernel(const Affine<Fld>* __restrict__ bases0,
-                                                            const Affine<Fld>* __restrict__ bases1, size_t npts,
-                                                            uint32_t* __restrict__ skip, size_t ys) {
-  __builtin_amdgcn_s_setprio(3);   // short sort-stage kernel: win issue arbitration against the bulk accumulate waves
-  // ys != 0 (grid.y = 2): one mask per base vector; ys == 0: one mask, set where EVERY vector holds the identity
-  ZK_YSHIFT(skip);
+__global__ __launch_bounds__(256) void msm_skip_mask_kernel(const Affine<Fld>* __restrict__ bases, size_t npts,
+                                                            uint32_t* __restrict__ skip) {
+  __builtin_amdgcn_s_setprio(3);   // short kernel: win issue arbitration against the bulk accumulate waves
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool id = false;
-  if (i < npts) {
-    if (ys) {
-      id = load_elem((blockIdx.y ? bases1 : bases0) + i).is_identity();
-    } else {
-      id = load_elem(bases0 + i).is_identity();
-      if (id && bases1) id = load_elem(bases1 + i).is_identity();
-    }
-  }
+  const bool id = i < npts && load_elem(bases + i).is_identity();
   const uint64_t m = __ballot(id);
   const int lane = threadIdx.x & 63;
   if (lane == 0 && i < npts) skip[i >> 5] = (uint32_t)m;
@@ -384,8 +370,6 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_hist_kernel(MsmScalars<Fp<FrP
                                                                int lo_bits, int ppt, uint32_t tiles_per_vec,
                                                                uint32_t wmask /* 0: fixed-base table, all windows
                                                                share one bucket set; ~0: one set per window */,
-                                                               int w_begin /* the launch sorts windows [w_begin, nwin)
-                                                               only (a window group of a split MSM): set = w - w_begin */,
                                                                uint32_t* __restrict__ bins,
                                                                MsmBaseId bid,
                                                                Fp<FrP>* __restrict__ canon,
@@ -407,7 +391,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_hist_kernel(MsmScalars<Fp<FrP
   // the identity tests of the thread's points first: independent loads, in flight together (inside the loop below each
   // would sit in front of its scalar's load: two dependent memory latencies per point)
   uint32_t idmask = 0;
-  if (bid.b0 || bid.skip)
+  if (bid.b0)
     for (int k = 0; k < ppt; k++) {
       const uint32_t i = pt0 + (uint32_t)k * BIG_THREADS + threadIdx.x;
       if (i < sc.npts && msm_base_is_identity(bid, i, ys)) idmask |= 1u << k;
@@ -419,7 +403,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_hist_kernel(MsmScalars<Fp<FrP
     const Fp<FrP> s = ((idmask >> k) & 1u) ? Fp<FrP>::zero() : msm_canon_scalar<FrP>(sc, coef, part_len, vb, i, no_id, ys);
     store_elem(canon + (size_t)vb * sc.npts + i, s);
     msm_for_each_digit<FrP>(s, c, nwin, wide, [&](int w, uint32_t b, uint32_t) {
-      if (w >= w_begin) atomicAdd(&big_lds[(((uint32_t)(w - w_begin) & wmask) << hi_bits) | (b >> lo_bits)], 1u);
+      atomicAdd(&big_lds[(((uint32_t)w & wmask) << hi_bits) | (b >> lo_bits)], 1u);
     });
   }
   __syncthreads();
@@ -496,7 +480,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_hist_kernel(MsmScalars<Fp<FrP
 template <class FrP, bool WIDE>
 __global__ __launch_bounds__(BIG_THREADS) void msm_scatter_direct_kernel(MsmScalars<Fp<FrP>> sc, int c, int nwin, int wide,
                                                                          int hi_bits, int lo_bits, int ppt,
-                                                                         uint32_t tiles_per_vec, uint32_t wmask, int w_begin,
+                                                                         uint32_t tiles_per_vec, uint32_t wmask,
                                                                          uint32_t pre_stride, uint32_t pre_off,
                                                                          int idx_bits, uint32_t* __restrict__ bins,
                                                                          uint32_t* __restrict__ tmp,
@@ -522,7 +506,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_scatter_direct_kernel(MsmScal
     const uint32_t i = pt0 + (uint32_t)k * BIG_THREADS + threadIdx.x;
     if (i >= sc.npts) break;
     msm_for_each_digit<FrP>(load_elem(my + i), c, nwin, wide, [&](int w, uint32_t b, uint32_t) {
-      if (w >= w_begin) atomicAdd(&cnt[(((uint32_t)(w - w_begin) & wmask) << hi_bits) | (b >> lo_bits)], 1u);
+      atomicAdd(&cnt[(((uint32_t)w & wmask) << hi_bits) | (b >> lo_bits)], 1u);
     });
   }
   __syncthreads();
@@ -537,8 +521,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_scatter_direct_kernel(MsmScal
     const uint32_t i = pt0 + (uint32_t)k * BIG_THREADS + threadIdx.x;
     if (i >= sc.npts) break;
     msm_for_each_digit<FrP>(load_elem(my + i), c, nwin, wide, [&](int w, uint32_t b, uint32_t neg) {
-      if (w < w_begin) return;
-      const uint32_t lbin = (((uint32_t)(w - w_begin) & wmask) << hi_bits) | (b >> lo_bits);
+      const uint32_t lbin = (((uint32_t)w & wmask) << hi_bits) | (b >> lo_bits);
       const uint32_t dst = gbase[lbin] + atomicAdd(&cnt[lbin], 1u);
       const uint32_t idx = pre_stride ? (uint32_t)w * pre_stride + pre_off + i : i;
       if (WIDE) {
@@ -554,7 +537,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_scatter_direct_kernel(MsmScal
 // Entry formats of tmp[]: packed = {index : idx_bits, sign : 1, low bucket bits}; wide = {index | sign << 31} + 16-bit low part
 template <class FrP, int THR, int PPT, bool WIDE>
 __global__ __launch_bounds__(THR) void msm_scatter_kernel(MsmScalars<Fp<FrP>> sc, int c, int nwin, int wide, int hi_bits,
-                                                          int lo_bits, uint32_t tiles_per_vec, uint32_t wmask, int w_begin,
+                                                          int lo_bits, uint32_t tiles_per_vec, uint32_t wmask,
                                                           int wgroup /* windows per round */, uint32_t pre_stride,
                                                           uint32_t pre_off, int idx_bits, uint32_t stage_cap,
                                                           uint32_t* __restrict__ bins, uint32_t* __restrict__ tmp,
@@ -592,7 +575,7 @@ __global__ __launch_bounds__(THR) void msm_scatter_kernel(MsmScalars<Fp<FrP>> sc
       const uint32_t i = pt0 + (uint32_t)k * THR + threadIdx.x;
       if (i < sc.npts)
         msm_for_each_digit<FrP>(load_elem(my + i), c, nwin, wide, [&](int w, uint32_t b, uint32_t) {
-          if (w >= w_begin) atomicAdd(&cur[(((uint32_t)(w - w_begin) & wmask) << hi_bits) | (b >> lo_bits)], 1u);
+          atomicAdd(&cur[(((uint32_t)w & wmask) << hi_bits) | (b >> lo_bits)], 1u);
         });
     }
   }
@@ -624,16 +607,11 @@ __global__ __launch_bounds__(THR) void msm_scatter_kernel(MsmScalars<Fp<FrP>> sc
     const uint32_t i = pt0 + (uint32_t)k * THR + threadIdx.x;
     s[k] = i < sc.npts ? load_elem(my + i) : Fp<FrP>::zero();
     carry[k] = 0;
-    for (int w = 0; w < w_begin; w++) {          // the windows of another group: only their carry matters here
-      uint32_t b, neg;
-      (void)msm_next_digit<FrP>(s[k], carry[k], w < wide ? c : c - 1, &b, &neg);
-    }
   }
   const uint32_t lo_mask = (1u << lo_bits) - 1;
-  for (int w0 = w_begin; w0 < nwin; w0 += wgroup) {
+  for (int w0 = 0; w0 < nwin; w0 += wgroup) {
     const int w1 = w0 + wgroup < nwin ? w0 + wgroup : nwin;
-    const uint32_t lb_lo = ((uint32_t)(w0 - w_begin) & wmask) << hi_bits,
-                   lb_hi = ((((uint32_t)(w1 - w_begin) - 1) & wmask) + 1) << hi_bits;
+    const uint32_t lb_lo = ((uint32_t)w0 & wmask) << hi_bits, lb_hi = ((((uint32_t)w1 - 1) & wmask) + 1) << hi_bits;
     const uint32_t r0 = cur[lb_lo], r1 = lb_hi < nbl ? cur[lb_hi] : tile_total;     // untouched so far: bins of this round
     __syncthreads();
 #pragma unroll
@@ -642,7 +620,7 @@ __global__ __launch_bounds__(THR) void msm_scatter_kernel(MsmScalars<Fp<FrP>> sc
       for (int w = w0; w < w1; w++) {
         uint32_t b, neg;
         if (!msm_next_digit<FrP>(s[k], carry[k], w < wide ? c : c - 1, &b, &neg)) continue;
-        const uint32_t lbin = (((uint32_t)(w - w_begin) & wmask) << hi_bits) | (b >> lo_bits);
+        const uint32_t lbin = (((uint32_t)w & wmask) << hi_bits) | (b >> lo_bits);
         const uint32_t j = atomicAdd(&cur[lbin], 1u) - r0;
         const uint32_t idx = pre_stride ? (uint32_t)w * pre_stride + pre_off + i : i;
         if (WIDE) {
@@ -935,14 +913,10 @@ static __global__ __launch_bounds__(ISCAN_THREADS) void iscan_carry_kernel(uint3
 // between the field multiplications to shorten live ranges) was measured and rejected: 0.96 ms against 0.73 ms per
 // 52k-point launch -- with so few waves the multiplier needs the instruction-level parallelism across independent
 // field multiplications more than it needs a second wave.
-#ifndef ZK_ACC_WAVES_12
-#define ZK_ACC_WAVES_12 3
-#endif
-#ifndef ZK_ACC_WAVES_8
-#define ZK_ACC_WAVES_8 4          // round 4: 128 VGPRs with the lazy mixed addition (4 dwords of scratch, read twice per step)
-#endif
+// Base-field (G1) kernel only: 12-limb fields 3 waves; 8-limb fields 4 since round 4 (128 VGPRs with the lazy mixed
+// addition, 4 dwords of scratch read twice per step)
 template <class Fld>
-constexpr int ACC_WAVES = sizeof(Fld) == 48 ? ZK_ACC_WAVES_12 : ZK_ACC_WAVES_8;       // base-field (G1) kernel only
+constexpr int ACC_WAVES = sizeof(Fld) == 48 ? 3 : 4;
 // BALANCED PARTITION.  The sorted entry array (offsets[nkeys] entries, grouped by bucket) is cut into `nlanes`
 // contiguous ranges of T = ceil(entries / nlanes) entries, one per lane (per lane pair in G2), whatever the bucket
 // boundaries are: every lane of the launch performs the same number of mixed additions, so a wave has no idle lanes
@@ -1035,19 +1009,16 @@ ZK_D void msm_report_heavy(uint32_t* __restrict__ heavy, uint32_t k, uint32_t L)
 inline size_t msm_heavy_cap(size_t nlanes) { return nlanes / FIN_SEQ + 8; }
 inline size_t msm_heavy_vcap(size_t nlanes) { return nlanes / FIN_SEQ + nlanes / 256 + 8; }
 
-// Base fields whose running sums the accumulate kernel keeps as lazy residues (field.hpp, LAZY_OK); ZK_ACC_LAZY=0 at build
-// time restores the canonical form.  Same-box A/B on BN254 (profiles/r04_acc_lazy_ab.txt): d_msm 8 x 2^20 12.40 against
-// 12.78 ms (-3 %), C4 599 against 592 proofs/s when compiled for four waves (at three waves the kernel takes 140
-// VGPRs and the table-free proof, whose MSMs overlap, loses 4 %).  The 12-limb base fields are left canonical: there
-// the lazy form spills (20 / 39 dwords at three waves) and C5 measures 1.31 against 1.285 s.
-#ifndef ZK_ACC_LAZY
-#define ZK_ACC_LAZY 1
-#endif
+// Base fields whose running sums the accumulate kernel keeps as lazy residues (field.hpp, LAZY_OK) instead of the
+// canonical form.  Same-box A/B on BN254 (profiles/r04_acc_lazy_ab.txt): d_msm 8 x 2^20 12.40 against 12.78 ms (-3 %),
+// C4 599 against 592 proofs/s when compiled for four waves (at three waves the kernel takes 140 VGPRs and the
+// table-free proof, whose MSMs overlap, loses 4 %).  The 12-limb base fields are left canonical: there the lazy form
+// spills (20 / 39 dwords at three waves) and C5 measures 1.31 against 1.285 s.
 template <class F>
 constexpr bool acc_lazy_v = false;
 #if defined(__HIP_DEVICE_COMPILE__)
 template <class P>
-constexpr bool acc_lazy_v<Fp<P>> = ZK_ACC_LAZY && Fp<P>::LAZY_OK && P::N <= 8;      // (the lazy operations exist in the device pass only)
+constexpr bool acc_lazy_v<Fp<P>> = Fp<P>::LAZY_OK && P::N <= 8;      // (the lazy operations exist in the device pass only)
 #endif
 
 template <class Fld>
@@ -1523,7 +1494,6 @@ struct MsmBatchArg {
 struct MsmPending {
   bool active = false;
   int kwin = 0, c = 0, wide = 0, nb = 1, lo_bits = 0;
-  int w0 = 0;                                    // first window of the launch (a window group of a split MSM)
   bool tabbed = false;                           // fixed-base table: one bucket set, every window c bits wide
   int batch = 1;                                 // scalar vectors of the launch (results: [base vector][batch])
   size_t stats_off = 0, offered = 0;             // statistics: where the sorts' entry counts land in the pinned buffer;
@@ -1555,12 +1525,9 @@ struct MsmTuning {
   size_t bigsort_min;
   MsmGate gate;
   int c_force = 0;       // window bits asked for by zk_ctx_set_option "msm_c" / "msm_c_g2" (0: the cost model)
-  // dynamic LDS bytes asked for with every accumulate workgroup (zk_ctx_set_option "msm_acc_lds"; the kernels use none):
-  // caps the accumulate workgroups a CU holds, i.e. leaves wave slots and registers free for the short kernels of a
-  // proof's critical chain, which otherwise wait for an accumulate wave to retire before they can become resident
-  unsigned acc_lds = 0;
-  bool skip_kernel = false;   // A/B only: identity bases through round 5's separate mask kernel instead of MsmBaseId's test
-  int sort_lo_tab = 0;        // A/B only (zk_ctx_set_option "msm_sort_lo_tab"): low bucket bits per bin of a small TABLE sort (0 = 7)
+  // (The accumulate kernels are launched without dynamic LDS.  Asking for some caps the accumulate workgroups a CU holds,
+  // which leaves wave slots and registers free for the short kernels of a proof's critical chain: measured in round 6 with
+  // 23 / 27 / 33 KB, a loss at every size -- the gather-bound accumulate needs its waves more, profiles/r06_acc_lds_sweep.txt.)
 };
 
 // Window width: minimise nwin * (npts + 4 * buckets) -- mixed additions plus the per-bucket reduction work --
@@ -1687,7 +1654,7 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
     XYZZ<Fld> total = XYZZ<Fld>::identity();
     for (int w = w_hi; w >= w_lo; w--) {
       const XYZZ<Fld>* sl = h + (size_t)w * nslices;
-      const int cw = (p.tabbed || w + p.w0 < wide) ? c : c - 1;
+      const int cw = (p.tabbed || w < wide) ? c : c - 1;
       for (int t = cw - 1; t >= 0; t--) {
         total = xyzz_dbl_ni(total);
         const XYZZ<Fld>& s = t >= lo_bits ? sl[t - lo_bits] : sl[hb + 1 + t];
@@ -1698,7 +1665,7 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
   };
   auto width_of = [&](int w_hi, int w_lo) {
     int bits = 0;
-    for (int w = w_hi; w >= w_lo; w--) bits += (p.tabbed || w + p.w0 < wide) ? c : c - 1;
+    for (int w = w_hi; w >= w_lo; w--) bits += (p.tabbed || w < wide) ? c : c - 1;
     return bits;
   };
   // Table-free MSMs have one bucket set per window: ~250 doublings + c additions per window on one host thread
@@ -1706,7 +1673,6 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
   // contiguous groups in parallel (below).  (With a fixed-base table there is one window and nothing to split.)
   constexpr int FOLD_PARTS_MAX = 8;
   HostPool* pool = eng->host_pool();
-  constexpr bool par_fold = true;
   // bucket sets of (base vector v, scalar vector b) start at hall + ((v * batch + b) * kwin) * nslices
   auto sets_of = [&](int v, int b) { return hall + ((size_t)v * batch + b) * kwin * nslices; };
   // only with free workers for every sub-task: this may itself be a pool task, and waiting for sub-tasks that nobody can
@@ -1714,7 +1680,7 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
   if (batch > 1) {
     // a batch: one fold per (v, b); table-free folds (kwin > 1) are spread over free workers
     const int jobs = nvec * batch;
-    if (kwin > 1 && pool && par_fold && pool->idle() >= jobs) {
+    if (kwin > 1 && pool && pool->idle() >= jobs) {
       std::vector<std::future<void>> futs;
       for (int i = 1; i < jobs; i++) {
         XYZZ<Fld>* dst = results + i;
@@ -1729,7 +1695,7 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
     }
     return ZK_OK;
   }
-  const int max_parts = !pool || !par_fold ? 1 : std::min({FOLD_PARTS_MAX, kwin / 2, (pool->idle() + 1) / std::max(nvec, 1)});
+  const int max_parts = !pool ? 1 : std::min({FOLD_PARTS_MAX, kwin / 2, (pool->idle() + 1) / std::max(nvec, 1)});
   if (max_parts < 2) {
     for (int v = 0; v < nvec; v++) results[v] = fold_range(sets_of(v, 0), kwin - 1, 0);
     return ZK_OK;
@@ -1843,7 +1809,7 @@ class MsmRunner {
                const MsmBatchArg* batch = nullptr) {
     if (wslot < 0 || wslot >= MSM_WS) return eng->fail(ZK_ERR_BAD_INPUT, "bad msm workspace slot");
     if (pend->active) return eng->fail(ZK_ERR_GENERIC, "msm workspace slot still in flight");
-    MsmTuning tune{bigsort_min, gate, IsExtField<Fld>::value ? c_g2 : c_g1, acc_lds, skip_kernel, sort_lo_tab};
+    MsmTuning tune{bigsort_min, gate, IsExtField<Fld>::value ? c_g2 : c_g1};
     return msm_launch<FrP, Fld>(eng, slots_[wslot], tune, bases, bases2, scalars, npts, coef_d, part_len, st, pend,
                                 batch);
   }
@@ -2067,14 +2033,13 @@ class MsmRunner {
     he = hipStreamSynchronize(st);
     if (he != hipSuccess) return eng->hip_fail(he, "msm_table_kernel");
     {
-      // does the vector hold any identity at all?  (once, here: an MSM over a vector without one skips the mask kernel)
+      // does the vector hold any identity at all?  (once, here: an MSM over a vector without one skips the identity test)
       using KF = typename KernelField<Fld>::type;
       const size_t words = ((len + 63) / 64) * 2;
       uint32_t* mask_d = nullptr;
       he = hipMalloc(&mask_d, words * 4);
       if (he != hipSuccess) return eng->hip_fail(he, "identity mask");
-      msm_skip_mask_kernel<KF><<<dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st>>>((const Affine<KF>*)bases, nullptr, len,
-                                                                                       mask_d, 0);
+      msm_skip_mask_kernel<KF><<<dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st>>>((const Affine<KF>*)bases, len, mask_d);
       std::vector<uint32_t> mask_h(words);
       he = hipMemcpyAsync(mask_h.data(), mask_d, words * 4, hipMemcpyDeviceToHost, st);
       if (he == hipSuccess) he = hipStreamSynchronize(st);
@@ -2098,9 +2063,6 @@ class MsmRunner {
 
   // two-level sort from this many points on (zk_ctx_set_option "msm_bigsort_min")
   size_t bigsort_min = (size_t)1 << 14;
-  unsigned acc_lds = 0;           // zk_ctx_set_option "msm_acc_lds" (MsmTuning::acc_lds)
-  bool skip_kernel = false;       // zk_ctx_set_option "msm_skip_kernel" (MsmTuning::skip_kernel)
-  int sort_lo_tab = 0;            // zk_ctx_set_option "msm_sort_lo_tab" (MsmTuning::sort_lo_tab)
   MsmSlot slots_[MSM_WS];
   Fr* coef_d_ = nullptr;
   std::vector<Fr> coef_h_;

@@ -40,14 +40,10 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
   const int c = (T + nwin - 1) / nwin;            // widest window
   const int wide = T - nwin * (c - 1);            // 1 <= wide <= nwin
   const uint32_t B = 1u << (c - 1);
-  // the kernels sort and sum a window range [w_begin, w_end): every launch covers all of them (a split into window groups
-  // on two streams was measured in round 4 and removed, see MsmRunner)
-  const int w_begin = 0, w_end = nwin;
-  const int nwin_r = w_end - w_begin;
-  const int kwin = tab ? 1 : nwin_r;              // bucket sets per scalar vector: with a table all windows share one
+  const int kwin = tab ? 1 : nwin;                // bucket sets per scalar vector: with a table all windows share one
   const size_t nsets = batch * (size_t)kwin;      // bucket sets of the launch
   const size_t nkeys = nsets * B;
-  const size_t max_sorted = npts * batch * nwin_r;
+  const size_t max_sorted = npts * batch * nwin;
   if (max_sorted >= ((size_t)1 << 32)) return eng->fail(ZK_ERR_BAD_INPUT, "msm too large (points x windows >= 2^32)");
   const uint32_t pre_stride = tab ? (uint32_t)tab->len : 0u, pre_off = tab ? (uint32_t)toff : 0u;
   // accumulate lanes (msm.hpp "balanced partition"): every lane adds the same number of sorted entries
@@ -75,7 +71,6 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
   // Two base vectors over the same scalars then get their OWN sorts (their identities differ: a fused sort could only
   // skip a point that is the identity in both) -- same kernels, grid.y = 2, the sort-stage arrays in two copies of one
   // workspace region (ZK_YSHIFT in the kernels).
-  constexpr bool skip_on = true;
   // registered vectors know whether they hold an identity at all (zk_msm_precompute): without one there is no mask
   const bool none = tab && !tab->any_identity && (NB == 1 || (tab2 && !tab2->any_identity));
   const unsigned NS = (NB == 2 && !none) ? 2u : 1u;       // sorts of this launch
@@ -91,8 +86,9 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
   if (large && tab)
     while (ppt > 1 && (size_t)nwin * sthr * ppt > stage_max) ppt >>= 1;       // with a table the whole tile is one round
   // small launches: at least 7 low bits per bin (a table-free proof has 12-bit buckets in 20 sets: 8 top bits made 5120
-  // bins of 16 buckets, one workgroup each -- measured 428 -> 442-447 proofs/s table-free with 5 top bits)
-  int sort_hi = std::min(msm_big_hi(nsets), std::max(1, c - 1 - (tab && tune.sort_lo_tab ? tune.sort_lo_tab : 7))), sort_lo;
+  // bins of 16 buckets, one workgroup each -- measured 428 -> 442-447 proofs/s table-free with 5 top bits; the proof's
+  // table sorts with 6 or 8 low bits instead of 7: no gain, profiles/r06_sort_bins_ab.txt)
+  int sort_hi = std::min(msm_big_hi(nsets), std::max(1, c - 1 - 7)), sort_lo;
   if (large) {
     // runs of level 1 are (tile entries per bucket set) / 2^hi long, runs of level 2 (chunk) / 2^lo: balance them
     auto lg = [](size_t v) { int l = 0; while (((size_t)1 << (l + 1)) <= v) l++; return l; };
@@ -126,7 +122,6 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
          o_bins = take(big ? msm_bins_words(nbins_tot) * 4 : 0),     // right behind the heavy list: one zeroing launch
          o_cursor = take(nkeys * 4), o_offsets = take((nkeys + 1) * 4), o_bt = take(iscan_blocks * 4),
          o_sorted = take(max_sorted * 4);
-  const size_t o_skip = take(((npts + 63) / 64) * 8);
   const size_t o_k0 = take((size_t)nlanes * 4);                // first bucket of every accumulate lane
   const size_t o_canon = take(npts * batch * sizeof(Fr));      // canonical scalars (written by the first sort pass)
   size_t o_tmp = 0, o_tmp_lo = 0, o_tcnt = 0;
@@ -195,7 +190,7 @@ do {                                                                           \
   // heavy-bucket counter
   if (big) MSM_HIP(msm_zero(heavy, o_bins + (nbins_tot + 1) * 4 - o_heavy, st, NS, ys));
   else MSM_HIP(msm_zero(counts, o_heavy + 16 - o_counts, st, NS, ys));
-  dim3 pg((unsigned)((npts + 255) / 256), NS), pb(256);
+  dim3 pb(256);
   dim3 pgb((unsigned)((npts * batch + 255) / 256), NS);     // one thread per (scalar vector, point)
   MsmScalars<Fr> sc{};
   for (size_t b = 0; b < batch; b++) sc.p[b] = (const Fr*)(ba ? ba->p[b] : scalars);
@@ -205,16 +200,10 @@ do {                                                                           \
   Fr* canon = (Fr*)(ws + o_canon);
   // identity bases: the first sort-stage kernel looks at the caller's points itself (msm.hpp MsmBaseId)
   MsmBaseId bid;
-  if (skip_on && !none) {
+  if (!none) {
     bid.b0 = bases_in;
     bid.b1 = bases2_in;
     bid.elem16 = (uint32_t)(sizeof(Affine<KF>) / 16);
-    if (tune.skip_kernel) {
-      uint32_t* skip = (uint32_t*)(ws + o_skip);
-      msm_skip_mask_kernel<KF><<<pg, pb, 0, st>>>((const Affine<KF>*)bases_in, (const Affine<KF>*)bases2_in, npts, skip, ys);
-      bid.skip = skip;
-      bid.skip_ys = ys / 4;
-    }
   }
   const size_t plen = part_len ? part_len : npts;
   {
@@ -232,7 +221,7 @@ do {                                                                           \
       const size_t hl = (nbins_tot + BIG_THREADS / 64) * 4;      // tile histogram (one vector's bins); all bins for the last workgroup's scan
       if (hl > 48 * 1024) MSM_HIP(msm_lds_attr((const void*)msm_hist_kernel<FrP>, hl, eng->device));
       msm_hist_kernel<FrP><<<dim3(tpv * (unsigned)batch, NS), dim3(BIG_THREADS), hl, st>>>(
-          sc, coef_d, plen, c, w_end, wide, sort_hi, sort_lo, hp, tpv, wmask, w_begin, bins, bid, canon, tcnt, ys);
+          sc, coef_d, plen, c, nwin, wide, sort_hi, sort_lo, hp, tpv, wmask, bins, bid, canon, tcnt, ys);
     }
     if (large) {
       const unsigned tpv = (unsigned)((npts + tile_pts - 1) / tile_pts);
@@ -243,7 +232,7 @@ do {                                                                           \
   do {                                                                                                                 \
     if (l1 > 48 * 1024) MSM_HIP(msm_lds_attr((const void*)msm_scatter_kernel<FrP, 1024, P_, W_>, l1, eng->device));    \
     msm_scatter_kernel<FrP, 1024, P_, W_><<<dim3(tpv * (unsigned)batch, NS), dim3(1024), l1, st>>>(                    \
-        sc, c, w_end, wide, sort_hi, sort_lo, tpv, wmask, w_begin, wgroup, pre_stride, pre_off, idx_bits, (uint32_t)stage_cap,   \
+        sc, c, nwin, wide, sort_hi, sort_lo, tpv, wmask, wgroup, pre_stride, pre_off, idx_bits, (uint32_t)stage_cap,   \
         bins, tmp, tmp_lo, canon, tcnt, ys);                                                                           \
   } while (0)
 #define ZK_SCATTER_P(P_)                  \
@@ -266,10 +255,10 @@ do {                                                                           \
       if (l1 > 48 * 1024) MSM_HIP(msm_lds_attr(wide_fmt ? (const void*)msm_scatter_direct_kernel<FrP, true> : (const void*)msm_scatter_direct_kernel<FrP, false>, l1, eng->device));
       if (wide_fmt)
         msm_scatter_direct_kernel<FrP, true><<<dim3(tpv * (unsigned)batch, NS), dim3(BIG_THREADS), l1, st>>>(
-            sc, c, w_end, wide, sort_hi, sort_lo, ppt, tpv, wmask, w_begin, pre_stride, pre_off, idx_bits, bins, tmp, tmp_lo, canon, ys);
+            sc, c, nwin, wide, sort_hi, sort_lo, ppt, tpv, wmask, pre_stride, pre_off, idx_bits, bins, tmp, tmp_lo, canon, ys);
       else
         msm_scatter_direct_kernel<FrP, false><<<dim3(tpv * (unsigned)batch, NS), dim3(BIG_THREADS), l1, st>>>(
-            sc, c, w_end, wide, sort_hi, sort_lo, ppt, tpv, wmask, w_begin, pre_stride, pre_off, idx_bits, bins, tmp, tmp_lo, canon, ys);
+            sc, c, nwin, wide, sort_hi, sort_lo, ppt, tpv, wmask, pre_stride, pre_off, idx_bits, bins, tmp, tmp_lo, canon, ys);
     }
     const size_t l2 = (2 * ((size_t)1 << sort_lo) + 1 + (size_t)(sthr / 64)) * 4 + (large ? (size_t)sthr * BIG_EPT * 6 : 0);
 #define ZK_BINSORT(THR_, W_, S_)                                                                                      \
@@ -325,10 +314,10 @@ do {                                                                           \
     MSM_HIP(hipStreamWaitEvent(st, tune.gate.wait_ev, 0));
   }
   if constexpr (G2FLD) {
-    msm_accumulate_split_kernel<typename BaseParams<Fld>::type><<<dim3((nlanes + 31) / 32, NB), dim3(128), tune.acc_lds, st>>>(
+    msm_accumulate_split_kernel<typename BaseParams<Fld>::type><<<dim3((nlanes + 31) / 32, NB), dim3(128), 0, st>>>(
         bases, bases2, sorted, offsets, (uint32_t)nkeys, nlanes, tmin, cap, buckets, edge, heavy, k0, ys);
   } else {
-    msm_accumulate_kernel<KF><<<dim3((nlanes + 127) / 128, NB), dim3(128), tune.acc_lds, st>>>(
+    msm_accumulate_kernel<KF><<<dim3((nlanes + 127) / 128, NB), dim3(128), 0, st>>>(
         (const Affine<KF>*)bases, (const Affine<KF>*)bases2, sorted, offsets, (uint32_t)nkeys, nlanes, tmin, cap, buckets, edge,
         heavy, k0, ys, 0);
   }
@@ -398,8 +387,7 @@ do {                                                                           \
   pend->stats_off = out_bytes;
   pend->nsorts = (int)NS;
   pend->g2 = G2FLD;
-  pend->offered = npts * batch * NB * (size_t)nwin_r;
-  pend->w0 = w_begin;
+  pend->offered = npts * batch * NB * (size_t)nwin;
   pend->tabbed = (bool)tab;
   pend->tab = std::move(tab);
   pend->tab2 = std::move(tab2);

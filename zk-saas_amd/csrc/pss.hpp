@@ -19,12 +19,6 @@ namespace zk {
 #if defined(__HIPCC__)
 
 constexpr int KING_THREADS = 256;
-// The king kernels of d_fft / deg_red reach unpack2 through the one-reduction dot product (Fp::dot_k) or through one
-// product per term: build-time choice for same-box A/B runs (tools/ab.sh), see DESIGN.md "unpack2 as dot products".
-#ifndef ZK_KING_DOT
-#define ZK_KING_DOT 1
-#endif
-constexpr bool KING_DOT = ZK_KING_DOT != 0;
 // One-wave workgroups for the short kernels of a Groth16 proof (NTT passes on 2^8-element tiles, king / deg_red / vec
 // kernels, workspace zeroing), so that a workgroup fits any single wave slot the concurrent MSM accumulate kernels free:
 // a 512-thread / 64 KB NTT workgroup needs a whole CU to drain and waited 0.7-1.9 ms for a 0.07 ms pass.  While the proof
@@ -103,13 +97,14 @@ ZK_D void unpack_term(F* sec, const F* __restrict__ U, int np, int s, const F& x
   for (int i = 0; i < L; i++) sec[i] = sec[i] + mulsel<L>(U[i * np + s], x);
 }
 // sec[i] += sum over one group of G rows, as L dot products with one reduction each (Fp::dot_k): the rows of U are
-// wave-uniform, so its limbs are the scalar operands of the multiply instructions
+// wave-uniform, so its limbs are the scalar operands of the multiply instructions.  (One product per term instead was
+// measured: a loss, d_fft 2^20 0.687 against 0.651 ms -- DESIGN.md §3 "dot_k".)
 template <class F, int L, int G>
 ZK_D void unpack_group(F* sec, const F* __restrict__ U, int np, int s0, const F* const* x) {
 #pragma unroll
   for (int i = 0; i < L; i++) sec[i] = sec[i] + F::template dot_k<G>(x, U + i * np + s0);
 }
-template <class F, int L, bool DOT = true, class RowFn>
+template <class F, int L, class RowFn>
 ZK_D void unpack_accumulate(F* sec, const F* __restrict__ U, int np, RowFn row) {
   constexpr int N = 4 * L, G = N < 8 ? N : 8;
   if (np % G == 0) {
@@ -119,7 +114,7 @@ ZK_D void unpack_accumulate(F* sec, const F* __restrict__ U, int np, RowFn row) 
       const F x0 = row(s0), x1 = row(s0 + 1), x2 = row(s0 + 2), x3 = row(s0 + 3);
       if constexpr (G == 8) {
         const F x4 = row(s0 + 4), x5 = row(s0 + 5), x6 = row(s0 + 6), x7 = row(s0 + 7);
-        if constexpr (L <= 2 && DOT) {
+        if constexpr (L <= 2) {
           const F* const xs[8] = {&x0, &x1, &x2, &x3, &x4, &x5, &x6, &x7};
           unpack_group<F, L, 8>(sec, U, np, s0, xs);
         } else {
@@ -132,14 +127,9 @@ ZK_D void unpack_accumulate(F* sec, const F* __restrict__ U, int np, RowFn row) 
           unpack_term<F, L>(sec, U, np, s0 + 6, x6);
           unpack_term<F, L>(sec, U, np, s0 + 7, x7);
         }
-      } else if constexpr (DOT) {
+      } else {
         const F* const xs[4] = {&x0, &x1, &x2, &x3};
         unpack_group<F, L, 4>(sec, U, np, s0, xs);
-      } else {
-        unpack_term<F, L>(sec, U, np, s0, x0);
-        unpack_term<F, L>(sec, U, np, s0 + 1, x1);
-        unpack_term<F, L>(sec, U, np, s0 + 2, x2);
-        unpack_term<F, L>(sec, U, np, s0 + 3, x3);
       }
     }
     return;
@@ -276,14 +266,14 @@ __global__ __launch_bounds__(KING_THREADS, 4) void king_fft2_kernel(
     const F* __restrict__ col = seg ? in + (blockIdx.x * Wc + tid) : in + k;
     const size_t pitch = seg ? (size_t)seg : (kb.row_pitch ? kb.row_pitch : (size_t)1 << log_lc);
     if (!in_mask) {
-      unpack_accumulate<F, L, KING_DOT>(v, U, np, [&](int s) { return load_elem(col + (size_t)s * pitch); });
+      unpack_accumulate<F, L>(v, U, np, [&](int s) { return load_elem(col + (size_t)s * pitch); });
     } else if (!in_scale) {
-      unpack_accumulate<F, L, KING_DOT>(v, U, np, [&](int s) {
+      unpack_accumulate<F, L>(v, U, np, [&](int s) {
         return load_elem(col + (size_t)s * pitch) + load_elem(in_mask + ((size_t)s << log_lc) + k);
       });
     } else {
       const F sc = load_elem(in_scale);
-      unpack_accumulate<F, L, KING_DOT>(v, U, np, [&](int s) {
+      unpack_accumulate<F, L>(v, U, np, [&](int s) {
         return mulsel<L>(load_elem(col + (size_t)s * pitch), sc) + load_elem(in_mask + ((size_t)s << log_lc) + k);
       });
     }
@@ -464,18 +454,18 @@ __global__ __launch_bounds__(KING_THREADS, 4) void king_degred_kernel(
   for (int i = 0; i < L; i++) sec[i] = F::zero();
   // one branch-free row function per case (see king_fft2_kernel)
   if (!mul_b && !in_mask) {
-    unpack_accumulate<F, L, KING_DOT>(sec, U, np, [&](int s) { return load_elem(in + (size_t)s * stride + j); });
+    unpack_accumulate<F, L>(sec, U, np, [&](int s) { return load_elem(in + (size_t)s * stride + j); });
   } else if (!mul_b) {
-    unpack_accumulate<F, L, KING_DOT>(sec, U, np, [&](int s) {
+    unpack_accumulate<F, L>(sec, U, np, [&](int s) {
       return load_elem(in + (size_t)s * stride + j) + load_elem(in_mask + (size_t)s * stride + j);
     });
   } else if (!in_mask) {
-    unpack_accumulate<F, L, KING_DOT>(sec, U, np, [&](int s) {
+    unpack_accumulate<F, L>(sec, U, np, [&](int s) {
       return load_elem(in + (size_t)s * stride + j) * load_elem(mul_b + (size_t)s * stride + j) -
              load_elem(sub_c + (size_t)s * stride + j);
     });
   } else {
-    unpack_accumulate<F, L, KING_DOT>(sec, U, np, [&](int s) {
+    unpack_accumulate<F, L>(sec, U, np, [&](int s) {
       return load_elem(in + (size_t)s * stride + j) * load_elem(mul_b + (size_t)s * stride + j) -
              load_elem(sub_c + (size_t)s * stride + j) + load_elem(in_mask + (size_t)s * stride + j);
     });
