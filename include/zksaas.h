@@ -257,11 +257,13 @@ int zk_msm_table_info(zk_ctx* ctx, int group, const void* bases_d, int info[2]);
  * "msm_c" / "msm_c_g2": window bits (2..20, 0 = the cost model) of table-free MSMs (tests force widths with it).
  * "h_first_log_m": domains of 2^value and up run circom_h and every MSM's sort ahead of the accumulate kernels (default 20).
  * "host_threads": workers of the context's host pool (0 = by the core count, else >= 4; before the first proof).
- * "wait_deadline_ms": bound of every host-side wait inside the prover entry points (an MSM chain's completion event, a gate
- *   between two launching threads, a pool task; default 120000, 0 = unbounded).  On expiry the call returns ZK_ERR_GENERIC
- *   naming what it waited for, the state of the job's gates and events goes to stderr, the job's slot is never reused and
- *   the context refuses further proofs ("wedged": destroy it).  zk_groth16_wait / zk_groth16_batch_wait / zk_msm and the
- *   zk_dist_* prover calls therefore cannot block for ever (the net's own rounds have zk_net_set_timeout_ms).
+ * "wait_deadline_ms": bound of every host-side wait inside the prover and MSM entry points (an MSM chain's completion event,
+ *   a gate between two launching threads, a pool task; default 120000, 0 = unbounded): zk_groth16_prove / _wait / _batch_wait,
+ *   zk_groth16_msms_finish, the zk_dist_*groth16* calls, zk_msm, zk_msm_batch, zk_d_msm, zk_d_msm_parties, zk_d_msm_local and
+ *   zk_dist_d_msm.  On expiry the call returns ZK_ERR_GENERIC naming what it waited for (a prover job's gates and events go
+ *   to stderr), the MSM workspace it used is never reused and the context is wedged: every later prover and MSM call fails
+ *   at once ("wedged": destroy the context).  So none of them can block for ever (the net's own rounds have
+ *   zk_net_set_timeout_ms).
  * "dist_deadline": 1 = the zk_dist_* calls return only with their data-plane work done (zk_net_sync inside).
  * "pack_glv": 0 = zk_pss_pack_points at two points per chunk walks the parties' full-length scalars; 1 (default) = the
  *   scalars are split by the curve's endomorphism phi(x, y) = (beta x, y) = lambda (x, y) into two half-length parts (half

@@ -98,6 +98,70 @@ def test_a_wait_that_cannot_be_met_is_an_error_not_a_hang(capfd):
     assert same_shares(pp2, again, good)
 
 
+def test_an_expired_standalone_msm_wait_wedges_the_context():
+    """zk_msm's wait is bounded and wedges the context like the prover's: a table-free G1 MSM over 2^23 points takes ~12.7 ms
+    (csrc/msm.hpp, table_c_auto), more than ten times a 1 ms deadline.  Every MSM entry point and the prover then fail at
+    once, and a fresh context gives the first result."""
+    from gpu_util import dec_jacobian
+    from oracle.curve import g1
+    from oracle.params import CURVES
+    from zksaas_amd.api import ZK_G1, d_msm, msm, msm_batch
+    G = g1(CURVES["bn254"])
+    pp, crs, wit, r, s, masks = _sha256_inputs()
+    npts = 1 << 23
+    bases = zg.base_points(pp, ZK_G1, synthetic.rand_fr_device(pp, npts, 501), npts)
+    sc = synthetic.rand_fr_device(pp, npts, 502)
+    first = msm(pp, ZK_G1, bases, sc, npts)
+    pp.set_option("wait_deadline_ms", 1)
+    t0 = time.perf_counter()
+    with pytest.raises(zk.ZkError) as e:
+        msm(pp, ZK_G1, bases, sc, npts)
+    assert time.perf_counter() - t0 < 5.0
+    assert e.value.code == 1 and "deadline" in str(e.value)                 # ZK_ERR_GENERIC = MpcNetError::Generic
+    pp.set_option("wait_deadline_ms", 120000)
+    calls = (lambda: msm(pp, ZK_G1, bases, sc, npts), lambda: msm_batch(pp, ZK_G1, bases, [sc], npts),
+             lambda: d_msm(pp, ZK_G1, bases, sc, npts // pp.n), lambda: zg.prove(pp, crs, wit, r, s, masks=masks, seed=1))
+    for call in calls:
+        t0 = time.perf_counter()
+        with pytest.raises(zk.ZkError) as e2:
+            call()
+        assert time.perf_counter() - t0 < 1.0 and "wedged" in str(e2.value)
+    pp.sync()
+    pp2 = zk.PackedSharingParams("bn254", 2)
+    again = msm(pp2, ZK_G1, bases, sc, npts)
+    assert G.eq(dec_jacobian(pp2, again), dec_jacobian(pp, first))
+
+
+def test_standalone_msms_beside_a_proof_in_flight_equal_their_serial_results():
+    """zk_msm and zk_d_msm have a workspace slot of their own (csrc/msm.hpp WS_STANDALONE), apart from the slots of a proof's
+    four MSMs: issued on another stream while a proof is in flight, they and the proof equal their one-at-a-time results."""
+    import torch
+    from bench import same_shares
+    from gpu_util import dec_jacobian
+    from oracle.curve import g1
+    from oracle.params import CURVES
+    from zksaas_amd.api import ZK_G1, d_msm, msm
+    G = g1(CURVES["bn254"])
+    pp, crs, wit, r, s, masks = _sha256_inputs()
+    npts = 1 << 20
+    bases = zg.base_points(pp, ZK_G1, synthetic.rand_fr_device(pp, npts, 601), npts)
+    sc = synthetic.rand_fr_device(pp, npts, 602)
+    pp.sync()
+    ref = zg.prove(pp, crs, wit, r, s, masks=masks, seed=1)
+    want_msm = dec_jacobian(pp, msm(pp, ZK_G1, bases, sc, npts))
+    want_d = [dec_jacobian(pp, v) for v in d_msm(pp, ZK_G1, bases, sc, npts // pp.n)]
+    st = torch.cuda.Stream()
+    for rep in range(20):
+        job = zg.prove_async(pp, crs, wit, r, s, masks=masks, seed=1)
+        got_msm = msm(pp, ZK_G1, bases, sc, npts, stream=st.cuda_stream)
+        got_d = d_msm(pp, ZK_G1, bases, sc, npts // pp.n, stream=st.cuda_stream)
+        proof = job.wait()
+        st.synchronize()
+        assert same_shares(pp, proof, ref), rep
+        assert G.eq(dec_jacobian(pp, got_msm), want_msm), rep
+        assert all(G.eq(dec_jacobian(pp, v), w) for v, w in zip(got_d, want_d)), rep
+
+
 @pytest.mark.parametrize("curve", ["bn254", "bls12_381"])
 def test_transforms_and_d_pp_on_two_streams_at_once_equal_the_serial_results(curve):
     import torch

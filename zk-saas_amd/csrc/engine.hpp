@@ -241,6 +241,26 @@ class IEngine {
   int hip_fail(hipError_t e, const char* where) {
     return fail(ZK_ERR_GENERIC, std::string(where) + ": " + hipGetErrorString(e));
   }
+  // A wait that expired leaves device work or a pool task that still uses a workspace: the context is then wedged --
+  // every prover and MSM entry point fails at once with the first message, until the context is destroyed.
+  std::atomic<bool> wedged_{false};
+  std::string wedged_msg_;
+  int wedge(const std::string& what) {
+    if (!wedged_.exchange(true)) {
+      std::lock_guard<std::mutex> lk(last_mu);
+      wedged_msg_ = what;
+    }
+    return fail(ZK_ERR_GENERIC, what);
+  }
+  int check_wedged() {
+    if (!wedged_.load()) return ZK_OK;
+    std::string m;
+    {
+      std::lock_guard<std::mutex> lk(last_mu);
+      m = wedged_msg_;
+    }
+    return fail(ZK_ERR_GENERIC, "the context is wedged by an earlier timed-out wait (destroy it): " + m);
+  }
   virtual size_t fr_bytes() const = 0;
   virtual size_t fq_bytes() const = 0;
   virtual int pss_pack(const void* secrets, size_t nchunks, int order, uint64_t seed, bool det, void* shares,

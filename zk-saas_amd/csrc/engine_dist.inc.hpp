@@ -380,13 +380,10 @@
       ZK_HIP(hipMemcpy(dist_coef_[sid].p, csub.data(), k * sizeof(Fr), hipMemcpyHostToDevice));
       cd = (const Fr*)dist_coef_[sid].p;
     }
-    MsmPending pend;
-    rc = msm_.template launch_t<Fld>(this, bases, scalars, (size_t)k * len, cd, len, st, MSM_WS - 1 - sid, &pend);
-    if (rc) return rc;
-    XYZZ<Fld> mine = XYZZ<Fld>::identity();
-    if (in_mask) mine = msm_.template mask_term<Fld>(in_mask, first, k, csub.empty() ? nullptr : csub.data());
-    XYZZ<Fld> r;
-    rc = msm_.template finish_t<Fld>(this, &pend, &r);
+    XYZZ<Fld> mine = XYZZ<Fld>::identity(), r;
+    rc = msm_.run_t(this, sid, bases, scalars, (size_t)k * len, cd, len, st, &r, [&] {
+      if (in_mask) mine = msm_.template mask_term<Fld>(in_mask, first, k, csub.empty() ? nullptr : csub.data());
+    });
     if (rc) return rc;
     mine = xyzz_add_ni(mine, r);
     std::vector<XYZZ<Fld>> all((size_t)net->world);
@@ -400,24 +397,16 @@
     }
     rc = net_err(net, net->bcast_host(sid, mask, &total, sizeof(total)));
     if (rc) return rc;
-    const Jacobian<Fld>* om = (const Jacobian<Fld>*)out_mask;
-    Jacobian<Fld>* o = (Jacobian<Fld>*)out;
-    for (int p = 0; p < k; p++) {
-      XYZZ<Fld> v = total;
-      if (om) v = xyzz_add_ni(v, jacobian_to_xyzz(om[p]));
-      o[p] = xyzz_to_jacobian(v);
-    }
+    msm_.write_parties(out, total, out_mask, k);
     return ZK_OK;
   }
   int dist_d_msm(Net* net, int sid, int group, const void* bases, const void* scalars, size_t len, const void* in_mask,
                  const void* out_mask, void* out, hipStream_t st) override {
     if (!out) return fail(ZK_ERR_BAD_INPUT, "null output");
     if (len && (!bases || !scalars)) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    if (group == ZK_G1) return dist_d_msm_t<Fq_>(net, sid, bases, scalars, len, in_mask, out_mask, out, st);
-    if (group == ZK_G2) {
-      if constexpr (Cfg::HAS_G2) return dist_d_msm_t<Fq2_>(net, sid, bases, scalars, len, in_mask, out_mask, out, st);
-    }
-    return fail(ZK_ERR_BAD_INPUT, "bad group");
+    return msm_.by_group(this, group, [&](auto fld) {
+      return dist_d_msm_t<decltype(fld)>(net, sid, bases, scalars, len, in_mask, out_mask, out, st);
+    });
   }
 
   // circom_h (ext_wit.rs:104-181): the three d_ifft, then the three d_fft, each triple in flight together on channels

@@ -359,15 +359,12 @@
   // d_msm when only the listed parties' contributions reached the king (ser_net.rs:57-94): bases/scalars [np][len]
   int d_msm_parties(int group, const void* bases, const void* scalars, size_t len, const uint32_t* parties, int np,
                     const void* in_mask, const void* out_mask, void* out, hipStream_t st) override {
-    using Fq = Fp<typename Cfg::FqP>;
-    using Fq2 = Fp2<typename Cfg::FqP>;
     std::vector<Fr> coef;
     int rc = coefs_for(parties, np, coef);
     if (rc) return rc;
-    if (group == ZK_G1) return msm_.template d_msm_coef_t<Fq>(this, bases, scalars, len, coef, in_mask, out_mask, out, st);
-    if (group == ZK_G2 && Cfg::HAS_G2)
-      return msm_.template d_msm_coef_t<Fq2>(this, bases, scalars, len, coef, in_mask, out_mask, out, st);
-    return fail(ZK_ERR_BAD_INPUT, "bad group");
+    return msm_.by_group(this, group, [&](auto fld) {
+      return msm_.template d_msm_coef_t<decltype(fld)>(this, bases, scalars, len, coef, in_mask, out_mask, out, st);
+    });
   }
   // DegRedMask::sample with gen = 1 (deg_red.rs:40-66)
   int degred_mask_sample(size_t len, uint64_t seed, void* in_mask, void* out_mask, hipStream_t st) override {

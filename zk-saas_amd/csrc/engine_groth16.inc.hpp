@@ -140,7 +140,6 @@
   // host contributes (scalar multiples of CRS constants, of the out-masks and of the in-mask sums, MSM window folds)
   // is a task of the context's persistent pool, submitted when the proof starts and running beside the device work
   // (the overlap the reference gets from tokio::try_join!, prove.rs:209-227); prove_end only adds points.
-  static constexpr int NJOBS = 2;                   // proofs in flight per context (zk_groth16_prove_async)
   struct ProveJob {
     bool active = false;
     int slot = 0;
@@ -151,7 +150,7 @@
     int first = 0, count = 0;
     Fr r, s;
     DevBuf hwork, hshare;
-    MsmPending pS, pV0, pW, pU;
+    MsmPending msm[NROLES];                         // by MsmRole (msm.hpp); workspace slots ws_job(slot, role)
     P1 S, H, W, U, sS, rH;
     P2 V0;
     P1 rN, sK, rsM, s_cA, r_cB1;
@@ -160,7 +159,7 @@
     P2 in2;
     std::vector<P1> s_om0, r_om1;                   // per party: s * out_mask_A[p], r * out_mask_B1[p]
     std::vector<std::future<void>> fut;
-    int rc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int rc[ROLE_U] = {};                            // results of the S+H, W and V tasks (U is folded by the join)
     Status err;                                     // first failure reported by a task (tasks must not touch `last`)
     std::mutex emu;
   };
@@ -178,18 +177,8 @@
   }
   // ---- bounded waits (round 6, VERDICT r5 #10 / ADVICE r5): every wait of a job is bounded by the context's deadline
   // (engine.hpp wait_deadline_ms).  A wait that expires leaves device work or a pool task that still references the
-  // job's buffers: the job's slot is then never reused (it stays `active`), the context is marked wedged -- later prover
-  // calls fail at once with the first message -- and the state of every gate / event of the job goes to stderr.
-  std::atomic<bool> wedged_{false};
-  std::string wedged_msg_;
-  int wedge(const std::string& what) {
-    bool was = wedged_.exchange(true);
-    if (!was) {
-      std::lock_guard<std::mutex> lk(last_mu);
-      wedged_msg_ = what;
-    }
-    return fail(ZK_ERR_GENERIC, what);
-  }
+  // job's buffers: the job's slot is then never reused (it stays `active`), the context is wedged (engine.hpp wedge)
+  // and the state of every gate / event of the job goes to stderr.
   static const char* ev_state(hipEvent_t e) {
     if (!e) return "none";
     hipError_t q = hipEventQuery(e);
@@ -210,22 +199,19 @@
     return true;
   }
   bool drain(ProveJob& j) { return drain_futs(j.fut); }
-  // waits for a launched MSM's device work without folding it (abort paths); false = deadline
-  bool settle(MsmPending* p) {
-    if (!p->active) return true;
-    hipError_t e = event_wait(p->slot->ev);
-    if (e == hipErrorNotReady) return false;
-    p->active = false;
-    p->tab.reset();
-    p->tab2.reset();
-    return true;
+  MsmSlot& job_slot(const ProveJob& j, int role) { return msm_.slots_[ws_job(j.slot, role)]; }
+  // once the job's tasks are joined, a busy slot is a wait that expired: its work may still run
+  bool job_busy(const ProveJob& j) {
+    for (int r = 0; r < NROLES; r++)
+      if (job_slot(j, r).busy) return true;
+    return false;
   }
   void dump_job(const char* why, ProveJob& j) {
-    fprintf(stderr, "[zksaas] %s: proof slot %d: pool tasks pending %d, sorted_cnt %d; MSM events S+H %s%s, V %s%s, W %s%s, U %s%s\n",
-            why, j.slot, futs_pending(j.fut), j.sorted_cnt.load(), j.pS.active ? "" : "(idle) ",
-            j.pS.slot ? ev_state(j.pS.slot->ev) : "-", j.pV0.active ? "" : "(idle) ", j.pV0.slot ? ev_state(j.pV0.slot->ev) : "-",
-            j.pW.active ? "" : "(idle) ", j.pW.slot ? ev_state(j.pW.slot->ev) : "-", j.pU.active ? "" : "(idle) ",
-            j.pU.slot ? ev_state(j.pU.slot->ev) : "-");
+    fprintf(stderr, "[zksaas] %s: proof slot %d: pool tasks pending %d, sorted_cnt %d; MSM events", why, j.slot,
+            futs_pending(j.fut), j.sorted_cnt.load());
+    for (int r = 0; r < NROLES; r++)
+      fprintf(stderr, " %s %s%s%s", ROLE_NAME[r], job_slot(j, r).busy ? "" : "(idle) ", ev_state(job_slot(j, r).ev),
+              r + 1 < NROLES ? "," : "\n");
   }
   // engine-level failure recorded from a pool task (IEngine::fail is not thread-safe)
   int task_fail(ProveJob& j, int code, const std::string& msg) {
@@ -267,7 +253,7 @@
     j.first = first;
     j.count = count;
     j.err = Status{};
-    for (int i = 0; i < 8; i++) j.rc[i] = 0;
+    for (int& e : j.rc) e = 0;
     j.S = j.H = j.W = j.U = j.sS = j.rH = j.s_in0 = j.r_in1 = P1::identity();
     j.V0 = j.in2 = P2::identity();
     for (int k = 0; k < 5; k++) j.in1[k] = P1::identity();
@@ -278,7 +264,7 @@
   MsmGate u_gate(ProveJob& j) {
     MsmGate g{};
     if (j.gate_sorts) {
-      g.sorted_ev = ev_sorted_[j.slot][3];
+      g.sorted_ev = ev_sorted_[j.slot][ROLE_U];
       g.sorted_cnt = &j.sorted_cnt;
     }
     return g;
@@ -300,7 +286,6 @@
     init_job(j, crs, mk, r, s, full, first, count);
     const size_t Lc = ((size_t)1 << log_m) / l;
     const int dev = device;
-    const int ws0 = j.slot * 6;
     // every internal stream is ordered after the work already queued on the caller's stream (the shares may still
     // be in flight there: found by tools/c5_bls381.py, where the a_share pack kernel of a 2^22 witness was still
     // running when the S/H/V MSMs started reading it)
@@ -348,39 +333,41 @@
       if (he != hipSuccess) return hip_fail(he, "h share buffer");
       rc = circom_h_ws(qa, qb, qc, log_m, mk, seed, j.hshare.p, j.hwork, streams_[5]);
       if (rc) return rc;
-      rc = msm_.template launch_t<Fq_>(this, crs->u_d, j.hshare.p, (size_t)n * crs->len_u, msm_.coef_d_, crs->len_u,
-                                      streams_[5], ws0 + 0, &j.pU, nullptr, u_gate(j));
+      rc = msm_.template launch_t<Fq_>(this, ws_job(j.slot, ROLE_U), crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
+                                      msm_.coef_d_, crs->len_u, streams_[5], &j.msm[ROLE_U], nullptr, u_gate(j));
       if (rc) return rc;
       hu_done = true;
     }
-    auto msm_task = [this, J, dev, gate](auto fld_tag, int which, const void* bases, const void* bases2, const void* scal,
-                                         size_t npts, const Fr* coef, size_t plen, hipStream_t stream, int wslot,
-                                         MsmPending* pend, auto* out1, auto* out2) {
+    auto msm_task = [this, J, dev, gate](auto fld_tag, MsmRole role, const void* bases, const void* bases2,
+                                         const void* scal, size_t npts, const Fr* coef, size_t plen, hipStream_t stream,
+                                         auto* out1, auto* out2) {
       using Fld = decltype(fld_tag);
       J->fut.push_back(pool_->submit([=]() {
         (void)hipSetDevice(dev);
         MsmGate g = gate;
-        if (g.n_wait_sorted) g.sorted_ev = ev_sorted_[J->slot][which];          // which = 0 (S/H), 1 (W), 2 (V); 3 = U
-        int rc2 = msm_.template launch_t<Fld>(this, bases, scal, npts, coef, plen, stream, wslot, pend, bases2, g);
+        if (g.n_wait_sorted) g.sorted_ev = ev_sorted_[J->slot][role];
+        MsmPending* pend = &J->msm[role];
+        int rc2 = msm_.template launch_t<Fld>(this, ws_job(J->slot, role), bases, scal, npts, coef, plen, stream, pend,
+                                              bases2, g);
         if (rc2 && g.sorted_cnt) g.sorted_cnt->fetch_add(1, std::memory_order_release);   // never leave the others spinning
-        if (!rc2) rc2 = msm_.template finish_t<Fld>(this, pend, out1, out2);
-        J->rc[which] = rc2;
+        if (!rc2) rc2 = msm_fold<Fld>(this, *pend, out1, out2);
+        J->rc[role] = rc2;
         if constexpr (std::is_same<Fld, Fq_>::value) {
-          if (!rc2 && J->full && which == 0) {        // s*S and r*H off the tail (prove.rs:229-235, linearity)
+          if (!rc2 && J->full && role == ROLE_SH) {   // s*S and r*H off the tail (prove.rs:229-235, linearity)
             J->sS = host_scalar_mul<FrP, Fq_>(J->S, J->s);
             if (out2 != nullptr && !J->r_zero) J->rH = host_scalar_mul<FrP, Fq_>(J->H, J->r);
           }
         }
       }));
     };
-    msm_task(Fq2_{}, 2, crs->v_d, nullptr, a_share, (size_t)count * cstride, cf, cstride, streams_[2], ws0 + 3, &j.pV0,
-             &j.V0, (P2*)nullptr);
+    msm_task(Fq2_{}, ROLE_V, crs->v_d, nullptr, a_share, (size_t)count * cstride, cf, cstride, streams_[2], &j.V0,
+             (P2*)nullptr);
     // S and H multiply two base vectors by the same witness shares: ONE launch over both vectors, each with its own sort
     // (their identity bases differ: b_query is the identity for every wire no B-row mentions, 59 % in the SHA-256 circuit)
-    msm_task(Fq_{}, 0, crs->s_d, j.r_zero ? nullptr : crs->h_d, a_share, (size_t)count * cstride, cf, cstride,
-             streams_[0], ws0 + 1, &j.pS, &j.S, j.r_zero ? (P1*)nullptr : &j.H);
-    msm_task(Fq_{}, 1, crs->w_d, nullptr, ax_share, (size_t)count * crs->len_w, cf, crs->len_w, streams_[3], ws0 + 4,
-             &j.pW, &j.W, (P1*)nullptr);
+    msm_task(Fq_{}, ROLE_SH, crs->s_d, j.r_zero ? nullptr : crs->h_d, a_share, (size_t)count * cstride, cf, cstride,
+             streams_[0], &j.S, j.r_zero ? (P1*)nullptr : &j.H);
+    msm_task(Fq_{}, ROLE_W, crs->w_d, nullptr, ax_share, (size_t)count * crs->len_w, cf, crs->len_w, streams_[3], &j.W,
+             (P1*)nullptr);
     // (the host terms are two dozen pool submissions: behind circom_h's launches when those are still to come -- they
     // are the head of the proof's longest chain and the terms are not needed before prove_end)
     if (!(full && !hu_done)) submit_host_terms(J, j.fut, full, first, count);
@@ -395,8 +382,8 @@
       rc = circom_h_ws(qa, qb, qc, log_m, mk, seed, j.hshare.p, j.hwork, hs);
       if (rc) return rc;
       host_span(PROF_HOST_H);
-      rc = msm_.template launch_t<Fq_>(this, crs->u_d, j.hshare.p, (size_t)n * crs->len_u, msm_.coef_d_, crs->len_u, hs,
-                                      ws0 + 0, &j.pU);
+      rc = msm_.template launch_t<Fq_>(this, ws_job(j.slot, ROLE_U), crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
+                                      msm_.coef_d_, crs->len_u, hs, &j.msm[ROLE_U]);
       if (rc) return rc;
       submit_host_terms(J, j.fut, full, first, count);
       host_span(PROF_HOST_U);
@@ -454,29 +441,26 @@
 
   // the U-MSM of a partial job (h comes from the caller's king rounds)
   int prove_launch_u(ProveJob& j, const void* h_share, hipStream_t st) {
-    return msm_.template launch_t<Fq_>(this, j.crs.u_d, h_share, (size_t)j.count * j.crs.len_u, msm_.coef_d_ + j.first,
-                                      j.crs.len_u, st, j.slot * 6 + 0, &j.pU, nullptr, u_gate(j));
+    return msm_.template launch_t<Fq_>(this, ws_job(j.slot, ROLE_U), j.crs.u_d, h_share, (size_t)j.count * j.crs.len_u,
+                                      msm_.coef_d_ + j.first, j.crs.len_u, st, &j.msm[ROLE_U], nullptr, u_gate(j));
   }
 
   // joins everything; sums[0..4] = S, H, V, W, U including the in-mask terms
   int prove_join(ProveJob& j, P1* S, P1* H, P2* V, P1* W, P1* U) {
-    int rc = msm_.template finish_t<Fq_>(this, &j.pU, &j.U);
-    if (rc && j.pU.active) {
-      dump_job("prove_join: the U-MSM chain did not finish within the deadline", j);
-      Status keep = last;
-      return wedge(keep.msg);
-    }
+    int rc = msm_fold<Fq_>(this, j.msm[ROLE_U], &j.U, nullptr);
     if (!drain(j)) {
       dump_job("prove_join: pool tasks did not finish within the deadline", j);
       return wedge("host tasks of the proof did not finish within the deadline (wait_deadline_ms); the slot is not reused");
     }
+    if (job_busy(j)) {
+      dump_job("prove_join: an MSM chain did not finish within the deadline", j);
+      Status keep = last;
+      return wedge(keep.msg);
+    }
     j.active = false;
     if (rc) return rc;
-    for (int i = 0; i < 8; i++)
-      if (j.rc[i]) {
-        // a pool task failed: its message was recorded on the engine by msm_launch (hip_fail); keep it
-        return j.rc[i];
-      }
+    for (int e : j.rc)
+      if (e) return e;      // a pool task failed: its message was recorded on the engine by msm_launch (hip_fail); keep it
     if (j.err.code) return fail(j.err.code, j.err.msg);
     *S = xyzz_add_ni(j.S, j.in1[0]);
     *H = j.r_zero ? P1::identity() : xyzz_add_ni(j.H, j.in1[1]);
@@ -497,7 +481,7 @@
       return wedge("zk_groth16_wait: host tasks of the proof did not finish within the deadline (wait_deadline_ms); the slot is not reused");
     }
     bool early_ok = !j.err.code;
-    for (int i = 0; i < 8; i++) early_ok = early_ok && !j.rc[i];
+    for (int e : j.rc) early_ok = early_ok && !e;
     std::vector<P1> c_part(early_ok ? n : 0);
     if (early_ok) {
       const P1 S = xyzz_add_ni(j.S, j.in1[0]), H = j.r_zero ? P1::identity() : xyzz_add_ni(j.H, j.in1[1]),
@@ -507,7 +491,7 @@
       if (rc) early_ok = false;
     }
     const auto t1 = std::chrono::steady_clock::now();
-    if (prof.on && j.pU.active) (void)event_wait(j.pU.slot->ev);                // (finish_t waits again: returns at once)
+    if (prof.on && job_slot(j, ROLE_U).busy) (void)event_wait(job_slot(j, ROLE_U).ev);   // (msm_fold waits again: returns at once)
     const auto t2 = std::chrono::steady_clock::now();
     struct HostSpans {                                                          // host:prove_wait / host:prove_tail
       Profiler& pr;
@@ -519,16 +503,16 @@
       }
     } spans{prof, t0, t2};
     (void)t1;
-    int rc = msm_.template finish_t<Fq_>(this, &j.pU, &j.U);
-    if (rc && j.pU.active) {               // the U chain's event did not signal within the deadline: nothing may be reused
-      dump_job("zk_groth16_wait: the U-MSM chain did not finish within the deadline", j);
+    int rc = msm_fold<Fq_>(this, j.msm[ROLE_U], &j.U, nullptr);
+    if (job_busy(j)) {                     // a chain's event did not signal within the deadline: nothing may be reused
+      dump_job("zk_groth16_wait: an MSM chain did not finish within the deadline", j);
       Status keep = last;
       return wedge(keep.msg);
     }
     j.active = false;
     if (rc) return rc;
-    for (int i = 0; i < 8; i++)
-      if (j.rc[i]) return j.rc[i];      // a pool task failed: its message was recorded on the engine by msm_launch; keep it
+    for (int e : j.rc)
+      if (e) return e;                  // a pool task failed: its message was recorded on the engine by msm_launch; keep it
     if (j.err.code) return fail(j.err.code, j.err.msg);
     if (!early_ok) return fail(ZK_ERR_GENERIC, "proof assembly failed");
     Jacobian<Fq_>* oc = (Jacobian<Fq_>*)pi_c;
@@ -589,14 +573,8 @@
 
   int check_prove_args(const zk_crs_share* crs, const void* r_, const void* s_, int log_m) {
     if (!Cfg::HAS_G2) return fail(ZK_ERR_BAD_INPUT, "G2 is not available for this curve");
-    if (wedged_.load()) {
-      std::string m;
-      {
-        std::lock_guard<std::mutex> lk(last_mu);
-        m = wedged_msg_;
-      }
-      return fail(ZK_ERR_GENERIC, "the context is wedged by an earlier timed-out wait (destroy it): " + m);
-    }
+    int rc = check_wedged();
+    if (rc) return rc;
     if (!crs || !r_ || !s_) return fail(ZK_ERR_BAD_INPUT, "null pointer");
     int log_l = ilog2(l);
     if (log_m < log_l || log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
@@ -652,8 +630,7 @@
   void abort_job(ProveJob& j) {
     j.sorted_cnt.fetch_add(1 << 20, std::memory_order_release);      // tasks waiting at the sort barrier go on (and fail or finish)
     bool ok = drain(j);
-    MsmPending* ps[4] = {&j.pS, &j.pV0, &j.pW, &j.pU};
-    for (MsmPending* p : ps) ok = settle(p) && ok;
+    for (int r = 0; r < NROLES; r++) ok = ok && job_slot(j, r).wait(this) != hipErrorNotReady;
     if (!ok) {
       dump_job("abort: work of the proof is still pending after the deadline", j);
       Status keep = last;
@@ -686,15 +663,14 @@
     bool active = false;
     int nb = 0;
     std::vector<std::unique_ptr<ProveJob>> pj;      // per proof: host terms and the five MSM totals
-    MsmPending pSH, pV, pW, pU;
+    MsmPending msm[NROLES];                         // by MsmRole; workspace slots ws_batch(slot, role)
     DevBuf hwork, hshare;
     std::vector<std::future<void>> fut;
-    int rc[4] = {0, 0, 0, 0};
+    int rc[ROLE_U] = {};                            // results of the S+H, W and V tasks (U is folded by batch_join)
   };
   // Two batches may be in flight (zk_groth16_prove_batch_async): each has its own MSM workspaces, scratch and stream
   // set, so that the sort phase of one batch runs under the accumulate kernels of the other and the reduction tails of one
   // under the other's accumulates -- one batch alone leaves the chip partly idle for ~1 ms at either end.
-  static constexpr int NBATCH = 3;
   struct BatchJobX : BatchJob {
     zk_crs_share crs{};
     int slot = 0;
@@ -702,25 +678,28 @@
     bool own_streams = false, full = true;
     int first = 0, count = 0;
     MsmGate gate_u;
-    hipEvent_t ev_acc[4] = {nullptr, nullptr, nullptr, nullptr};      // V, S+H, W, U: recorded behind the accumulate kernel
-    std::atomic<int> acc_flag[4];                                     // ... once that record has been enqueued (MsmGate)
+    hipEvent_t ev_acc[NROLES] = {};                 // by role: recorded behind the accumulate kernel
+    std::atomic<int> acc_flag[NROLES];              // ... once that record has been enqueued (MsmGate)
     hipStream_t st[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   };
   BatchJobX bjobs_[NBATCH];
 
+  MsmSlot& batch_slot(const BatchJobX& B, int role) { return msm_.slots_[ws_batch(B.slot, role)]; }
+  bool batch_busy(const BatchJobX& B) {
+    for (int r = 0; r < NROLES; r++)
+      if (batch_slot(B, r).busy) return true;
+    return false;
+  }
   void dump_batch(const char* why, BatchJobX& B) {
-    const MsmPending* ps[4] = {&B.pV, &B.pSH, &B.pW, &B.pU};
-    const char* nm[4] = {"V", "S+H", "W", "U"};
     fprintf(stderr, "[zksaas] %s: batch slot %d (%d proofs): pool tasks pending %d;", why, B.slot, B.nb, futs_pending(B.fut));
-    for (int i = 0; i < 4; i++)
-      fprintf(stderr, " %s: launched-flag %d, accumulate event %s, chain event %s%s;", nm[i], B.acc_flag[i].load(), ev_state(B.ev_acc[i]),
-              ps[i]->slot ? ev_state(ps[i]->slot->ev) : "-", ps[i]->active ? "" : " (idle)");
+    for (int r = 0; r < NROLES; r++)
+      fprintf(stderr, " %s: launched-flag %d, accumulate event %s, chain event %s%s;", ROLE_NAME[r], B.acc_flag[r].load(),
+              ev_state(B.ev_acc[r]), ev_state(batch_slot(B, r).ev), batch_slot(B, r).busy ? "" : " (idle)");
     fprintf(stderr, "\n");
   }
   void abort_batch(BatchJobX& B) {
     bool ok = drain_futs(B.fut);
-    MsmPending* ps[4] = {&B.pSH, &B.pV, &B.pW, &B.pU};
-    for (MsmPending* p : ps) ok = settle(p) && ok;
+    for (int r = 0; r < NROLES; r++) ok = ok && batch_slot(B, r).wait(this) != hipErrorNotReady;
     if (!ok) {
       dump_batch("abort: work of the batch is still pending after the deadline", B);
       Status keep = last;
@@ -771,9 +750,9 @@
     MsmBatchArg ba_h;
     ba_h.nb = B.nb;
     for (int b = 0; b < B.nb; b++) ba_h.p[b] = h_all + (size_t)b * stride;
-    int rc = msm_.template launch_t<Fq_>(this, B.crs.u_d, nullptr, (size_t)B.count * B.crs.len_u, msm_.coef_d_ + B.first,
-                                        B.crs.len_u, st, 12 + 6 * B.slot + 0, &B.pU, nullptr, B.gate_u, &ba_h);
-    B.acc_flag[3].store(1, std::memory_order_release);
+    int rc = msm_.template launch_t<Fq_>(this, ws_batch(B.slot, ROLE_U), B.crs.u_d, nullptr, (size_t)B.count * B.crs.len_u,
+                                        msm_.coef_d_ + B.first, B.crs.len_u, st, &B.msm[ROLE_U], nullptr, B.gate_u, &ba_h);
+    B.acc_flag[ROLE_U].store(1, std::memory_order_release);
     return rc;
   }
   // Starts a batch: the four witness MSMs of parties [first, first + count) for nb proofs (one launch chain each) and
@@ -804,8 +783,8 @@
     {
       // every handle is checked on its own: a failure half-way leaves the rest to be created by the next call
       if (!B.ev_in) ZK_HIP(hipEventCreateWithFlags(&B.ev_in, hipEventDisableTiming));
-      for (int i = 0; i < 4; i++)
-        if (!B.ev_acc[i]) ZK_HIP(hipEventCreateWithFlags(&B.ev_acc[i], hipEventDisableTiming));
+      for (hipEvent_t& e : B.ev_acc)
+        if (!e) ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
       // (splitting the chip between the G2 MSM and the rest with CU masks was measured in round 3 and dropped: DESIGN.md
       // "batched proving")
       B.own_streams = slot != 0;
@@ -838,13 +817,12 @@
       init_job(*B.pj[b], crs, mk ? &mk[b] : nullptr, r, s, full, first, count);
       all_r_zero = all_r_zero && r.is_zero();
     }
-    for (int i = 0; i < 4; i++) B.rc[i] = 0;
+    for (int& e : B.rc) e = 0;
     ZK_HIP(hipEventRecord(ev_batch_in_, st));
     for (int i = 0; i < 6; i++) ZK_HIP(hipStreamWaitEvent(streams_[i], ev_batch_in_, 0));
     B.active = true;
     BatchJob* BJ = &B;
     const int dev = device;
-    const int ws0 = 12 + 6 * slot;                      // the batch's own MSM workspaces (msm.hpp MSM_WS)
     const Fr* cf = msm_.coef_d_ + first;
     MsmBatchArg ba_a, ba_x;
     ba_a.nb = ba_x.nb = nb;
@@ -857,14 +835,17 @@
     // run beside it -- and spares them each other: issued together, four kernels' waves interleave on every SIMD, the
     // 256-register G2 waves are crowded out by the 168-register G1 waves (which fit any slot a G1 wave frees) and V's
     // accumulate ends alone long after the others with its reduction tail on an empty chip
-    // (profiles/r03_b8_timeline_*.txt).  Letters of the chain in order, V S W U (S = the S + H launch); "-" = no chain.
-    // (a small batch does not fill the chip with one accumulate: its kernels run side by side as in a single proof)
+    // (profiles/r03_b8_timeline_*.txt).  The chain in order, by the first letters of ROLE_NAME (S = the S + H launch);
+    // "-" = no chain.  (A small batch does not fill the chip with one accumulate: its kernels run side by side as in a
+    // single proof.)
     const std::string order = nb >= 4 ? "VSWU" : "-";
-    MsmGate gates[4];                                  // V, S, W, U
+    MsmGate gates[NROLES];
     {
       int prev = -1;
       for (char ch : order) {
-        const int id = ch == 'V' ? 0 : ch == 'S' ? 1 : ch == 'W' ? 2 : ch == 'U' ? 3 : -1;
+        int id = -1;
+        for (int r = 0; r < NROLES; r++)
+          if (ROLE_NAME[r][0] == ch) id = r;
         if (id < 0 || gates[id].signal_ev) continue;
         B.acc_flag[id].store(0, std::memory_order_relaxed);
         gates[id].signal_ev = B.ev_acc[id];
@@ -876,29 +857,28 @@
         prev = id;
       }
     }
-    const MsmGate gate_v = gates[0], gate_s = gates[1], gate_w = gates[2], gate_u = gates[3];
     std::atomic<int>* aflag = B.acc_flag;
     // ---- the witness MSMs: V (G2) first on its high-priority stream, S + H as one launch over both base vectors, W
     B.fut.push_back(pool_->submit([=]() {
       (void)hipSetDevice(dev);
-      int rc2 = msm_.template launch_t<Fq2_>(this, crs->v_d, nullptr, (size_t)n * crs->len_a, cf, crs->len_a, streams_[2],
-                                            ws0 + 3, &BJ->pV, nullptr, gate_v, &ba_a);
-      aflag[0].store(1, std::memory_order_release);        // also when the launch failed early (waiters must not hang)
+      int rc2 = msm_.template launch_t<Fq2_>(this, ws_batch(slot, ROLE_V), crs->v_d, nullptr, (size_t)n * crs->len_a, cf,
+                                            crs->len_a, streams_[2], &BJ->msm[ROLE_V], nullptr, gates[ROLE_V], &ba_a);
+      aflag[ROLE_V].store(1, std::memory_order_release);   // also when the launch failed early (waiters must not hang)
       std::vector<P2> res((size_t)nb);
-      if (!rc2) rc2 = msm_fold_batch<Fq2_>(this, BJ->pV, res.data(), 1);
-      BJ->rc[1] = rc2;
+      if (!rc2) rc2 = msm_fold_batch<Fq2_>(this, BJ->msm[ROLE_V], res.data(), 1);
+      BJ->rc[ROLE_V] = rc2;
       if (!rc2)
         for (int b = 0; b < nb; b++) BJ->pj[b]->V0 = res[b];
     }));
     const void* hd = all_r_zero ? nullptr : crs->h_d;
     B.fut.push_back(pool_->submit([=]() {
       (void)hipSetDevice(dev);
-      int rc2 = msm_.template launch_t<Fq_>(this, crs->s_d, nullptr, (size_t)n * crs->len_a, cf, crs->len_a, streams_[0],
-                                           ws0 + 1, &BJ->pSH, hd, gate_s, &ba_a);
-      aflag[1].store(1, std::memory_order_release);
+      int rc2 = msm_.template launch_t<Fq_>(this, ws_batch(slot, ROLE_SH), crs->s_d, nullptr, (size_t)n * crs->len_a, cf,
+                                           crs->len_a, streams_[0], &BJ->msm[ROLE_SH], hd, gates[ROLE_SH], &ba_a);
+      aflag[ROLE_SH].store(1, std::memory_order_release);
       std::vector<P1> res((size_t)nb * 2);
-      if (!rc2) rc2 = msm_fold_batch<Fq_>(this, BJ->pSH, res.data(), hd ? 2 : 1);
-      BJ->rc[0] = rc2;
+      if (!rc2) rc2 = msm_fold_batch<Fq_>(this, BJ->msm[ROLE_SH], res.data(), hd ? 2 : 1);
+      BJ->rc[ROLE_SH] = rc2;
       if (rc2) return;
       // s*S and r*H per proof (prove.rs:229-235, linearity): spread over the pool, this task takes proof 0
       std::vector<std::future<void>> sub;
@@ -920,18 +900,18 @@
     }));
     B.fut.push_back(pool_->submit([=]() {
       (void)hipSetDevice(dev);
-      int rc2 = msm_.template launch_t<Fq_>(this, crs->w_d, nullptr, (size_t)n * crs->len_w, cf, crs->len_w, streams_[3],
-                                           ws0 + 4, &BJ->pW, nullptr, gate_w, &ba_x);
-      aflag[2].store(1, std::memory_order_release);
+      int rc2 = msm_.template launch_t<Fq_>(this, ws_batch(slot, ROLE_W), crs->w_d, nullptr, (size_t)n * crs->len_w, cf,
+                                           crs->len_w, streams_[3], &BJ->msm[ROLE_W], nullptr, gates[ROLE_W], &ba_x);
+      aflag[ROLE_W].store(1, std::memory_order_release);
       std::vector<P1> res((size_t)nb);
-      if (!rc2) rc2 = msm_fold_batch<Fq_>(this, BJ->pW, res.data(), 1);
-      BJ->rc[2] = rc2;
+      if (!rc2) rc2 = msm_fold_batch<Fq_>(this, BJ->msm[ROLE_W], res.data(), 1);
+      BJ->rc[ROLE_W] = rc2;
       if (!rc2)
         for (int b = 0; b < nb; b++) BJ->pj[b]->W = res[b];
     }));
     // ---- host terms of every proof
     for (int b = 0; b < nb; b++) submit_host_terms(B.pj[b].get(), B.fut, full, first, count);
-    B.gate_u = gate_u;
+    B.gate_u = gates[ROLE_U];
     *slot_out = slot;
     return ZK_OK;
   }
@@ -943,9 +923,9 @@
   int batch_join(BatchJobX& B, std::vector<BatchSums>& sums) {
     const int nb = B.nb;
     std::vector<P1> ures((size_t)nb);
-    int rc = msm_fold_batch<Fq_>(this, B.pU, ures.data(), 1);
+    int rc = msm_fold_batch<Fq_>(this, B.msm[ROLE_U], ures.data(), 1);
     if (rc) {
-      if (B.pU.active) dump_batch("zk_groth16_batch_wait: the U-MSM chain did not finish within the deadline", B);
+      if (batch_slot(B, ROLE_U).busy) dump_batch("zk_groth16_batch_wait: the U-MSM chain did not finish within the deadline", B);
       Status keep = last;
       abort_batch(B);
       last = keep;
@@ -955,9 +935,14 @@
       dump_batch("zk_groth16_batch_wait: pool tasks did not finish within the deadline", B);
       return wedge("zk_groth16_batch_wait: host tasks of the batch did not finish within the deadline (wait_deadline_ms); the slot is not reused");
     }
+    if (batch_busy(B)) {
+      dump_batch("zk_groth16_batch_wait: an MSM chain did not finish within the deadline", B);
+      Status keep = last;
+      return wedge(keep.msg);
+    }
     B.active = false;
-    for (int i = 0; i < 4; i++)
-      if (B.rc[i]) return B.rc[i];
+    for (int e : B.rc)
+      if (e) return e;
     sums.resize((size_t)nb);
     for (int b = 0; b < nb; b++) {
       ProveJob& j = *B.pj[b];
@@ -1004,52 +989,28 @@
       if (len && !scalars[b]) return fail(ZK_ERR_BAD_INPUT, "null pointer");
       ba.p[b] = scalars[b];
     }
-    auto run = [&](auto tag) -> int {
-      using Fld = decltype(tag);
-      MsmPending pend;
-      int rc = msm_.template launch_t<Fld>(this, bases, nullptr, len, nullptr, 1, st, 0, &pend, nullptr, MsmGate{}, &ba);
-      if (rc) return rc;
+    return msm_.by_group(this, group, [&](auto fld) -> int {
+      using Fld = decltype(fld);
       std::vector<XYZZ<Fld>> res((size_t)nb);
-      rc = msm_fold_batch<Fld>(this, pend, res.data(), 1);
+      int rc = msm_.run_t(this, -1, bases, nullptr, len, nullptr, 1, st, res.data(), [] {}, &ba);
       if (rc) return rc;
-      for (int b = 0; b < nb; b++) {
-        Jacobian<Fld> j = xyzz_to_jacobian(res[b]);
-        memcpy((char*)out + (size_t)b * sizeof(j), &j, sizeof(j));
-      }
+      for (int b = 0; b < nb; b++) msm_.write_jacobian((char*)out + (size_t)b * sizeof(Jacobian<Fld>), res[b]);
       return ZK_OK;
-    };
-    if (group == ZK_G1) return run(Fq_{});
-    if (group == ZK_G2) {
-      if constexpr (Cfg::HAS_G2) return run(Fq2_{});
-    }
-    return fail(ZK_ERR_BAD_INPUT, "bad group");
+    });
   }
 
   // sum over the listed local parties of coef_p * (msm_p + in_mask_p): one rank's contribution to the king's
   // unpack2 + sum (dmsm/mod.rs:85-86) when the n parties are spread over several GPUs.
   int d_msm_local(int group, const void* bases, const void* scalars, size_t len, int first_party, int nparties,
                   const void* in_mask, void* out, hipStream_t st) override {
-    using Fq = Fp<typename Cfg::FqP>;
-    using Fq2 = Fp2<typename Cfg::FqP>;
     if (first_party < 0 || nparties <= 0 || first_party + nparties > n) return fail(ZK_ERR_BAD_INPUT, "bad party range");
     if (!out) return fail(ZK_ERR_BAD_INPUT, "null output");
-    if (group == ZK_G1) {
-      XYZZ<Fq> r;
-      int rc = msm_.template d_msm_range_t<Fq>(this, bases, scalars, len, first_party, nparties, in_mask, &r, st);
-      if (rc) return rc;
-      Jacobian<Fq> j = xyzz_to_jacobian(r);
-      memcpy(out, &j, sizeof(j));
-      return ZK_OK;
-    }
-    if (group == ZK_G2 && Cfg::HAS_G2) {
-      XYZZ<Fq2> r;
-      int rc = msm_.template d_msm_range_t<Fq2>(this, bases, scalars, len, first_party, nparties, in_mask, &r, st);
-      if (rc) return rc;
-      Jacobian<Fq2> j = xyzz_to_jacobian(r);
-      memcpy(out, &j, sizeof(j));
-      return ZK_OK;
-    }
-    return fail(ZK_ERR_BAD_INPUT, "bad group");
+    return msm_.by_group(this, group, [&](auto fld) {
+      XYZZ<decltype(fld)> r;
+      int rc = msm_.d_msm_range_t(this, bases, scalars, len, first_party, nparties, in_mask, &r, st);
+      if (!rc) msm_.write_jacobian(out, r);
+      return rc;
+    });
   }
   // MsmMask::sample (dmsm/mod.rs:21-47); scalar form: shares of (x_0..x_{l-1} | t random) times the generator
   template <class Fld>

@@ -392,7 +392,7 @@ class Engine : public IEngine {
     for (int i = 0; i < NJOBS; i++) {
       ZK_HIP(hipEventCreateWithFlags(&ev_in_[i], hipEventDisableTiming));
       ZK_HIP(hipEventCreateWithFlags(&ev_gate_[i], hipEventDisableTiming));
-      for (int k = 0; k < 4; k++) ZK_HIP(hipEventCreateWithFlags(&ev_sorted_[i][k], hipEventDisableTiming));
+      for (hipEvent_t& e : ev_sorted_[i]) ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     // host workers: the MSM tasks block on their events while the scalar-multiple tasks run
     int nthreads = host_threads_;                        // zk_ctx_set_option("host_threads"), before the first proof
@@ -409,7 +409,7 @@ class Engine : public IEngine {
   HostPool* host_pool() override { return pool_.get(); }
   hipEvent_t ev_in_[NJOBS] = {nullptr, nullptr};
   hipEvent_t ev_gate_[NJOBS] = {nullptr, nullptr};
-  hipEvent_t ev_sorted_[NJOBS][4] = {};
+  hipEvent_t ev_sorted_[NJOBS][NROLES] = {};     // by MsmRole: the "all sorts first" barrier of a proof (prove_begin_impl)
   int h_first_log_m_ = 20;      // zk_ctx_set_option("h_first_log_m"): see prove_begin_impl
   int host_threads_ = 0;        // zk_ctx_set_option("host_threads"): workers of the host pool (0 = by the core count)
   hipStream_t streams_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -7,7 +7,7 @@
     if (nb != ns) {   // dmsm/mod.rs:73: G::msm returns Err(min len) -> MpcNetError::Generic(len.to_string())
       return fail(ZK_ERR_GENERIC, std::to_string(nb < ns ? nb : ns));
     }
-    return msm_.run(this, group, bases, scalars, nb, nullptr, 1, out, st);
+    return msm_.run(this, group, bases, scalars, nb, out, st);
   }
   int d_msm(int group, const void* bases, const void* scalars, size_t len, const void* in_mask, const void* out_mask,
             void* out, hipStream_t st) override {

@@ -43,8 +43,34 @@ constexpr size_t MSM_RANGE_MIN = 20, MSM_RANGE = 64;        // entries per accum
 constexpr size_t MSM_RANGE_MIN_G2 = 16, MSM_RANGE_G2 = 64;  // ... per lane quad of the extension-field kernel (32 until
                                                             // round 4; C5: 1.303 s at 32, 1.286 at 64, 1.280 at 128)
 constexpr uint32_t FIN_SEQ = 16;      // a bucket spread over more accumulate lanes than this is summed by a workgroup
-constexpr int MSM_WS = 30;            // independent workspaces: 6 per proof in flight (concurrent MSMs on separate
-                                      // streams) + 6 per batch of proofs in flight (zk_groth16_prove_batch)
+
+// The four MSMs of a proof, in the order of its "all sorts first" barrier (engine_groth16.inc.hpp prove_begin_impl):
+// S and H (one launch over both base vectors), W, V (G2), U (over h).  ROLE_NAME's first letters spell the batch's chain.
+enum MsmRole { ROLE_SH, ROLE_W, ROLE_V, ROLE_U, NROLES };
+constexpr const char* ROLE_NAME[NROLES] = {"S+H", "W", "V", "U"};
+constexpr int NJOBS = 2;              // proofs in flight per context (zk_groth16_prove_async)
+constexpr int NBATCH = 3;             // batches of proofs in flight per context (zk_groth16_prove_batch_async)
+// Workspace slots (MsmRunner::slots_), one per MSM that may be in flight: a role of a proof job, a role of a batch, a
+// net channel (zk_dist_d_msm) or the standalone MSMs (zk_msm, zk_msm_batch, zk_d_msm, ...).  Slots are allocated on
+// first use.
+constexpr int ws_job(int j, int r) { return j * NROLES + r; }
+constexpr int ws_batch(int b, int r) { return (NJOBS + b) * NROLES + r; }
+constexpr int ws_dist(int sid) { return (NJOBS + NBATCH) * NROLES + sid; }
+constexpr int WS_STANDALONE = ws_dist(NET_NSID);
+constexpr int MSM_WS = WS_STANDALONE + 1;
+constexpr bool msm_ws_disjoint() {
+  int uses[MSM_WS] = {};
+  for (int r = 0; r < NROLES; r++) {
+    for (int j = 0; j < NJOBS; j++) uses[ws_job(j, r)]++;
+    for (int b = 0; b < NBATCH; b++) uses[ws_batch(b, r)]++;
+  }
+  for (int s = 0; s < NET_NSID; s++) uses[ws_dist(s)]++;
+  uses[WS_STANDALONE]++;
+  for (int u : uses)
+    if (u != 1) return false;
+  return true;
+}
+static_assert(msm_ws_disjoint(), "every MSM that may be in flight has a workspace slot of its own, and no slot is spare");
 
 // Sort-stage arrays of a launch over TWO base vectors with per-vector sorts (their identity bases differ) live in two
 // copies of one workspace region; blockIdx.y picks the copy: every sort-stage kernel shifts its array pointers by
@@ -1462,12 +1488,26 @@ struct KernelField<Fp2T<P, false>> {
 
 // ---------------------------------------------------------------------------------------------------- host
 // One workspace slot = device scratch + a pinned host buffer for the (S, A) pairs + the event that marks the end of
-// the slot's last launch.  Independent MSMs run on different slots / streams.
+// the slot's last launch.  Independent MSMs run on different slots / streams.  A slot is busy from the first enqueue of
+// a launch until wait() has seen its event: it holds the launch's tables until then and refuses other launches.
 struct MsmSlot {
   DevBuf ws;
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
   hipEvent_t ev = nullptr;
+  std::atomic<bool> busy{false};
+  std::shared_ptr<const MsmTable> tab, tab2;     // keep the tables alive while the kernels run
+  // Waits for the slot's last launch (bounded by the context's deadline): then the slot is free and drops its tables.
+  // hipErrorNotReady = the deadline passed; the slot stays busy (its kernels may still run).
+  hipError_t wait(const IEngine* eng) {
+    if (!busy) return hipSuccess;
+    hipError_t he = eng->event_wait(ev);
+    if (he == hipErrorNotReady) return he;
+    tab.reset();
+    tab2.reset();
+    busy = false;
+    return he;
+  }
   ~MsmSlot() {
     if (pinned) (void)hipHostFree(pinned);
     if (ev) (void)hipEventDestroy(ev);
@@ -1483,24 +1523,22 @@ struct MsmSlot {
   }
 };
 
-// A launched MSM (or two sharing one sort) whose (S, A) pairs are on their way to the slot's pinned buffer.
-// msm_fold() waits for the event and folds on the host.
 // the scalar vectors of a batched launch (host side of MsmScalars)
 struct MsmBatchArg {
   int nb = 1;
   const void* p[16] = {nullptr};
 };
 
+// The launch geometry of an MSM (or two sharing one sort) whose (S, A) pairs are on their way to the slot's pinned
+// buffer.  msm_fold() waits for the slot and folds on the host.
 struct MsmPending {
-  bool active = false;
   int kwin = 0, c = 0, wide = 0, nb = 1, lo_bits = 0;
   bool tabbed = false;                           // fixed-base table: one bucket set, every window c bits wide
   int batch = 1;                                 // scalar vectors of the launch (results: [base vector][batch])
   size_t stats_off = 0, offered = 0;             // statistics: where the sorts' entry counts land in the pinned buffer;
   int nsorts = 1;                                // (point, window) pairs offered to the sort
   bool g2 = false;
-  MsmSlot* slot = nullptr;
-  std::shared_ptr<const MsmTable> tab, tab2;     // keep the tables alive while the kernels run
+  MsmSlot* slot = nullptr;                       // nullptr: nothing was launched (no points), the results are identities
 };
 
 // Ordering between the accumulate kernels of concurrent launches (the Groth16 prover runs the G2 accumulate ahead of the
@@ -1624,17 +1662,11 @@ template <class Fld>
 int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
   const int batch = p.batch;
   for (int i = 0; i < nvec * batch; i++) results[i] = XYZZ<Fld>::identity();
-  if (!p.active) return ZK_OK;
-  p.active = false;
-  hipError_t he = eng->event_wait(p.slot->ev);
-  if (he == hipErrorNotReady) {
-    // the tables stay referenced (the kernels may still run); the caller aborts the job
-    p.active = true;
+  if (!p.slot) return ZK_OK;
+  hipError_t he = p.slot->wait(eng);
+  if (he == hipErrorNotReady)      // the slot stays busy (the kernels may still run); the caller wedges the context
     return eng->fail(ZK_ERR_GENERIC, std::string("msm fold: the completion event of a ") + (p.g2 ? "G2" : "G1") +
                                          " MSM chain did not signal within the deadline (zk_ctx_set_option wait_deadline_ms)");
-  }
-  p.tab.reset();
-  p.tab2.reset();
   if (he != hipSuccess) return eng->hip_fail(he, "msm event");
   const int kwin = p.kwin, c = p.c, wide = p.wide, lo_bits = p.lo_bits, nslices = p.c;
   const int hb = c - 1 - lo_bits;                  // row slices 0..hb come first, then lo_bits column slices
@@ -1758,7 +1790,7 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
 // single scalar vector: result (and result2 for the second base vector of the launch)
 template <class Fld>
 int msm_fold(IEngine* eng, MsmPending& p, XYZZ<Fld>* result, XYZZ<Fld>* result2) {
-  if (p.active && p.batch != 1) return eng->fail(ZK_ERR_GENERIC, "msm_fold on a batched launch");
+  if (p.slot && p.batch != 1) return eng->fail(ZK_ERR_GENERIC, "msm_fold on a batched launch");
   XYZZ<Fld> r[2];
   int rc = msm_fold_batch<Fld>(eng, p, r, result2 ? 2 : 1);
   *result = r[0];
@@ -1802,33 +1834,54 @@ class MsmRunner {
   void plan(size_t npts, bool g2, int* out) const { msm_plan_of<FrP>(npts, g2, out, g2 ? c_g2 : c_g1); }
   int c_g1 = 0, c_g2 = 0;        // zk_ctx_set_option "msm_c" / "msm_c_g2": forced window bits of table-free MSMs (0 = cost model)
 
-  // launch on workspace slot `wslot`; the result is collected with finish_t
+  // launch on workspace slot `ws` (ws_job, ws_batch, ...); the result is collected with msm_fold / msm_fold_batch.  A
+  // launch that fails after enqueueing work waits for that work: its slot is free again unless that wait expires too.
   template <class Fld>
-  int launch_t(IEngine* eng, const void* bases, const void* scalars, size_t npts, const Fr* coef_d, size_t part_len,
-               hipStream_t st, int wslot, MsmPending* pend, const void* bases2 = nullptr, MsmGate gate = MsmGate{},
+  int launch_t(IEngine* eng, int ws, const void* bases, const void* scalars, size_t npts, const Fr* coef_d,
+               size_t part_len, hipStream_t st, MsmPending* pend, const void* bases2 = nullptr, MsmGate gate = MsmGate{},
                const MsmBatchArg* batch = nullptr) {
-    if (wslot < 0 || wslot >= MSM_WS) return eng->fail(ZK_ERR_BAD_INPUT, "bad msm workspace slot");
-    if (pend->active) return eng->fail(ZK_ERR_GENERIC, "msm workspace slot still in flight");
+    if (ws < 0 || ws >= MSM_WS) return eng->fail(ZK_ERR_BAD_INPUT, "bad msm workspace slot");
+    if (slots_[ws].busy) return eng->fail(ZK_ERR_GENERIC, "msm workspace slot still in flight");
     MsmTuning tune{bigsort_min, gate, IsExtField<Fld>::value ? c_g2 : c_g1};
-    return msm_launch<FrP, Fld>(eng, slots_[wslot], tune, bases, bases2, scalars, npts, coef_d, part_len, st, pend,
-                                batch);
-  }
-  template <class Fld>
-  int finish_t(IEngine* eng, MsmPending* pend, XYZZ<Fld>* result, XYZZ<Fld>* result2 = nullptr) {
-    return msm_fold<Fld>(eng, *pend, result, result2);
+    int rc = msm_launch<FrP, Fld>(eng, slots_[ws], tune, bases, bases2, scalars, npts, coef_d, part_len, st, pend,
+                                  batch);
+    if (rc) (void)slots_[ws].wait(eng);
+    return rc;
   }
   // (Round 4 measured a large lone MSM as TWO window groups on two streams -- the sort of the upper windows under the
   // accumulate of the lower ones: 13.3-13.4 ms with the staged sort kernels, 15.2-15.3 with small-workgroup ones, against
   // 13.1-13.7 for the single launch: the accumulate kernel wants the chip to itself.  The path was removed in round 5.)
-  // blocking form
-  template <class Fld>
-  int run_t(IEngine* eng, const void* bases, const void* scalars, size_t npts, const Fr* coef_d, size_t part_len,
-            XYZZ<Fld>* result, hipStream_t st, int wslot = 0, const void* bases2 = nullptr,
-            XYZZ<Fld>* result2 = nullptr) {
-    MsmPending pend;
-    int rc = launch_t<Fld>(eng, bases, scalars, npts, coef_d, part_len, st, wslot, &pend, bases2);
+  // The blocking MSM of the standalone entry points: on the standalone slot (sid < 0), held under a mutex for the call so
+  // that host threads sharing a context take turns, or on the slot of net channel `sid` (zk_dist_d_msm).  `host()` runs
+  // while the device works; out: one point per scalar vector.  A wait that expires wedges the context (the slot stays busy).
+  template <class Fld, class Host>
+  int run_t(IEngine* eng, int sid, const void* bases, const void* scalars, size_t npts, const Fr* coef_d,
+            size_t part_len, hipStream_t st, XYZZ<Fld>* out, Host&& host, const MsmBatchArg* batch = nullptr) {
+    int rc = eng->check_wedged();
     if (rc) return rc;
-    return finish_t<Fld>(eng, &pend, result, result2);
+    std::unique_lock<std::mutex> lk(standalone_mu_, std::defer_lock);
+    if (sid < 0) lk.lock();
+    MsmPending pend;
+    rc = launch_t<Fld>(eng, sid < 0 ? WS_STANDALONE : ws_dist(sid), bases, scalars, npts, coef_d, part_len, st, &pend,
+                       nullptr, MsmGate{}, batch);
+    if (!rc) {
+      host();
+      rc = msm_fold_batch<Fld>(eng, pend, out, 1);
+    }
+    if (rc && pend.slot && pend.slot->busy) {
+      Status keep = eng->last;
+      return eng->wedge(keep.msg);
+    }
+    return rc;
+  }
+  // the G1 / G2 dispatch of the MSM entry points: f(Fq{}) or f(Fq2{})
+  template <class F>
+  static int by_group(IEngine* eng, int group, F&& f) {
+    if (group == ZK_G1) return f(Fq{});
+    if (group == ZK_G2) {
+      if constexpr (Cfg::HAS_G2) return f(Fq2{});
+    }
+    return eng->fail(ZK_ERR_BAD_INPUT, "bad group");
   }
 
   template <class Fld>
@@ -1836,31 +1889,28 @@ class MsmRunner {
     Jacobian<Fld> j = xyzz_to_jacobian(p);
     memcpy(out, &j, sizeof(j));
   }
+  // every one of `np` parties receives r plus its own out-mask (if any): Jacobian points out[np]
+  template <class Fld>
+  static void write_parties(void* out, const XYZZ<Fld>& r, const void* out_mask, int np) {
+    const Jacobian<Fld>* om = (const Jacobian<Fld>*)out_mask;
+    Jacobian<Fld>* o = (Jacobian<Fld>*)out;
+    for (int p = 0; p < np; p++) {
+      XYZZ<Fld> v = r;
+      if (om) v = xyzz_add_ni(v, jacobian_to_xyzz(om[p]));
+      o[p] = xyzz_to_jacobian(v);
+    }
+  }
 
   // G::msm: one Jacobian point to host memory.
-  int run(IEngine* eng, int group, const void* bases, const void* scalars, size_t npts, const Fr* coef_d,
-          size_t part_len, void* out, hipStream_t st) {
+  int run(IEngine* eng, int group, const void* bases, const void* scalars, size_t npts, void* out, hipStream_t st) {
     if (npts && (!bases || !scalars)) return eng->fail(ZK_ERR_BAD_INPUT, "null pointer");
     if (!out) return eng->fail(ZK_ERR_BAD_INPUT, "null output");
-    if (group == ZK_G1) {
-      XYZZ<Fq> r;
-      int rc = run_t<Fq>(eng, bases, scalars, npts, coef_d, part_len, &r, st);
-      if (rc) return rc;
-      write_jacobian(out, r);
-      return ZK_OK;
-    }
-    if (group == ZK_G2) {
-      if constexpr (Cfg::HAS_G2) {
-        XYZZ<Fq2> r;
-        int rc = run_t<Fq2>(eng, bases, scalars, npts, coef_d, part_len, &r, st);
-        if (rc) return rc;
-        write_jacobian(out, r);
-        return ZK_OK;
-      } else {
-        return eng->fail(ZK_ERR_BAD_INPUT, "G2 is not available for this curve");
-      }
-    }
-    return eng->fail(ZK_ERR_BAD_INPUT, "group must be ZK_G1 or ZK_G2");
+    return by_group(eng, group, [&](auto fld) {
+      XYZZ<decltype(fld)> r;
+      int rc = run_t(eng, -1, bases, scalars, npts, nullptr, 1, st, &r, [] {});
+      if (!rc) write_jacobian(out, r);
+      return rc;
+    });
   }
 
   // sum_p coef[first + p] * mask_p over `count` Jacobian points (the in-mask term of d_msm's king step)
@@ -1879,38 +1929,13 @@ class MsmRunner {
   // parties [first, first + count): bases/scalars [count][len]
   template <class Fld>
   int d_msm_range_t(IEngine* eng, const void* bases, const void* scalars, size_t len, int first, int count,
-                    const void* in_mask, XYZZ<Fld>* result, hipStream_t st, int wslot = 0) {
-    MsmPending pend;
-    int rc = launch_t<Fld>(eng, bases, scalars, (size_t)count * len, coef_d_ + first, len, st, wslot, &pend);
-    if (rc) return rc;
-    XYZZ<Fld> mt = XYZZ<Fld>::identity();
-    if (in_mask) mt = mask_term<Fld>(in_mask, first, count);
-    XYZZ<Fld> r;
-    rc = finish_t<Fld>(eng, &pend, &r);
+                    const void* in_mask, XYZZ<Fld>* result, hipStream_t st) {
+    XYZZ<Fld> r, mt = XYZZ<Fld>::identity();
+    int rc = run_t(eng, -1, bases, scalars, (size_t)count * len, coef_d_ + first, len, st, &r, [&] {
+      if (in_mask) mt = mask_term<Fld>(in_mask, first, count);
+    });
     if (rc) return rc;
     *result = in_mask ? xyzz_add_ni(r, mt) : r;
-    return ZK_OK;
-  }
-  template <class Fld>
-  int d_msm_sum_t(IEngine* eng, const void* bases, const void* scalars, size_t len, const void* in_mask,
-                  XYZZ<Fld>* result, hipStream_t st, int wslot = 0) {
-    return d_msm_range_t<Fld>(eng, bases, scalars, len, 0, eng->n, in_mask, result, st, wslot);
-  }
-
-  template <class Fld>
-  int d_msm_t(IEngine* eng, const void* bases, const void* scalars, size_t len, const void* in_mask,
-              const void* out_mask, void* out, hipStream_t st) {
-    const int n = eng->n;
-    XYZZ<Fld> r;
-    int rc = d_msm_sum_t<Fld>(eng, bases, scalars, len, in_mask, &r, st);
-    if (rc) return rc;
-    const Jacobian<Fld>* om = (const Jacobian<Fld>*)out_mask;
-    Jacobian<Fld>* o = (Jacobian<Fld>*)out;
-    for (int p = 0; p < n; p++) {
-      XYZZ<Fld> v = r;
-      if (om) v = xyzz_add_ni(v, jacobian_to_xyzz(om[p]));
-      o[p] = xyzz_to_jacobian(v);
-    }
     return ZK_OK;
   }
 
@@ -1919,12 +1944,12 @@ class MsmRunner {
     if (!out) return eng->fail(ZK_ERR_BAD_INPUT, "null output");
     if (len && (!bases || !scalars)) return eng->fail(ZK_ERR_BAD_INPUT, "null pointer");
     if (!coef_d_) return eng->fail(ZK_ERR_GENERIC, "d_msm coefficients not initialised");
-    if (group == ZK_G1) return d_msm_t<Fq>(eng, bases, scalars, len, in_mask, out_mask, out, st);
-    if (group == ZK_G2) {
-      if constexpr (Cfg::HAS_G2) return d_msm_t<Fq2>(eng, bases, scalars, len, in_mask, out_mask, out, st);
-      else return eng->fail(ZK_ERR_BAD_INPUT, "G2 is not available for this curve");
-    }
-    return eng->fail(ZK_ERR_BAD_INPUT, "group must be ZK_G1 or ZK_G2");
+    return by_group(eng, group, [&](auto fld) {
+      XYZZ<decltype(fld)> r;
+      int rc = d_msm_range_t(eng, bases, scalars, len, 0, eng->n, in_mask, &r, st);
+      if (!rc) write_parties(out, r, out_mask, eng->n);
+      return rc;
+    });
   }
 
   // d_msm with explicit per-contributor coefficients (party subsets): bases/scalars [coef.size()][len]; every one
@@ -1938,18 +1963,15 @@ class MsmRunner {
     hipError_t he = hipMalloc((void**)&cd, np * sizeof(Fr));
     if (he != hipSuccess) return eng->hip_fail(he, "hipMalloc coef");
     he = hipMemcpy(cd, coef.data(), np * sizeof(Fr), hipMemcpyHostToDevice);
-    XYZZ<Fld> r;
-    int rc = he == hipSuccess ? run_t<Fld>(eng, bases, scalars, (size_t)np * len, cd, len, &r, st) : eng->hip_fail(he, "memcpy");
+    XYZZ<Fld> r, mt = XYZZ<Fld>::identity();
+    int rc = he != hipSuccess ? eng->hip_fail(he, "memcpy")
+                              : run_t(eng, -1, bases, scalars, (size_t)np * len, cd, len, st, &r, [&] {
+                                  if (in_mask) mt = mask_term<Fld>(in_mask, 0, np, coef.data());
+                                });
     (void)hipFree(cd);
     if (rc) return rc;
-    if (in_mask) r = xyzz_add_ni(r, mask_term<Fld>(in_mask, 0, np, coef.data()));
-    const Jacobian<Fld>* om = (const Jacobian<Fld>*)out_mask;
-    Jacobian<Fld>* o = (Jacobian<Fld>*)out;
-    for (int p = 0; p < eng->n; p++) {
-      XYZZ<Fld> v = r;
-      if (om) v = xyzz_add_ni(v, jacobian_to_xyzz(om[p]));
-      o[p] = xyzz_to_jacobian(v);
-    }
+    if (in_mask) r = xyzz_add_ni(r, mt);
+    write_parties(out, r, out_mask, eng->n);
     return ZK_OK;
   }
 
@@ -2064,6 +2086,7 @@ class MsmRunner {
   // two-level sort from this many points on (zk_ctx_set_option "msm_bigsort_min")
   size_t bigsort_min = (size_t)1 << 14;
   MsmSlot slots_[MSM_WS];
+  std::mutex standalone_mu_;     // held by run_t for the call on the standalone slot
   Fr* coef_d_ = nullptr;
   std::vector<Fr> coef_h_;
 };

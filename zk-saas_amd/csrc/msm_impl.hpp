@@ -12,7 +12,7 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
                const void* scalars, size_t npts, const Fp<FrP>* coef_d, size_t part_len, hipStream_t st,
                MsmPending* pend, const MsmBatchArg* ba) {
   using Fr = Fp<FrP>;
-  pend->active = false;
+  *pend = MsmPending{};
   const unsigned NB = bases2 ? 2u : 1u;
   const size_t batch = ba ? (size_t)ba->nb : 1;    // scalar vectors multiplied against the same base vector(s)
   if (batch < 1 || batch > (size_t)MSM_MAXB) return eng->fail(ZK_ERR_BAD_INPUT, "bad msm batch");
@@ -150,6 +150,20 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
     he = hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming);
     if (he != hipSuccess) return eng->hip_fail(he, "msm event");
   }
+  // From the first enqueue on the slot is busy and holds the tables; every exit records its event (a failed launch may
+  // have enqueued work), so that only MsmSlot::wait frees it.
+  slot.busy = true;
+  slot.tab = tab;
+  slot.tab2 = tab2;
+  pend->slot = &slot;
+  struct RecordOnExit {
+    MsmSlot& s;
+    hipStream_t st;
+    bool done = false;
+    ~RecordOnExit() {
+      if (!done) (void)hipEventRecord(s.ev, st);
+    }
+  } record_on_exit{slot, st};
   char* ws = (char*)slot.ws.p;
   uint32_t* counts = (uint32_t*)(ws + o_counts);
   uint32_t* cursor = (uint32_t*)(ws + o_cursor);
@@ -375,22 +389,19 @@ do {                                                                           \
   MSM_HIP(hipGetLastError());
   MSM_STAGE("reduce");
   MSM_HIP(hipEventRecord(slot.ev, st));
+  record_on_exit.done = true;
 #undef MSM_HIP
 #undef MSM_STAGE
-  pend->active = true;
   pend->kwin = kwin;
   pend->c = c;
   pend->wide = wide;
   pend->nb = (int)NB;
   pend->lo_bits = lo_bits;
-  pend->slot = &slot;
   pend->stats_off = out_bytes;
   pend->nsorts = (int)NS;
   pend->g2 = G2FLD;
   pend->offered = npts * batch * NB * (size_t)nwin;
   pend->tabbed = (bool)tab;
-  pend->tab = std::move(tab);
-  pend->tab2 = std::move(tab2);
   return ZK_OK;
 }
 
