@@ -278,3 +278,59 @@ def test_proof_with_fixed_base_tables_equals_proof_without():
     crs.precompute()
     tabled = [norm(zg.prove(pp, crs, wit, rr, s, seed=5)) for rr in (r, 0)]
     assert plain == tabled
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("skip_h", [0, 1])
+def test_msms_begin_finish_equal_d_msm_local(masked, skip_h):
+    """zk_groth16_msms_begin / _finish (the MSM half of the multi-GPU flow) over parties [first, first + k) of the small
+    circuit: out[0..4] = S, H, V (G2), W, U are the zk_d_msm_local of the same base vector, shares, party range and
+    in-mask (U over the h_share given to _finish); skip_h gives the identity for H; begin twice or finish alone is
+    ZK_ERR_BAD_INPUT."""
+    from zksaas_amd import multigpu as mg
+    from zksaas_amd.api import ZK_G1, ZK_G2
+    ZK_ERR_BAD_INPUT = 4
+    r1, w = small_r1cs()
+    pp = zk.PackedSharingParams("bn254", 2)
+    try:
+        crs = zg.Crs(pp, zg.SetupScalars("bn254", r1, *_trapdoor(46)))
+        wit = zg.Witness(pp, "bn254", r1, w, seed=12)
+        Lc = (1 << wit.log_m) // pp.l
+        assert crs.len_u == Lc
+        masks = zg.ProofMasks(pp, wit.log_m, seed=400) if masked else None
+        h_full = pp.alloc_fr(pp.n * Lc)
+        pp._check(pp.lib.zk_circom_h(pp.h, wit.qap[0].ptr, wit.qap[1].ptr, wit.qap[2].ptr, wit.log_m, None, 7,
+                                     h_full.ptr, None))
+        pp.sync()
+        G1, G2 = g1(BN254), g2(BN254)
+        nl = pp.fq.nl
+        bufs = [np.zeros((6 if i == 2 else 3) * nl, dtype=np.uint64) for i in range(5)]
+        arr = (C.c_void_p * 5)(*[b.ctypes.data for b in bufs])
+        assert pp.lib.zk_groth16_msms_finish(pp.h, h_full.ptr, arr, None) == ZK_ERR_BAD_INPUT     # finish without begin
+        for first, k in ((0, pp.n), (2, 4), (pp.n - 1, 1)):
+            lcrs = mg.LocalCrs(pp, crs, first, k)
+            _, a_sh, ax_sh = mg.local_witness(pp, wit, first, k)
+            h = mg.rows(h_full, first, k, Lc * pp.fr.nbytes)
+            mct, keep = mg.local_masks(pp, masks, wit.log_m, first, k)
+            mref = None if mct is None else C.byref(mct)
+            pp._check(pp.lib.zk_groth16_msms_begin(pp.h, C.byref(lcrs.ct), a_sh.ptr, ax_sh.ptr, first, k, skip_h, mref, None))
+            assert pp.lib.zk_groth16_msms_begin(pp.h, C.byref(lcrs.ct), a_sh.ptr, ax_sh.ptr, first, k, skip_h, mref,
+                                                None) == ZK_ERR_BAD_INPUT                          # begin twice
+            pp._check(pp.lib.zk_groth16_msms_finish(pp.h, h.ptr, arr, None))
+            assert pp.lib.zk_groth16_msms_finish(pp.h, h.ptr, arr, None) == ZK_ERR_BAD_INPUT       # the job is joined
+            legs = [(ZK_G1, lcrs.s, a_sh, crs.len_a), (ZK_G1, lcrs.h, a_sh, crs.len_a), (ZK_G2, lcrs.v, a_sh, crs.len_a),
+                    (ZK_G1, lcrs.w, ax_sh, crs.len_w), (ZK_G1, lcrs.u, h, crs.len_u)]
+            for i, (grp, bases, scal, ln) in enumerate(legs):
+                is2 = grp == ZK_G2
+                G = G2 if is2 else G1
+                got = dec_jacobian(pp, bufs[i], is2)
+                if i == 1 and skip_h:
+                    assert G.eq(got, G.identity), (first, k)
+                    continue
+                want = np.zeros((6 if is2 else 3) * nl, dtype=np.uint64)
+                pp._check(pp.lib.zk_d_msm_local(pp.h, grp, bases.ptr, scal.ptr, ln, first, k,
+                                                None if mct is None else mct.msm_in[i], want.ctypes.data, None))
+                assert G.eq(got, dec_jacobian(pp, want, is2)), (i, first, k)
+                assert not G.eq(got, G.identity), (i, first, k)
+    finally:
+        pp.close()

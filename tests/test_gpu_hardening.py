@@ -85,6 +85,7 @@ def test_a_wait_that_cannot_be_met_is_an_error_not_a_hang(capfd):
     assert e.value.code == 1 and "deadline" in str(e.value)                 # ZK_ERR_GENERIC = MpcNetError::Generic
     err = capfd.readouterr().err
     assert "[zksaas]" in err and "batch slot" in err and "chain event" in err
+    assert "pool tasks pending" in err and "launched-flag" in err           # the common dump format, batch extras
     # the context refuses further proofs at once (its slot still holds work), a fresh one is unaffected
     pp.set_option("wait_deadline_ms", 120000)
     with pytest.raises(zk.ZkError) as e2:

@@ -7,7 +7,7 @@
   // not show up within the timeout are left out and the king goes through lagrange_unpack (pss.rs:170-221) like
   // ser_net.rs:57-94 does with `Partial` results.
   DevBuf dist_in_[NET_NSID], dist_out_[NET_NSID], dist_coef_[NET_NSID];
-  DevBuf dist_w0_, dist_w1_, dist_h_;
+  DevBuf dist_w0_;
 
   int net_err(Net* net, int rc) {
     if (rc == ZK_OK) return rc;
@@ -439,9 +439,7 @@
       }
       for (int j = 0; j < 3; j++) {
         const int mi = phase * 3 + j;
-        const bool masked = mk && mk->fft_in[mi];
         if ((mk && mk->fft_in[mi] != nullptr) != has_in) return fail(ZK_ERR_BAD_INPUT, "mixed in-masks in circom_h");
-        (void)masked;
         rc = dist_d_fft_on(net, j, cmask[j], W + j * per, mk ? (const Fr*)mk->fft_in[mi] : nullptr,
                            mk ? (const Fr*)mk->fft_out[mi] : nullptr, phase == 0 ? 1 : 0, log_m, inverse,
                            phase == 0 ? (const void*)&w2m : nullptr, seed + mi, false);
@@ -733,94 +731,92 @@
   //                     for all five products in one message, dmsm/mod.rs:76-92) and assembles the k proof shares.
   // Every rank issues the same sequence of calls (channels are ordered, multi.rs:418-445): async(A), async(B), wait(A),
   // wait(B) overlaps B's king rounds with A's MSMs.
-  struct DistJob {
-    bool active = false;
-    int k = 0;
-    uint32_t cmask3 = 0;
-  };
-  DistJob djobs_[NJOBS];
   DevBuf dist_wj_[NJOBS], dist_hj_[NJOBS];
-  int dist_prove_async(Net* net, const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
-                       const void* a_share, const void* ax_share, const void* r_, const void* s_, int log_m,
-                       const zk_groth16_masks* mk, uint64_t seed, hipStream_t st, int* handle) override {
-    int rc = check_prove_args(crs, r_, s_, log_m);
+  // Control-plane admission of a sharded proof or batch: this rank's party window, then the round of every channel, then
+  // all parties present (that order is part of the protocol).  first: index of the rank's first party in the coefficient
+  // table; cmask: the channels' party masks.
+  int dist_admit(Net* net, const char* what, int* first, uint32_t* cmask) {
+    int rc = local_window(net, first);
     if (rc) return rc;
-    if (!qa || !qb || !qc || !a_share || !ax_share || !handle) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    int slot = -1;
-    for (int i = 0; i < NJOBS; i++)
-      if (!jobs_[i].active && !djobs_[i].active) {
-        slot = i;
-        break;
-      }
-    if (slot < 0) return fail(ZK_ERR_BAD_INPUT, "too many proofs in flight (zk_dist_groth16_wait one first)");
-    const int k = net->parties_per_rank();
-    int first = 0;
-    rc = local_window(net, &first);
-    if (rc) return rc;
-    const size_t Lc = ((size_t)1 << log_m) / l;
-    uint32_t cmask[NET_NSID];
     for (int j = 0; j < NET_NSID; j++) {
       rc = net_err(net, net->enter(j, &cmask[j]));
       if (rc) return rc;
     }
     for (int j = 0; j < NET_NSID; j++)
       if (cmask[j] != net->full_mask())
-        return fail(ZK_ERR_PROTOCOL, "a party did not show up for the proof (timed out)", -1);
+        return fail(ZK_ERR_PROTOCOL, std::string("a party did not show up for the ") + what + " (timed out)", -1);
+    return ZK_OK;
+  }
+  // d_msm's king step for the five products of `cnt` proofs (dmsm/mod.rs:76-92), in place: this rank's totals go to the
+  // king on channel 3 as host messages of as many proofs as fit the payload, rank 0 adds the ranks' and broadcasts.
+  int sum_over_ranks(Net* net, uint32_t cmask3, MsmSums* sums, int cnt) {
+    const int per_msg = (int)(NET_PAYLOAD / sizeof(MsmSums));
+    std::vector<MsmSums> all((size_t)net->world * std::min(cnt, per_msg));
+    for (int b0 = 0; b0 < cnt; b0 += per_msg) {
+      const int c = std::min(cnt - b0, per_msg);
+      const size_t bytes = (size_t)c * sizeof(MsmSums);
+      int rc = net_err(net, net->gather_host(3, cmask3, sums + b0, bytes, all.data()));
+      if (rc) return rc;
+      if (net->rank == 0)
+        for (int rr = 1; rr < net->world; rr++)
+          for (int i = 0; i < c; i++) {
+            const MsmSums& o = all[(size_t)rr * c + i];
+            MsmSums& t_ = sums[b0 + i];
+            t_.S = xyzz_add_ni(t_.S, o.S);
+            t_.H = xyzz_add_ni(t_.H, o.H);
+            t_.V = xyzz_add_ni(t_.V, o.V);
+            t_.W = xyzz_add_ni(t_.W, o.W);
+            t_.U = xyzz_add_ni(t_.U, o.U);
+          }
+      rc = net_err(net, net->bcast_host(3, cmask3, sums + b0, bytes));
+      if (rc) return rc;
+    }
+    return ZK_OK;
+  }
+  int dist_prove_async(Net* net, const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
+                       const void* a_share, const void* ax_share, const void* r_, const void* s_, int log_m,
+                       const zk_groth16_masks* mk, uint64_t seed, hipStream_t st, int* handle) override {
+    int rc = check_prove_args(crs, r_, s_, log_m);
+    if (rc) return rc;
+    if (!qa || !qb || !qc || !a_share || !ax_share || !handle) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    ProveJob* jp = free_job(jobs_);
+    if (!jp) return fail(ZK_ERR_BAD_INPUT, "too many proofs in flight (zk_dist_groth16_wait one first)");
+    ProveJob& j = *jp;
+    const int k = net->parties_per_rank();
+    int first = 0;
+    uint32_t cmask[NET_NSID];
+    rc = dist_admit(net, "proof", &first, cmask);
+    if (rc) return rc;
+    const size_t Lc = ((size_t)1 << log_m) / l;
     Fr r = Fr::from_limbs((const uint32_t*)r_), s = Fr::from_limbs((const uint32_t*)s_);
-    ProveJob& j = jobs_[slot];
-    j.slot = slot;
     // the four MSMs over the witness shares start now and overlap the king rounds of circom_h (prove.rs try_join!)
     rc = prove_begin(j, crs, nullptr, nullptr, nullptr, a_share, ax_share, r, s, log_m, mk, seed, false, first, k, st, true);
-    auto bail = [&](int code) {
-      Status keep = last;
-      abort_job(j);
-      last = keep;
-      return code;
-    };
-    if (rc) return bail(rc);
+    if (rc) return rc;
     {
-      hipError_t he = dist_hj_[slot].ensure((size_t)k * Lc * sizeof(Fr));
-      if (he != hipSuccess) return bail(hip_fail(he, "h share buffer"));
+      hipError_t he = dist_hj_[j.slot].ensure((size_t)k * Lc * sizeof(Fr));
+      if (he != hipSuccess) return bail(j, hip_fail(he, "h share buffer"));
     }
-    rc = dist_circom_h_on(net, cmask, qa, qb, qc, log_m, mk, seed, dist_hj_[slot].p, st, &dist_wj_[slot]);
-    if (rc) return bail(rc);
-    rc = prove_launch_u(j, dist_hj_[slot].p, st);
-    if (rc) return bail(rc);
-    djobs_[slot].active = true;
-    djobs_[slot].k = k;
-    djobs_[slot].cmask3 = cmask[3];
-    *handle = slot;
+    rc = dist_circom_h_on(net, cmask, qa, qb, qc, log_m, mk, seed, dist_hj_[j.slot].p, st, &dist_wj_[j.slot]);
+    if (rc) return bail(j, rc);
+    rc = prove_launch_u(j, dist_hj_[j.slot].p, st);
+    if (rc) return bail(j, rc);
+    j.sharded = true;
+    j.k = k;
+    j.cmask3 = cmask[3];
+    *handle = j.slot;
     return ZK_OK;
   }
   int dist_prove_wait(Net* net, int handle, void* pi_a, void* pi_b, void* pi_c) override {
-    if (handle < 0 || handle >= NJOBS || !djobs_[handle].active) return fail(ZK_ERR_BAD_INPUT, "no sharded proof in flight on this handle");
+    if (handle < 0 || handle >= NJOBS || !jobs_[handle].sharded) return fail(ZK_ERR_BAD_INPUT, "no sharded proof in flight on this handle");
     if (!pi_a || !pi_b || !pi_c) return fail(ZK_ERR_BAD_INPUT, "null pointer");
     ProveJob& j = jobs_[handle];
-    DistJob& d = djobs_[handle];
-    d.active = false;
-    struct Sums {
-      P1 S, H, W, U;
-      P2 V;
-    } mine, total;
-    int rc = prove_join(j, &mine.S, &mine.H, &mine.V, &mine.W, &mine.U);
+    j.sharded = false;
+    int rc = join(j, "zk_dist_groth16_wait");
     if (rc) return rc;
-    static_assert(sizeof(Sums) <= NET_PAYLOAD, "payload");
-    std::vector<Sums> all((size_t)net->world);
-    rc = net_err(net, net->gather_host(3, d.cmask3, &mine, sizeof(mine), all.data()));
+    MsmSums total = j.pt.sums();
+    rc = sum_over_ranks(net, j.cmask3, &total, 1);
     if (rc) return rc;
-    total = mine;
-    if (net->rank == 0)
-      for (int rr = 1; rr < net->world; rr++) {
-        total.S = xyzz_add_ni(total.S, all[rr].S);
-        total.H = xyzz_add_ni(total.H, all[rr].H);
-        total.V = xyzz_add_ni(total.V, all[rr].V);
-        total.W = xyzz_add_ni(total.W, all[rr].W);
-        total.U = xyzz_add_ni(total.U, all[rr].U);
-      }
-    rc = net_err(net, net->bcast_host(3, d.cmask3, &total, sizeof(total)));
-    if (rc) return rc;
-    return assemble_points(&j.crs, j.r, j.s, total.S, total.H, total.V, total.W, total.U, j.has_mk ? &j.mk : nullptr, d.k, pi_a,
-                           pi_b, pi_c);
+    return assemble_points(&j.pt.crs, j.pt.r, j.pt.s, total, j.pt.masks(), j.k, pi_a, pi_b, pi_c);
   }
   int dist_prove(Net* net, const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
                  const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk,
@@ -850,67 +846,33 @@
     int first = 0;
     const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)k * Lc;
     uint32_t cmask[NET_NSID];
-    int rc = local_window(net, &first);
+    int rc = dist_admit(net, "batch", &first, cmask);
     if (rc) return rc;
-    for (int j = 0; j < NET_NSID; j++) {
-      rc = net_err(net, net->enter(j, &cmask[j]));
-      if (rc) return rc;
-    }
-    for (int j = 0; j < NET_NSID; j++)
-      if (cmask[j] != net->full_mask())
-        return fail(ZK_ERR_PROTOCOL, "a party did not show up for the batch (timed out)", -1);
-    int slot = -1;
-    rc = batch_begin(crs, nb, a_share, ax_share, r_, s_, log_m, mk, false, first, k, st, &slot);
+    BatchJob* Bp = nullptr;
+    rc = batch_begin(crs, nb, a_share, ax_share, r_, s_, log_m, mk, false, first, k, st, &Bp);
     if (rc) return rc;
-    BatchJobX& B = bjobs_[slot];
-    auto bail = [&](int code) {
-      Status keep = last;
-      abort_batch(B);
-      last = keep;
-      return code;
-    };
+    BatchJob& B = *Bp;
     // circom_h of the whole batch: one king round per phase and channel carries all nb proofs (7 rounds per batch; the MSMs
     // of the batch run beside them; round 3 ran one proof's rounds after the other's).
     rc = dist_circom_h_batch_on(net, cmask, nb, qa, qb, qc, log_m, mk, seed, (Fr*)B.hshare.p, st);
-    if (rc) return bail(rc);
+    if (rc) return bail(B, rc);
     // the U-MSM runs on its own stream of the batch's set, behind everything queued on the caller's stream
     {
       hipError_t he = hipEventRecord(B.ev_in, st);
       if (he == hipSuccess) he = hipStreamWaitEvent(B.st[5], B.ev_in, 0);
-      if (he != hipSuccess) return bail(hip_fail(he, "batch U-MSM ordering"));
+      if (he != hipSuccess) return bail(B, hip_fail(he, "batch U-MSM ordering"));
     }
     rc = batch_launch_u(B, (const Fr*)B.hshare.p, per, B.st[5]);
-    if (rc) return bail(rc);
-    std::vector<BatchSums> mine;
-    rc = batch_join(B, mine);
+    if (rc) return bail(B, rc);
+    rc = join(B, "zk_dist_groth16_prove_batch");
     if (rc) return rc;
-    // d_msm's king step for the 5 nb products (dmsm/mod.rs:76-92): host messages of as many proofs as fit the payload
-    std::vector<BatchSums> total = mine;
-    const int per_msg = (int)(NET_PAYLOAD / sizeof(BatchSums));
-    static_assert(sizeof(BatchSums) <= NET_PAYLOAD, "payload");
-    std::vector<BatchSums> all((size_t)net->world * per_msg);
-    for (int b0 = 0; b0 < nb; b0 += per_msg) {
-      const int cnt = nb - b0 < per_msg ? nb - b0 : per_msg;
-      const size_t bytes = (size_t)cnt * sizeof(BatchSums);
-      rc = net_err(net, net->gather_host(3, cmask[3], mine.data() + b0, bytes, all.data()));
-      if (rc) return rc;
-      if (net->rank == 0)
-        for (int rr = 1; rr < net->world; rr++)
-          for (int i = 0; i < cnt; i++) {
-            const BatchSums& o = *(const BatchSums*)((const char*)all.data() + (size_t)rr * bytes + (size_t)i * sizeof(BatchSums));
-            BatchSums& t_ = total[b0 + i];
-            t_.S = xyzz_add_ni(t_.S, o.S);
-            t_.H = xyzz_add_ni(t_.H, o.H);
-            t_.V = xyzz_add_ni(t_.V, o.V);
-            t_.W = xyzz_add_ni(t_.W, o.W);
-            t_.U = xyzz_add_ni(t_.U, o.U);
-          }
-      rc = net_err(net, net->bcast_host(3, cmask[3], total.data() + b0, bytes));
-      if (rc) return rc;
-    }
+    std::vector<MsmSums> total((size_t)nb);
+    for (int b = 0; b < nb; b++) total[b] = B.pt[b].sums();
+    rc = sum_over_ranks(net, cmask[3], total.data(), nb);
+    if (rc) return rc;
     for (int b = 0; b < nb; b++) {
-      const ProveJob& j = *B.pj[b];
-      rc = assemble_points(crs, j.r, j.s, total[b].S, total[b].H, total[b].V, total[b].W, total[b].U, mk ? &mk[b] : nullptr, k,
+      const ProofTerms& j = B.pt[b];
+      rc = assemble_points(crs, j.r, j.s, total[b], mk ? &mk[b] : nullptr, k,
                            (char*)pi_a + (size_t)b * k * sizeof(Jacobian<Fq_>), (char*)pi_b + (size_t)b * k * sizeof(Jacobian<Fq2_>),
                            (char*)pi_c + (size_t)b * k * sizeof(Jacobian<Fq_>));
       if (rc) return rc;

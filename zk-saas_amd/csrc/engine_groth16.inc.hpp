@@ -136,21 +136,21 @@
   }
 
   // ---------------------------------------------------------------- prover (prove.rs, sha256.rs:32-129)
-  // One proof in flight = one ProveJob: its device scratch, the pending MSMs and the host-side terms.  Everything the
-  // host contributes (scalar multiples of CRS constants, of the out-masks and of the in-mask sums, MSM window folds)
-  // is a task of the context's persistent pool, submitted when the proof starts and running beside the device work
-  // (the overlap the reference gets from tokio::try_join!, prove.rs:209-227); prove_end only adds points.
-  struct ProveJob {
-    bool active = false;
-    int slot = 0;
+  // Everything the host contributes to a proof (scalar multiples of CRS constants, of the out-masks and of the in-mask
+  // sums, MSM window folds) is a task of the context's persistent pool, submitted when the proof starts and running
+  // beside the device work (the overlap the reference gets from tokio::try_join!, prove.rs:209-227); the end of a proof
+  // only adds points.  The bookkeeping is split by what it belongs to:
+  //   ProofTerms   ONE proof, whatever launched it: its inputs, the MSM results and every host term;
+  //   JobCore      ONE set of MSM chains in flight: workspace slots, pending launches, scratch, pool tasks, events;
+  //   ProveJob     JobCore + one ProofTerms (a single or a sharded proof); BatchJob: JobCore + nb ProofTerms.
+  // Slot lookup, busy, drain, dump, abort, bail and join work on the JobCore, whichever kind of job it is part of.
+
+  struct ProofTerms {
     zk_crs_share crs{};
     zk_groth16_masks mk{};
-    bool has_mk = false, r_zero = false, full = true, gate_sorts = false;
-    std::atomic<int> sorted_cnt{0};     // witness MSMs of this proof whose sort has been enqueued and recorded (MsmGate)
+    bool has_mk = false, r_zero = false, full = true;
     int first = 0, count = 0;
     Fr r, s;
-    DevBuf hwork, hshare;
-    MsmPending msm[NROLES];                         // by MsmRole (msm.hpp); workspace slots ws_job(slot, role)
     P1 S, H, W, U, sS, rH;
     P2 V0;
     P1 rN, sK, rsM, s_cA, r_cB1;
@@ -158,12 +158,82 @@
     P1 in1[5], s_in0, r_in1;                        // in-mask sums (index 2 unused) and their multiples
     P2 in2;
     std::vector<P1> s_om0, r_om1;                   // per party: s * out_mask_A[p], r * out_mask_B1[p]
-    std::vector<std::future<void>> fut;
-    int rc[ROLE_U] = {};                            // results of the S+H, W and V tasks (U is folded by the join)
     Status err;                                     // first failure reported by a task (tasks must not touch `last`)
     std::mutex emu;
+    const zk_groth16_masks* masks() const { return has_mk ? &mk : nullptr; }
+    MsmSums sums() const {
+      return {xyzz_add_ni(S, in1[0]), r_zero ? P1::identity() : xyzz_add_ni(H, in1[1]), xyzz_add_ni(W, in1[3]),
+              xyzz_add_ni(U, in1[4]), xyzz_add_ni(V0, in2)};
+    }
+  };
+  struct JobCore {
+    const bool is_batch;
+    bool active = false;
+    int slot = 0, ws0 = 0;                          // handle; workspace slot of role 0 (ws_job / ws_batch): set by Engine()
+    MsmPending msm[NROLES];                         // by MsmRole (msm.hpp); workspace slots ws0 + role
+    DevBuf hwork, hshare;
+    std::vector<std::future<void>> fut;
+    int rc[ROLE_U] = {};                            // results of the S+H, W and V tasks (U is folded by the join)
+    hipEvent_t ev_in = nullptr;                     // orders the job's streams behind the caller's
+    hipEvent_t ev_role[NROLES] = {};                // by MsmRole: behind the sort (a proof's "all sorts first" barrier,
+                                                    // prove_begin_impl) or behind the accumulate kernel (a batch's chain)
+    explicit JobCore(bool batch) : is_batch(batch) {}
+    ~JobCore() {
+      if (ev_in) (void)hipEventDestroy(ev_in);
+      for (hipEvent_t e : ev_role)
+        if (e) (void)hipEventDestroy(e);
+    }
+  };
+  // One proof in flight.  `sharded`: started by zk_dist_groth16_prove_async for this rank's k parties -- the handle is
+  // then joined by zk_dist_groth16_wait only (and released by zk_groth16_abort like any other).
+  struct ProveJob : JobCore {
+    ProveJob() : JobCore(false) {}
+    ProofTerms pt;
+    bool gate_sorts = false, sharded = false;
+    std::atomic<int> sorted_cnt{0};     // witness MSMs of this proof whose sort has been enqueued and recorded (MsmGate)
+    int k = 0;
+    uint32_t cmask3 = 0;
   };
   ProveJob jobs_[NJOBS];
+  // A batch of proofs against one CRS in flight (zk_groth16_prove_batch_async).  Each batch slot has its own MSM
+  // workspaces, scratch and stream set, so that the sort phase of one batch runs under the accumulate kernels of the
+  // other and the reduction tails of one under the other's accumulates -- one batch alone leaves the chip partly idle
+  // for ~1 ms at either end.
+  struct BatchJob : JobCore {
+    BatchJob() : JobCore(true) {}
+    int nb = 0;
+    std::deque<ProofTerms> pt;                      // per proof (grows to the largest batch seen)
+    bool own_streams = false;
+    MsmGate gate_u;
+    std::atomic<int> acc_flag[NROLES] = {};         // by role: the record of ev_role has been enqueued (MsmGate)
+    hipStream_t st[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~BatchJob() {
+      if (own_streams)
+        for (hipStream_t s_ : st)
+          if (s_) (void)hipStreamDestroy(s_);
+    }
+  };
+  BatchJob bjobs_[NBATCH];
+
+  static const char* kind(const JobCore& c) { return c.is_batch ? "batch" : "proof"; }
+  static int nproofs(const JobCore& c) { return c.is_batch ? static_cast<const BatchJob&>(c).nb : 1; }
+  static ProofTerms& terms(JobCore& c, int b) {
+    return c.is_batch ? static_cast<BatchJob&>(c).pt[b] : static_cast<ProveJob&>(c).pt;
+  }
+  // the first free job of a kind, nullptr when all are in flight
+  template <class Job, size_t N>
+  static Job* free_job(Job (&jobs)[N]) {
+    for (Job& j : jobs)
+      if (!j.active) return &j;
+    return nullptr;
+  }
+  // every handle is checked on its own: a failure half-way leaves the rest to be created by the next call
+  int ensure_events(JobCore& c) {
+    if (!c.ev_in) ZK_HIP(hipEventCreateWithFlags(&c.ev_in, hipEventDisableTiming));
+    for (hipEvent_t& e : c.ev_role)
+      if (!e) ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return ZK_OK;
+  }
 
   static P1 aff1(const void* p) {
     Affine<Fq_> a;
@@ -184,65 +254,102 @@
     hipError_t q = hipEventQuery(e);
     return q == hipSuccess ? "done" : (q == hipErrorNotReady ? "PENDING" : hipGetErrorString(q));
   }
-  static int futs_pending(std::vector<std::future<void>>& fut) {
-    int np = 0;
-    for (auto& f : fut)
-      if (f.valid() && f.wait_for(std::chrono::seconds(0)) != std::future_status::ready) np++;
-    return np;
-  }
-  // joins the pool tasks of a job; false = some did not finish within the deadline (they stay in `fut`)
-  bool drain_futs(std::vector<std::future<void>>& fut) {
-    const auto dl = deadline_from_now();
-    for (auto& f : fut)
-      if (f.valid() && f.wait_until(dl) != std::future_status::ready) return false;
-    fut.clear();
-    return true;
-  }
-  bool drain(ProveJob& j) { return drain_futs(j.fut); }
-  MsmSlot& job_slot(const ProveJob& j, int role) { return msm_.slots_[ws_job(j.slot, role)]; }
+  MsmSlot& job_slot(const JobCore& c, int role) { return msm_.slots_[c.ws0 + role]; }
   // once the job's tasks are joined, a busy slot is a wait that expired: its work may still run
-  bool job_busy(const ProveJob& j) {
+  bool busy(const JobCore& c) {
     for (int r = 0; r < NROLES; r++)
-      if (job_slot(j, r).busy) return true;
+      if (job_slot(c, r).busy) return true;
     return false;
   }
-  void dump_job(const char* why, ProveJob& j) {
-    fprintf(stderr, "[zksaas] %s: proof slot %d: pool tasks pending %d, sorted_cnt %d; MSM events", why, j.slot,
-            futs_pending(j.fut), j.sorted_cnt.load());
-    for (int r = 0; r < NROLES; r++)
-      fprintf(stderr, " %s %s%s%s", ROLE_NAME[r], job_slot(j, r).busy ? "" : "(idle) ", ev_state(job_slot(j, r).ev),
-              r + 1 < NROLES ? "," : "\n");
+  // joins the pool tasks of a job; false = some did not finish within the deadline (they stay in `fut`)
+  bool drain(JobCore& c) {
+    const auto dl = deadline_from_now();
+    for (auto& f : c.fut)
+      if (f.valid() && f.wait_until(dl) != std::future_status::ready) return false;
+    c.fut.clear();
+    return true;
+  }
+  void dump(const char* who, const char* why, JobCore& c) {
+    int np = 0;
+    for (auto& f : c.fut)
+      if (f.valid() && f.wait_for(std::chrono::seconds(0)) != std::future_status::ready) np++;
+    fprintf(stderr, "[zksaas] %s: %s: %s slot %d (%d proofs): pool tasks pending %d", who, why, kind(c), c.slot, nproofs(c), np);
+    if (!c.is_batch) fprintf(stderr, ", sorted_cnt %d", static_cast<ProveJob&>(c).sorted_cnt.load());
+    fprintf(stderr, ";");
+    for (int r = 0; r < NROLES; r++) {
+      fprintf(stderr, " %s:", ROLE_NAME[r]);
+      if (c.is_batch)
+        fprintf(stderr, " launched-flag %d, accumulate event %s,", static_cast<BatchJob&>(c).acc_flag[r].load(), ev_state(c.ev_role[r]));
+      fprintf(stderr, " chain event %s%s;", ev_state(job_slot(c, r).ev), job_slot(c, r).busy ? "" : " (idle)");
+    }
+    fprintf(stderr, "\n");
+  }
+  // joins a job's tasks and device work and marks it free (after an error, or zk_groth16_abort)
+  void abort(JobCore& c) {
+    // a proof's tasks waiting at the sort barrier go on (and fail or finish); a batch's gates are always raised (msm_task)
+    if (!c.is_batch) static_cast<ProveJob&>(c).sorted_cnt.fetch_add(1 << 20, std::memory_order_release);
+    bool ok = drain(c);
+    for (int r = 0; r < NROLES; r++) ok = ok && job_slot(c, r).wait(this) != hipErrorNotReady;
+    if (!ok) {
+      dump("abort", "work of the job is still pending after the deadline", c);
+      Status keep = last;
+      wedge(std::string("a ") + kind(c) + " could not be aborted within the deadline (wait_deadline_ms): its slot is not reused");
+      if (keep.code) last = keep;
+      return;                                                        // stays active: nothing of it is reused
+    }
+    c.active = false;
+  }
+  // A failure after the job was marked active leaves pool tasks and MSMs in flight that reference the caller's buffers:
+  // every such return aborts the job -- once -- and keeps the first error's message.
+  int bail(JobCore& c, int rc) {
+    Status keep = last;
+    abort(c);
+    last = keep;
+    return rc;
+  }
+  int drain_or_wedge(JobCore& c, const char* who) {
+    if (drain(c)) return ZK_OK;
+    dump(who, "pool tasks did not finish within the deadline", c);
+    return wedge(std::string(who) + ": host tasks of the " + kind(c) +
+                 " did not finish within the deadline (wait_deadline_ms); the slot is not reused");
+  }
+  // The end of every job: folds U (always waited for, whatever failed before: its launch references the job's buffers)
+  // into the proofs' terms, joins the pool tasks and frees the job -- unless a wait expired, which wedges the context.
+  // `who`: the ABI call that joins.  Afterwards terms(c, b).sums() are the proofs' totals.
+  int join(JobCore& c, const char* who) {
+    P1 ures[MSM_MAXB];
+    int rc = msm_fold_batch<Fq_>(this, c.msm[ROLE_U], ures, 1);
+    Status keep = last;
+    const bool expired = rc && job_slot(c, ROLE_U).busy;
+    if (expired) dump(who, "the U-MSM chain did not finish within the deadline", c);
+    if (int rd = drain_or_wedge(c, who)) return rd;
+    if (busy(c)) {                        // a chain's event did not signal within the deadline: nothing may be reused
+      if (!expired) dump(who, "an MSM chain did not finish within the deadline", c);
+      return wedge(expired ? keep.msg : std::string(last.msg));
+    }
+    c.active = false;
+    if (rc) return rc;
+    for (int e : c.rc)
+      if (e) return e;      // a pool task failed: its message was recorded on the engine by msm_launch (hip_fail); keep it
+    for (int b = 0; b < nproofs(c); b++) {
+      ProofTerms& t = terms(c, b);
+      if (t.err.code) return fail(t.err.code, t.err.msg);
+      t.U = ures[b];
+    }
+    return ZK_OK;
   }
   // engine-level failure recorded from a pool task (IEngine::fail is not thread-safe)
-  int task_fail(ProveJob& j, int code, const std::string& msg) {
-    std::lock_guard<std::mutex> lk(j.emu);
-    if (j.err.code == ZK_OK) {
-      j.err.code = code;
-      j.err.msg = msg;
+  int task_fail(ProofTerms& t, int code, const std::string& msg) {
+    std::lock_guard<std::mutex> lk(t.emu);
+    if (t.err.code == ZK_OK) {
+      t.err.code = code;
+      t.err.msg = msg;
     }
     return code;
   }
 
-  // Starts one proof (full = all n parties and the assembly; otherwise the five partial d_msm sums of parties
-  // [first, first + count) for the multi-GPU flow, where circom_h is driven by the caller and h arrives in finish).
-  // A failure after the job has been marked active leaves pool tasks and MSMs in flight that reference the caller's
-  // buffers: every such return goes through abort_job (the job is free again, the error message is kept).
-  int prove_begin(ProveJob& j, const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
-                  const void* a_share, const void* ax_share, const Fr& r, const Fr& s, int log_m,
-                  const zk_groth16_masks* mk, uint64_t seed, bool full, int first, int count, hipStream_t st,
-                  bool gate_sorts = false) {
-    if (j.active) return fail(ZK_ERR_BAD_INPUT, "a proof is already in flight on this slot");
-    int rc = prove_begin_impl(j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, full, first, count, st,
-                              gate_sorts);
-    if (rc && j.active) {
-      Status keep = last;
-      abort_job(j);
-      last = keep;
-    }
-    return rc;
-  }
-  void init_job(ProveJob& j, const zk_crs_share* crs, const zk_groth16_masks* mk, const Fr& r, const Fr& s, bool full,
-                int first, int count) {
+  void init_terms(ProofTerms& j, const zk_crs_share* crs, const zk_groth16_masks* mk, const Fr& r, const Fr& s, bool full,
+                  int first, int count) {
     j.crs = *crs;
     j.has_mk = mk != nullptr;
     j.mk = mk ? *mk : zk_groth16_masks{};
@@ -253,18 +360,86 @@
     j.first = first;
     j.count = count;
     j.err = Status{};
-    for (int& e : j.rc) e = 0;
     j.S = j.H = j.W = j.U = j.sS = j.rH = j.s_in0 = j.r_in1 = P1::identity();
     j.V0 = j.in2 = P2::identity();
     for (int k = 0; k < 5; k++) j.in1[k] = P1::identity();
     j.s_om0.assign(n, P1::identity());
     j.r_om1.assign(n, P1::identity());
   }
+  // One witness MSM of a job as a pool task: it enqueues the launch (a dozen kernel launches) on workspace slot
+  // ws0 + role, waits for the slot's event, folds the windows on the host and hands the points to then(res), res =
+  // [base vector][scalar vector].  Whatever waits on this launch is released also when it failed early (waiters must not
+  // hang): a batch raises `raise` (its accumulate-order flag of the role) in any case, a proof counts a failed launch into
+  // its sort barrier.  batch: the scalar vectors of a batched launch (copied), else `scal`.
+  template <class Fld, class Then>
+  void msm_task(JobCore& c, MsmRole role, const void* bases, const void* bases2, const void* scal, const MsmBatchArg* batch,
+                size_t npts, const Fr* coef, size_t plen, hipStream_t stream, const MsmGate& gate, std::atomic<int>* raise,
+                Then then) {
+    JobCore* C = &c;
+    const int dev = device;
+    const bool batched = batch != nullptr;
+    const MsmBatchArg ba = batched ? *batch : MsmBatchArg{};
+    c.fut.push_back(pool_->submit([=]() {
+      (void)hipSetDevice(dev);
+      MsmPending* pend = &C->msm[role];
+      int rc2 = msm_.template launch_t<Fld>(this, C->ws0 + role, bases, scal, npts, coef, plen, stream, pend, bases2, gate,
+                                            batched ? &ba : nullptr);
+      if (raise) raise->store(1, std::memory_order_release);
+      else if (rc2 && gate.sorted_cnt) gate.sorted_cnt->fetch_add(1, std::memory_order_release);
+      XYZZ<Fld> res[2 * MSM_MAXB];
+      if (!rc2) rc2 = msm_fold_batch<Fld>(this, *pend, res, bases2 ? 2 : 1);
+      C->rc[role] = rc2;
+      if (!rc2) then(res);
+    }));
+  }
+  // what the folded points of the witness MSMs are to the job's proofs
+  void take_V(JobCore& c, const P2* res) {
+    for (int b = 0; b < nproofs(c); b++) terms(c, b).V0 = res[b];
+  }
+  void take_W(JobCore& c, const P1* res) {
+    for (int b = 0; b < nproofs(c); b++) terms(c, b).W = res[b];
+  }
+  // S (and H, res[nb + b]) of every proof, then s*S and r*H off the tail of a full proof (prove.rs:229-235, linearity):
+  // the proofs of a batch are spread over the pool, this task takes proof 0
+  void take_SH(JobCore& c, const P1* res, bool with_h) {
+    const int nb = nproofs(c);
+    JobCore* C = &c;
+    auto fin = [=](int b) {
+      ProofTerms& t = terms(*C, b);
+      const bool h = with_h && !t.r_zero;
+      t.S = res[b];
+      if (h) t.H = res[nb + b];
+      if (!t.full) return;
+      t.sS = host_scalar_mul<FrP, Fq_>(t.S, t.s);
+      if (h) t.rH = host_scalar_mul<FrP, Fq_>(t.H, t.r);
+    };
+    std::vector<std::future<void>> sub;
+    for (int b = 1; b < nb; b++) sub.push_back(pool_->submit([=]() { fin(b); }));
+    fin(0);
+    // (the sub-tasks reference the caller's frame: the task runs queued work while it waits, HostPool::wait_helping -- a
+    // pool whose workers all sit here with their sub-tasks queued behind them cannot starve)
+    for (auto& f : sub)
+      while (!pool_->wait_helping(f, deadline_from_now())) {}
+  }
+
+  // Starts one proof (full = all n parties and the assembly; otherwise the five partial d_msm sums of parties
+  // [first, first + count) for the multi-GPU flow, where circom_h is driven by the caller and h arrives in finish).
+  // A failure after the job has been marked active has aborted the job when this returns (bail): callers only return.
+  int prove_begin(ProveJob& j, const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
+                  const void* a_share, const void* ax_share, const Fr& r, const Fr& s, int log_m,
+                  const zk_groth16_masks* mk, uint64_t seed, bool full, int first, int count, hipStream_t st,
+                  bool gate_sorts = false) {
+    if (j.active) return fail(ZK_ERR_BAD_INPUT, "a proof is already in flight on this slot");
+    j.sharded = false;
+    int rc = prove_begin_impl(j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, full, first, count, st,
+                              gate_sorts);
+    return rc && j.active ? bail(j, rc) : rc;
+  }
   // the gate of a proof's U-MSM: its sort is event 3 of the "all sorts first" barrier (prove_begin_impl)
   MsmGate u_gate(ProveJob& j) {
     MsmGate g{};
     if (j.gate_sorts) {
-      g.sorted_ev = ev_sorted_[j.slot][ROLE_U];
+      g.sorted_ev = j.ev_role[ROLE_U];
       g.sorted_cnt = &j.sorted_cnt;
     }
     return g;
@@ -282,10 +457,11 @@
       t_mark = now;
     };
     int rc = ensure_streams();
+    if (!rc) rc = ensure_events(j);
     if (rc) return rc;
-    init_job(j, crs, mk, r, s, full, first, count);
+    init_terms(j.pt, crs, mk, r, s, full, first, count);
+    for (int& e : j.rc) e = 0;
     const size_t Lc = ((size_t)1 << log_m) / l;
-    const int dev = device;
     // every internal stream is ordered after the work already queued on the caller's stream (the shares may still
     // be in flight there: found by tools/c5_bls381.py, where the a_share pack kernel of a 2^22 witness was still
     // running when the S/H/V MSMs started reading it)
@@ -293,14 +469,14 @@
     // instead of an event and six waits at the head of every chain of the proof)
     if (hipStreamQuery(st) != hipSuccess) {
       (void)hipGetLastError();                       // hipErrorNotReady is not an error here
-      ZK_HIP(hipEventRecord(ev_in_[j.slot], st));
-      for (hipStream_t is : streams_) ZK_HIP(hipStreamWaitEvent(is, ev_in_[j.slot], 0));
+      ZK_HIP(hipEventRecord(j.ev_in, st));
+      for (hipStream_t is : streams_) ZK_HIP(hipStreamWaitEvent(is, j.ev_in, 0));
     }
     j.active = true;
     ProveJob* J = &j;
     const size_t cstride = crs->len_a;
     // ---- device pipelines: the four MSMs over the witness shares do not depend on h.  Each is enqueued by a pool task
-    // (a launch is a dozen kernel launches), which then waits for the slot's event and folds the windows on the host.
+    // (msm_task), which then waits for the slot's event and folds the windows on the host.
     // V (G2) is the longest chain: issued first, on a high-priority stream, as ONE launch over all parties (two halves
     // on two streams paid a second bucket reduction: 257 vs 279 proofs/s, round 2).
     // Orders that were measured and dropped (rounds 2-4, DESIGN.md "What bounds one proof"): V's accumulate ahead of the
@@ -324,53 +500,37 @@
     j.sorted_cnt.store(0, std::memory_order_relaxed);
     if (gated) {
       gate.sorted_cnt = &j.sorted_cnt;
-      gate.wait_sorted = ev_sorted_[j.slot];
+      gate.wait_sorted = j.ev_role;
       gate.n_wait_sorted = gate.sorted_need = 4;
     }
+    auto role_gate = [&](MsmRole role) {
+      MsmGate g = gate;
+      if (g.n_wait_sorted) g.sorted_ev = J->ev_role[role];
+      return g;
+    };
     bool hu_done = false;
     if (full && gated) {
       hipError_t he = j.hshare.ensure((size_t)n * Lc * sizeof(Fr));
       if (he != hipSuccess) return hip_fail(he, "h share buffer");
       rc = circom_h_ws(qa, qb, qc, log_m, mk, seed, j.hshare.p, j.hwork, streams_[5]);
       if (rc) return rc;
-      rc = msm_.template launch_t<Fq_>(this, ws_job(j.slot, ROLE_U), crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
+      rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
                                       msm_.coef_d_, crs->len_u, streams_[5], &j.msm[ROLE_U], nullptr, u_gate(j));
       if (rc) return rc;
       hu_done = true;
     }
-    auto msm_task = [this, J, dev, gate](auto fld_tag, MsmRole role, const void* bases, const void* bases2,
-                                         const void* scal, size_t npts, const Fr* coef, size_t plen, hipStream_t stream,
-                                         auto* out1, auto* out2) {
-      using Fld = decltype(fld_tag);
-      J->fut.push_back(pool_->submit([=]() {
-        (void)hipSetDevice(dev);
-        MsmGate g = gate;
-        if (g.n_wait_sorted) g.sorted_ev = ev_sorted_[J->slot][role];
-        MsmPending* pend = &J->msm[role];
-        int rc2 = msm_.template launch_t<Fld>(this, ws_job(J->slot, role), bases, scal, npts, coef, plen, stream, pend,
-                                              bases2, g);
-        if (rc2 && g.sorted_cnt) g.sorted_cnt->fetch_add(1, std::memory_order_release);   // never leave the others spinning
-        if (!rc2) rc2 = msm_fold<Fld>(this, *pend, out1, out2);
-        J->rc[role] = rc2;
-        if constexpr (std::is_same<Fld, Fq_>::value) {
-          if (!rc2 && J->full && role == ROLE_SH) {   // s*S and r*H off the tail (prove.rs:229-235, linearity)
-            J->sS = host_scalar_mul<FrP, Fq_>(J->S, J->s);
-            if (out2 != nullptr && !J->r_zero) J->rH = host_scalar_mul<FrP, Fq_>(J->H, J->r);
-          }
-        }
-      }));
-    };
-    msm_task(Fq2_{}, ROLE_V, crs->v_d, nullptr, a_share, (size_t)count * cstride, cf, cstride, streams_[2], &j.V0,
-             (P2*)nullptr);
+    msm_task<Fq2_>(j, ROLE_V, crs->v_d, nullptr, a_share, nullptr, (size_t)count * cstride, cf, cstride, streams_[2],
+                   role_gate(ROLE_V), nullptr, [this, J](const P2* res) { take_V(*J, res); });
     // S and H multiply two base vectors by the same witness shares: ONE launch over both vectors, each with its own sort
     // (their identity bases differ: b_query is the identity for every wire no B-row mentions, 59 % in the SHA-256 circuit)
-    msm_task(Fq_{}, ROLE_SH, crs->s_d, j.r_zero ? nullptr : crs->h_d, a_share, (size_t)count * cstride, cf, cstride,
-             streams_[0], &j.S, j.r_zero ? (P1*)nullptr : &j.H);
-    msm_task(Fq_{}, ROLE_W, crs->w_d, nullptr, ax_share, (size_t)count * crs->len_w, cf, crs->len_w, streams_[3], &j.W,
-             (P1*)nullptr);
+    const void* hd = j.pt.r_zero ? nullptr : crs->h_d;
+    msm_task<Fq_>(j, ROLE_SH, crs->s_d, hd, a_share, nullptr, (size_t)count * cstride, cf, cstride, streams_[0],
+                  role_gate(ROLE_SH), nullptr, [this, J, hd](const P1* res) { take_SH(*J, res, hd != nullptr); });
+    msm_task<Fq_>(j, ROLE_W, crs->w_d, nullptr, ax_share, nullptr, (size_t)count * crs->len_w, cf, crs->len_w, streams_[3],
+                  role_gate(ROLE_W), nullptr, [this, J](const P1* res) { take_W(*J, res); });
     // (the host terms are two dozen pool submissions: behind circom_h's launches when those are still to come -- they
     // are the head of the proof's longest chain and the terms are not needed before prove_end)
-    if (!(full && !hu_done)) submit_host_terms(J, j.fut, full, first, count);
+    if (!(full && !hu_done)) submit_host_terms(&j.pt, j.fut);
     // ---- circom_h and the U-MSM that depends on it form a long dependent chain: high-priority internal stream.
     // At the SHA-256 size, holding the other MSM streams (or only their accumulate launches) back until circom_h has
     // finished was measured and rejected: 8.6-8.8 ms per proof against 6.9 ms when everything is issued at once.
@@ -382,10 +542,10 @@
       rc = circom_h_ws(qa, qb, qc, log_m, mk, seed, j.hshare.p, j.hwork, hs);
       if (rc) return rc;
       host_span(PROF_HOST_H);
-      rc = msm_.template launch_t<Fq_>(this, ws_job(j.slot, ROLE_U), crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
+      rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
                                       msm_.coef_d_, crs->len_u, hs, &j.msm[ROLE_U]);
       if (rc) return rc;
-      submit_host_terms(J, j.fut, full, first, count);
+      submit_host_terms(&j.pt, j.fut);
       host_span(PROF_HOST_U);
     }
     return ZK_OK;
@@ -393,7 +553,9 @@
 
   // Host-side terms of one proof that depend on nothing but its inputs (scalar multiples of CRS constants, in-mask sums,
   // per-party multiples of the out-masks): tasks of the worker pool, running beside the device work.
-  void submit_host_terms(ProveJob* J, std::vector<std::future<void>>& fut, bool full, int first, int count) {
+  void submit_host_terms(ProofTerms* J, std::vector<std::future<void>>& fut) {
+    const bool full = J->full;
+    const int first = J->first, count = J->count;
     if (full) {
       fut.push_back(pool_->submit([J]() {
         P1 d1 = aff1(J->crs.delta_g1);
@@ -408,7 +570,7 @@
       fut.push_back(pool_->submit([J]() { J->rsM = host_scalar_mul<FrP, Fq_>(aff1(J->crs.delta_g1), J->r * J->s); }));
       fut.push_back(pool_->submit([J]() { J->sK2 = host_scalar_mul<FrP, Fq2_>(aff2(J->crs.delta_g2), J->s); }));
     }
-    const zk_groth16_masks* mk = J->has_mk ? &J->mk : nullptr;
+    const zk_groth16_masks* mk = J->masks();
     if (mk) {
       // in-mask terms sum_p coef_p * mask_p (the king's unpack2 + sum over the masked points, dmsm/mod.rs:85-86)
       for (int k = 0; k < 5; k++) {
@@ -441,57 +603,24 @@
 
   // the U-MSM of a partial job (h comes from the caller's king rounds)
   int prove_launch_u(ProveJob& j, const void* h_share, hipStream_t st) {
-    return msm_.template launch_t<Fq_>(this, ws_job(j.slot, ROLE_U), j.crs.u_d, h_share, (size_t)j.count * j.crs.len_u,
-                                      msm_.coef_d_ + j.first, j.crs.len_u, st, &j.msm[ROLE_U], nullptr, u_gate(j));
-  }
-
-  // joins everything; sums[0..4] = S, H, V, W, U including the in-mask terms
-  int prove_join(ProveJob& j, P1* S, P1* H, P2* V, P1* W, P1* U) {
-    int rc = msm_fold<Fq_>(this, j.msm[ROLE_U], &j.U, nullptr);
-    if (!drain(j)) {
-      dump_job("prove_join: pool tasks did not finish within the deadline", j);
-      return wedge("host tasks of the proof did not finish within the deadline (wait_deadline_ms); the slot is not reused");
-    }
-    if (job_busy(j)) {
-      dump_job("prove_join: an MSM chain did not finish within the deadline", j);
-      Status keep = last;
-      return wedge(keep.msg);
-    }
-    j.active = false;
-    if (rc) return rc;
-    for (int e : j.rc)
-      if (e) return e;      // a pool task failed: its message was recorded on the engine by msm_launch (hip_fail); keep it
-    if (j.err.code) return fail(j.err.code, j.err.msg);
-    *S = xyzz_add_ni(j.S, j.in1[0]);
-    *H = j.r_zero ? P1::identity() : xyzz_add_ni(j.H, j.in1[1]);
-    *V = xyzz_add_ni(j.V0, j.in2);
-    *W = xyzz_add_ni(j.W, j.in1[3]);
-    *U = xyzz_add_ni(j.U, j.in1[4]);
-    return ZK_OK;
+    const ProofTerms& t = j.pt;
+    return msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, t.crs.u_d, h_share, (size_t)t.count * t.crs.len_u,
+                                      msm_.coef_d_ + t.first, t.crs.len_u, st, &j.msm[ROLE_U], nullptr, u_gate(j));
   }
 
   // The end of one proof.  The U chain (circom_h, then its MSM) ends last by a margin: everything that does not depend on U
   // -- the join of the pool tasks, A and B of every party, C without its U term -- is done while it still runs; after U's
-  // event only its fold and one addition per party are left.  (U is always waited for, whatever failed before: its launch
-  // references the job's buffers.)
+  // event only its fold (join) and one addition per party are left.
   int prove_end(ProveJob& j, void* pi_a, void* pi_b, void* pi_c) {
+    const char* who = "zk_groth16_wait";
     const auto t0 = std::chrono::steady_clock::now();
-    if (!drain(j)) {
-      dump_job("zk_groth16_wait: pool tasks did not finish within the deadline", j);
-      return wedge("zk_groth16_wait: host tasks of the proof did not finish within the deadline (wait_deadline_ms); the slot is not reused");
-    }
-    bool early_ok = !j.err.code;
+    int rc = drain_or_wedge(j, who);
+    if (rc) return rc;
+    bool early_ok = !j.pt.err.code;
     for (int e : j.rc) early_ok = early_ok && !e;
     std::vector<P1> c_part(early_ok ? n : 0);
-    if (early_ok) {
-      const P1 S = xyzz_add_ni(j.S, j.in1[0]), H = j.r_zero ? P1::identity() : xyzz_add_ni(j.H, j.in1[1]),
-               W = xyzz_add_ni(j.W, j.in1[3]);
-      const P2 V = xyzz_add_ni(j.V0, j.in2);
-      int rc = assemble_job(j, S, H, V, W, j.in1[4], pi_a, pi_b, pi_c, c_part.data());
-      if (rc) early_ok = false;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    if (prof.on && job_slot(j, ROLE_U).busy) (void)event_wait(job_slot(j, ROLE_U).ev);   // (msm_fold waits again: returns at once)
+    if (early_ok) assemble_job(j.pt, j.pt.sums(), pi_a, pi_b, pi_c, c_part.data());    // (U is still the identity there)
+    if (prof.on && job_slot(j, ROLE_U).busy) (void)event_wait(job_slot(j, ROLE_U).ev);   // (the join waits again: returns at once)
     const auto t2 = std::chrono::steady_clock::now();
     struct HostSpans {                                                          // host:prove_wait / host:prove_tail
       Profiler& pr;
@@ -502,41 +631,27 @@
         pr.host_add(PROF_HOST_TAIL, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b).count());
       }
     } spans{prof, t0, t2};
-    (void)t1;
-    int rc = msm_fold<Fq_>(this, j.msm[ROLE_U], &j.U, nullptr);
-    if (job_busy(j)) {                     // a chain's event did not signal within the deadline: nothing may be reused
-      dump_job("zk_groth16_wait: an MSM chain did not finish within the deadline", j);
-      Status keep = last;
-      return wedge(keep.msg);
-    }
-    j.active = false;
+    rc = join(j, who);              // (a failed task or term, the reason for !early_ok, is returned here)
     if (rc) return rc;
-    for (int e : j.rc)
-      if (e) return e;                  // a pool task failed: its message was recorded on the engine by msm_launch; keep it
-    if (j.err.code) return fail(j.err.code, j.err.msg);
-    if (!early_ok) return fail(ZK_ERR_GENERIC, "proof assembly failed");
     Jacobian<Fq_>* oc = (Jacobian<Fq_>*)pi_c;
-    for (int p = 0; p < n; p++) oc[p] = xyzz_to_jacobian(xyzz_add_ni(c_part[p], j.U));
+    for (int p = 0; p < n; p++) oc[p] = xyzz_to_jacobian(xyzz_add_ni(c_part[p], j.pt.U));
     return ZK_OK;
   }
   // the n parties' (A, B, C) shares of one proof from its five MSM totals (in-mask terms included) and the host terms
   // (c_part != nullptr: the C shares stay in extended form there instead of pi_c -- prove_end adds a late term to them)
-  int assemble_job(ProveJob& j, const P1& S, const P1& H, const P2& V, const P1& W, const P1& U, void* pi_a, void* pi_b,
-                   void* pi_c, P1* c_part = nullptr) {
-    const zk_groth16_masks* mk = j.has_mk ? &j.mk : nullptr;
+  void assemble_job(const ProofTerms& j, const MsmSums& t, void* pi_a, void* pi_b, void* pi_c, P1* c_part = nullptr) {
+    const zk_groth16_masks* mk = j.masks();
     // prove.rs:40-56 / 99-110 / 148-158 / 229-235 for every party; C = s*A + r*B1 - rs*delta + W + U by linearity:
-    //   s*A_p = s*(a0 + r*delta + alpha) + s*S + s*in0 + s*om0_p     (every term was computed beside the device work)
+    //   s*A_p = s*(a0 + r*delta + alpha) + s*S + s*in0 + s*om0_p     (every term was computed beside the device work;
+    //   r*B1_p likewise, so the total H itself is not needed)
     P1 cA = xyzz_add_ni(xyzz_add_ni(aff1(j.crs.a_query0), j.rN), aff1(j.crs.alpha_g1));
-    P1 cB1 = xyzz_add_ni(xyzz_add_ni(aff1(j.crs.b_g1_query0), j.sK), aff1(j.crs.beta_g1));
     P2 cB2 = xyzz_add_ni(xyzz_add_ni(aff2(j.crs.b_g2_query0), j.sK2), aff2(j.crs.beta_g2));
-    P1 A0 = xyzz_add_ni(cA, S);
-    P2 B0 = xyzz_add_ni(cB2, V);
+    P1 A0 = xyzz_add_ni(cA, t.S);
+    P2 B0 = xyzz_add_ni(cB2, t.V);
     P1 C0 = xyzz_add_ni(xyzz_add_ni(j.s_cA, j.sS), j.s_in0);
     if (!j.r_zero) C0 = xyzz_add_ni(C0, xyzz_add_ni(xyzz_add_ni(j.r_cB1, j.rH), j.r_in1));
     C0 = xyzz_add_ni(C0, j.rsM.neg());
-    C0 = xyzz_add_ni(C0, xyzz_add_ni(W, U));
-    (void)cB1;
-    (void)H;
+    C0 = xyzz_add_ni(C0, xyzz_add_ni(t.W, t.U));
     Jacobian<Fq_>* oa = (Jacobian<Fq_>*)pi_a;
     Jacobian<Fq2_>* ob = (Jacobian<Fq2_>*)pi_b;
     Jacobian<Fq_>* oc = (Jacobian<Fq_>*)pi_c;
@@ -568,7 +683,6 @@
       if (c_part) c_part[p] = C;
       else oc[p] = xyzz_to_jacobian(C);
     }
-    return ZK_OK;
   }
 
   int check_prove_args(const zk_crs_share* crs, const void* r_, const void* s_, int log_m) {
@@ -600,53 +714,27 @@
     int rc = check_prove_args(crs, r_, s_, log_m);
     if (rc) return rc;
     if (!qa || !qb || !qc || !a_share || !ax_share || !handle) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    int slot = -1;
-    for (int i = 0; i < NJOBS; i++)
-      if (!jobs_[i].active && !djobs_[i].active) {       // (a sharded proof owns its slot until it is joined or aborted)
-        slot = i;
-        break;
-      }
-    if (slot < 0) return fail(ZK_ERR_BAD_INPUT, "too many proofs in flight (zk_groth16_wait one first)");
-    ProveJob& j = jobs_[slot];
-    j.slot = slot;
+    ProveJob* j = free_job(jobs_);
+    if (!j) return fail(ZK_ERR_BAD_INPUT, "too many proofs in flight (zk_groth16_wait one first)");
     Fr r = Fr::from_limbs((const uint32_t*)r_), s = Fr::from_limbs((const uint32_t*)s_);
-    rc = prove_begin(j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, true, 0, n, st);
-    if (rc) {
-      Status keep = last;
-      abort_job(j);
-      last = keep;
-      return rc;
-    }
-    *handle = slot;
+    rc = prove_begin(*j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, true, 0, n, st);
+    if (rc) return rc;
+    *handle = j->slot;
     return ZK_OK;
   }
   int groth16_wait(int handle, void* pi_a, void* pi_b, void* pi_c) override {
     if (handle < 0 || handle >= NJOBS || !jobs_[handle].active) return fail(ZK_ERR_BAD_INPUT, "no proof in flight on this handle");
-    if (djobs_[handle].active) return fail(ZK_ERR_BAD_INPUT, "a sharded proof is in flight on this handle: zk_dist_groth16_wait joins it");
+    if (jobs_[handle].sharded) return fail(ZK_ERR_BAD_INPUT, "a sharded proof is in flight on this handle: zk_dist_groth16_wait joins it");
     if (!pi_a || !pi_b || !pi_c) return fail(ZK_ERR_BAD_INPUT, "null pointer");
     return prove_end(jobs_[handle], pi_a, pi_b, pi_c);
-  }
-  // joins a job's tasks and device work and marks it free (after an error, or zk_groth16_abort)
-  void abort_job(ProveJob& j) {
-    j.sorted_cnt.fetch_add(1 << 20, std::memory_order_release);      // tasks waiting at the sort barrier go on (and fail or finish)
-    bool ok = drain(j);
-    for (int r = 0; r < NROLES; r++) ok = ok && job_slot(j, r).wait(this) != hipErrorNotReady;
-    if (!ok) {
-      dump_job("abort: work of the proof is still pending after the deadline", j);
-      Status keep = last;
-      wedge("a proof could not be aborted within the deadline (wait_deadline_ms): its slot is not reused");
-      if (keep.code) last = keep;
-      return;                                                        // stays active: nothing of it is reused
-    }
-    j.active = false;
   }
   // also the abort of a sharded proof in flight (zk_dist_groth16_prove_async hands out handles of the same space): the
   // slot is free for either kind afterwards.  The channels' round counters are NOT rewound -- every rank must abort the
   // same proof, as every rank must issue the same sequence of collective calls.
   int groth16_abort(int handle) override {
     if (handle < 0 || handle >= NJOBS) return fail(ZK_ERR_BAD_INPUT, "bad handle");
-    abort_job(jobs_[handle]);
-    djobs_[handle].active = false;
+    abort(jobs_[handle]);
+    jobs_[handle].sharded = false;
     return ZK_OK;
   }
 
@@ -659,56 +747,6 @@
   // vector (msm.hpp MsmScalars: bucket sets indexed by (proof, window)), circom_h is one launch chain over 3 nb
   // vectors.  Host terms (scalar multiples of masks and CRS constants) are per proof, on the worker pool as before.
   static constexpr int MAX_PROOF_BATCH = MSM_MAXB;
-  struct BatchJob {
-    bool active = false;
-    int nb = 0;
-    std::vector<std::unique_ptr<ProveJob>> pj;      // per proof: host terms and the five MSM totals
-    MsmPending msm[NROLES];                         // by MsmRole; workspace slots ws_batch(slot, role)
-    DevBuf hwork, hshare;
-    std::vector<std::future<void>> fut;
-    int rc[ROLE_U] = {};                            // results of the S+H, W and V tasks (U is folded by batch_join)
-  };
-  // Two batches may be in flight (zk_groth16_prove_batch_async): each has its own MSM workspaces, scratch and stream
-  // set, so that the sort phase of one batch runs under the accumulate kernels of the other and the reduction tails of one
-  // under the other's accumulates -- one batch alone leaves the chip partly idle for ~1 ms at either end.
-  struct BatchJobX : BatchJob {
-    zk_crs_share crs{};
-    int slot = 0;
-    hipEvent_t ev_in = nullptr;
-    bool own_streams = false, full = true;
-    int first = 0, count = 0;
-    MsmGate gate_u;
-    hipEvent_t ev_acc[NROLES] = {};                 // by role: recorded behind the accumulate kernel
-    std::atomic<int> acc_flag[NROLES];              // ... once that record has been enqueued (MsmGate)
-    hipStream_t st[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  };
-  BatchJobX bjobs_[NBATCH];
-
-  MsmSlot& batch_slot(const BatchJobX& B, int role) { return msm_.slots_[ws_batch(B.slot, role)]; }
-  bool batch_busy(const BatchJobX& B) {
-    for (int r = 0; r < NROLES; r++)
-      if (batch_slot(B, r).busy) return true;
-    return false;
-  }
-  void dump_batch(const char* why, BatchJobX& B) {
-    fprintf(stderr, "[zksaas] %s: batch slot %d (%d proofs): pool tasks pending %d;", why, B.slot, B.nb, futs_pending(B.fut));
-    for (int r = 0; r < NROLES; r++)
-      fprintf(stderr, " %s: launched-flag %d, accumulate event %s, chain event %s%s;", ROLE_NAME[r], B.acc_flag[r].load(),
-              ev_state(B.ev_acc[r]), ev_state(batch_slot(B, r).ev), batch_slot(B, r).busy ? "" : " (idle)");
-    fprintf(stderr, "\n");
-  }
-  void abort_batch(BatchJobX& B) {
-    bool ok = drain_futs(B.fut);
-    for (int r = 0; r < NROLES; r++) ok = ok && batch_slot(B, r).wait(this) != hipErrorNotReady;
-    if (!ok) {
-      dump_batch("abort: work of the batch is still pending after the deadline", B);
-      Status keep = last;
-      wedge("a batch could not be aborted within the deadline (wait_deadline_ms): its slot is not reused");
-      if (keep.code) last = keep;
-      return;
-    }
-    B.active = false;
-  }
 
   int groth16_prove_batch(const zk_crs_share* crs, int nb, const void* const* qa, const void* const* qb,
                           const void* const* qc, const void* const* a_share, const void* const* ax_share, const void* r_,
@@ -728,101 +766,75 @@
     if (nb >= 1 && nb <= MAX_PROOF_BATCH)
       for (int b = 0; b < nb; b++)
         if (!qa[b] || !qb[b] || !qc[b]) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    int slot = -1;
-    int rc = batch_begin(crs_in, nb, a_share, ax_share, r_, s_, log_m, mk, true, 0, n, st, &slot);
+    BatchJob* B = nullptr;
+    int rc = batch_begin(crs_in, nb, a_share, ax_share, r_, s_, log_m, mk, true, 0, n, st, &B);
     if (rc) return rc;
-    BatchJobX& B = bjobs_[slot];
     // ---- circom_h of the whole batch and the U-MSM behind it
     const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    rc = circom_h_batch(nb, qa, qb, qc, log_m, mk, seed, (Fr*)B.hshare.p, B.hwork, B.st[5]);
-    if (!rc) rc = batch_launch_u(B, (const Fr*)B.hshare.p, per, B.st[5]);
-    if (rc) {
-      Status keep = last;
-      abort_batch(B);
-      last = keep;
-      return rc;
-    }
-    *handle = slot;
+    rc = circom_h_batch(nb, qa, qb, qc, log_m, mk, seed, (Fr*)B->hshare.p, B->hwork, B->st[5]);
+    if (!rc) rc = batch_launch_u(*B, (const Fr*)B->hshare.p, per, B->st[5]);
+    if (rc) return bail(*B, rc);
+    *handle = B->slot;
     return ZK_OK;
   }
   // the U-MSM of a batch: h_all = [nb][count * m/l] (proof b at h_all + b * stride)
-  int batch_launch_u(BatchJobX& B, const Fr* h_all, size_t stride, hipStream_t st) {
+  int batch_launch_u(BatchJob& B, const Fr* h_all, size_t stride, hipStream_t st) {
+    const ProofTerms& t = B.pt[0];                   // (CRS and party range are the batch's)
     MsmBatchArg ba_h;
     ba_h.nb = B.nb;
     for (int b = 0; b < B.nb; b++) ba_h.p[b] = h_all + (size_t)b * stride;
-    int rc = msm_.template launch_t<Fq_>(this, ws_batch(B.slot, ROLE_U), B.crs.u_d, nullptr, (size_t)B.count * B.crs.len_u,
-                                        msm_.coef_d_ + B.first, B.crs.len_u, st, &B.msm[ROLE_U], nullptr, B.gate_u, &ba_h);
+    int rc = msm_.template launch_t<Fq_>(this, B.ws0 + ROLE_U, t.crs.u_d, nullptr, (size_t)t.count * t.crs.len_u,
+                                        msm_.coef_d_ + t.first, t.crs.len_u, st, &B.msm[ROLE_U], nullptr, B.gate_u, &ba_h);
     B.acc_flag[ROLE_U].store(1, std::memory_order_release);
     return rc;
   }
   // Starts a batch: the four witness MSMs of parties [first, first + count) for nb proofs (one launch chain each) and
   // the proofs' host terms.  full: all n parties, assembly included; otherwise the partial sums of one rank (the in-mask
-  // terms only).  The caller enqueues circom_h and batch_launch_u, then batch_join.
-  int batch_begin(const zk_crs_share* crs_in, int nb, const void* const* a_share, const void* const* ax_share,
+  // terms only).  The caller enqueues circom_h and batch_launch_u, then joins.
+  int batch_begin(const zk_crs_share* crs, int nb, const void* const* a_share, const void* const* ax_share,
                   const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk, bool full, int first, int count,
-                  hipStream_t st, int* slot_out) {
+                  hipStream_t st, BatchJob** job_out) {
     if (!Cfg::HAS_G2) return fail(ZK_ERR_BAD_INPUT, "G2 is not available for this curve");
-    int rc = check_prove_args(crs_in, r_, s_, log_m);
+    int rc = check_prove_args(crs, r_, s_, log_m);
     if (rc) return rc;
     if (nb < 1 || nb > MAX_PROOF_BATCH || 3 * nb > KING_BATCH || nb > DEGRED_BATCH)
       return fail(ZK_ERR_BAD_INPUT, "batch size must be in 1.." + std::to_string(MAX_PROOF_BATCH));
     if (!a_share || !ax_share) return fail(ZK_ERR_BAD_INPUT, "null pointer");
     for (int b = 0; b < nb; b++)
       if (!a_share[b] || !ax_share[b]) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    int slot = -1;
-    for (int i = 0; i < NBATCH; i++)
-      if (!bjobs_[i].active) {
-        slot = i;
-        break;
-      }
-    if (slot < 0) return fail(ZK_ERR_BAD_INPUT, "too many batches in flight (zk_groth16_batch_wait one first)");
-    BatchJobX& B = bjobs_[slot];
-    B.slot = slot;
+    BatchJob* Bp = free_job(bjobs_);
+    if (!Bp) return fail(ZK_ERR_BAD_INPUT, "too many batches in flight (zk_groth16_batch_wait one first)");
+    BatchJob& B = *Bp;
     rc = ensure_streams();
+    if (!rc) rc = ensure_events(B);
     if (rc) return rc;
-    {
-      // every handle is checked on its own: a failure half-way leaves the rest to be created by the next call
-      if (!B.ev_in) ZK_HIP(hipEventCreateWithFlags(&B.ev_in, hipEventDisableTiming));
-      for (hipEvent_t& e : B.ev_acc)
-        if (!e) ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      // (splitting the chip between the G2 MSM and the rest with CU masks was measured in round 3 and dropped: DESIGN.md
-      // "batched proving")
-      B.own_streams = slot != 0;
-      for (int i = 0; i < 6; i++) {
-        if (B.st[i]) continue;
-        if (!B.own_streams) {
-          B.st[i] = streams_[i];                     // batch slot 0 shares the single-proof stream set
-        } else {
-          int pr = 0;
-          ZK_HIP(hipStreamGetPriority(streams_[i], &pr));
-          ZK_HIP(hipStreamCreateWithPriority(&B.st[i], hipStreamNonBlocking, pr));
-        }
+    // (splitting the chip between the G2 MSM and the rest with CU masks was measured in round 3 and dropped: DESIGN.md
+    // "batched proving")
+    B.own_streams = B.slot != 0;
+    for (int i = 0; i < 6; i++) {
+      if (B.st[i]) continue;
+      if (!B.own_streams) {
+        B.st[i] = streams_[i];                       // batch slot 0 shares the single-proof stream set
+      } else {
+        int pr = 0;
+        ZK_HIP(hipStreamGetPriority(streams_[i], &pr));
+        ZK_HIP(hipStreamCreateWithPriority(&B.st[i], hipStreamNonBlocking, pr));
       }
     }
-    B.crs = *crs_in;
-    const zk_crs_share* crs = &B.crs;
-    hipStream_t* const streams_ = B.st;              // this batch's stream set
-    hipEvent_t const ev_batch_in_ = B.ev_in;
     const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)count * Lc;
     ZK_HIP(B.hshare.ensure(per * nb * sizeof(Fr)));
     B.nb = nb;
-    B.first = first;
-    B.count = count;
-    B.full = full;
-    const int n = count;                                 // parties of this launch (shadows the context's n below)
-    while ((int)B.pj.size() < nb) B.pj.emplace_back(new ProveJob());
+    while ((int)B.pt.size() < nb) B.pt.emplace_back();
     bool all_r_zero = true;
     for (int b = 0; b < nb; b++) {
       Fr r = Fr::from_limbs((const uint32_t*)r_ + (size_t)b * FrP::N), s = Fr::from_limbs((const uint32_t*)s_ + (size_t)b * FrP::N);
-      init_job(*B.pj[b], crs, mk ? &mk[b] : nullptr, r, s, full, first, count);
+      init_terms(B.pt[b], crs, mk ? &mk[b] : nullptr, r, s, full, first, count);
       all_r_zero = all_r_zero && r.is_zero();
     }
     for (int& e : B.rc) e = 0;
-    ZK_HIP(hipEventRecord(ev_batch_in_, st));
-    for (int i = 0; i < 6; i++) ZK_HIP(hipStreamWaitEvent(streams_[i], ev_batch_in_, 0));
+    ZK_HIP(hipEventRecord(B.ev_in, st));
+    for (int i = 0; i < 6; i++) ZK_HIP(hipStreamWaitEvent(B.st[i], B.ev_in, 0));
     B.active = true;
-    BatchJob* BJ = &B;
-    const int dev = device;
     const Fr* cf = msm_.coef_d_ + first;
     MsmBatchArg ba_a, ba_x;
     ba_a.nb = ba_x.nb = nb;
@@ -848,132 +860,41 @@
           if (ROLE_NAME[r][0] == ch) id = r;
         if (id < 0 || gates[id].signal_ev) continue;
         B.acc_flag[id].store(0, std::memory_order_relaxed);
-        gates[id].signal_ev = B.ev_acc[id];
+        gates[id].signal_ev = B.ev_role[id];
         gates[id].signal_flag = &B.acc_flag[id];
         if (prev >= 0) {
-          gates[id].wait_ev = B.ev_acc[prev];
+          gates[id].wait_ev = B.ev_role[prev];
           gates[id].wait_flag = &B.acc_flag[prev];
         }
         prev = id;
       }
     }
-    std::atomic<int>* aflag = B.acc_flag;
     // ---- the witness MSMs: V (G2) first on its high-priority stream, S + H as one launch over both base vectors, W
-    B.fut.push_back(pool_->submit([=]() {
-      (void)hipSetDevice(dev);
-      int rc2 = msm_.template launch_t<Fq2_>(this, ws_batch(slot, ROLE_V), crs->v_d, nullptr, (size_t)n * crs->len_a, cf,
-                                            crs->len_a, streams_[2], &BJ->msm[ROLE_V], nullptr, gates[ROLE_V], &ba_a);
-      aflag[ROLE_V].store(1, std::memory_order_release);   // also when the launch failed early (waiters must not hang)
-      std::vector<P2> res((size_t)nb);
-      if (!rc2) rc2 = msm_fold_batch<Fq2_>(this, BJ->msm[ROLE_V], res.data(), 1);
-      BJ->rc[ROLE_V] = rc2;
-      if (!rc2)
-        for (int b = 0; b < nb; b++) BJ->pj[b]->V0 = res[b];
-    }));
+    msm_task<Fq2_>(B, ROLE_V, crs->v_d, nullptr, nullptr, &ba_a, (size_t)count * crs->len_a, cf, crs->len_a, B.st[2],
+                   gates[ROLE_V], &B.acc_flag[ROLE_V], [this, Bp](const P2* res) { take_V(*Bp, res); });
     const void* hd = all_r_zero ? nullptr : crs->h_d;
-    B.fut.push_back(pool_->submit([=]() {
-      (void)hipSetDevice(dev);
-      int rc2 = msm_.template launch_t<Fq_>(this, ws_batch(slot, ROLE_SH), crs->s_d, nullptr, (size_t)n * crs->len_a, cf,
-                                           crs->len_a, streams_[0], &BJ->msm[ROLE_SH], hd, gates[ROLE_SH], &ba_a);
-      aflag[ROLE_SH].store(1, std::memory_order_release);
-      std::vector<P1> res((size_t)nb * 2);
-      if (!rc2) rc2 = msm_fold_batch<Fq_>(this, BJ->msm[ROLE_SH], res.data(), hd ? 2 : 1);
-      BJ->rc[ROLE_SH] = rc2;
-      if (rc2) return;
-      // s*S and r*H per proof (prove.rs:229-235, linearity): spread over the pool, this task takes proof 0
-      std::vector<std::future<void>> sub;
-      auto fin = [=, &res](int b) {
-        ProveJob* J = BJ->pj[b].get();
-        J->S = res[b];
-        J->sS = host_scalar_mul<FrP, Fq_>(J->S, J->s);
-        if (hd && !J->r_zero) {
-          J->H = res[(size_t)nb + b];
-          J->rH = host_scalar_mul<FrP, Fq_>(J->H, J->r);
-        }
-      };
-      for (int b = 1; b < nb; b++) sub.push_back(pool_->submit([=]() { fin(b); }));
-      fin(0);
-      // (the sub-tasks reference this frame: the task runs queued work while it waits, HostPool::wait_helping -- a pool
-      // whose workers all sit here with their sub-tasks queued behind them cannot starve)
-      for (auto& f : sub)
-        while (!pool_->wait_helping(f, deadline_from_now())) {}
-    }));
-    B.fut.push_back(pool_->submit([=]() {
-      (void)hipSetDevice(dev);
-      int rc2 = msm_.template launch_t<Fq_>(this, ws_batch(slot, ROLE_W), crs->w_d, nullptr, (size_t)n * crs->len_w, cf,
-                                           crs->len_w, streams_[3], &BJ->msm[ROLE_W], nullptr, gates[ROLE_W], &ba_x);
-      aflag[ROLE_W].store(1, std::memory_order_release);
-      std::vector<P1> res((size_t)nb);
-      if (!rc2) rc2 = msm_fold_batch<Fq_>(this, BJ->msm[ROLE_W], res.data(), 1);
-      BJ->rc[ROLE_W] = rc2;
-      if (!rc2)
-        for (int b = 0; b < nb; b++) BJ->pj[b]->W = res[b];
-    }));
+    msm_task<Fq_>(B, ROLE_SH, crs->s_d, hd, nullptr, &ba_a, (size_t)count * crs->len_a, cf, crs->len_a, B.st[0],
+                  gates[ROLE_SH], &B.acc_flag[ROLE_SH], [this, Bp, hd](const P1* res) { take_SH(*Bp, res, hd != nullptr); });
+    msm_task<Fq_>(B, ROLE_W, crs->w_d, nullptr, nullptr, &ba_x, (size_t)count * crs->len_w, cf, crs->len_w, B.st[3],
+                  gates[ROLE_W], &B.acc_flag[ROLE_W], [this, Bp](const P1* res) { take_W(*Bp, res); });
     // ---- host terms of every proof
-    for (int b = 0; b < nb; b++) submit_host_terms(B.pj[b].get(), B.fut, full, first, count);
+    for (int b = 0; b < nb; b++) submit_host_terms(&B.pt[b], B.fut);
     B.gate_u = gates[ROLE_U];
-    *slot_out = slot;
-    return ZK_OK;
-  }
-  // the five MSM totals of every proof of the batch, in-mask terms included (sums[b] = S, H, V, W, U)
-  struct BatchSums {
-    P1 S, H, W, U;
-    P2 V;
-  };
-  int batch_join(BatchJobX& B, std::vector<BatchSums>& sums) {
-    const int nb = B.nb;
-    std::vector<P1> ures((size_t)nb);
-    int rc = msm_fold_batch<Fq_>(this, B.msm[ROLE_U], ures.data(), 1);
-    if (rc) {
-      if (batch_slot(B, ROLE_U).busy) dump_batch("zk_groth16_batch_wait: the U-MSM chain did not finish within the deadline", B);
-      Status keep = last;
-      abort_batch(B);
-      last = keep;
-      return rc;
-    }
-    if (!drain_futs(B.fut)) {
-      dump_batch("zk_groth16_batch_wait: pool tasks did not finish within the deadline", B);
-      return wedge("zk_groth16_batch_wait: host tasks of the batch did not finish within the deadline (wait_deadline_ms); the slot is not reused");
-    }
-    if (batch_busy(B)) {
-      dump_batch("zk_groth16_batch_wait: an MSM chain did not finish within the deadline", B);
-      Status keep = last;
-      return wedge(keep.msg);
-    }
-    B.active = false;
-    for (int e : B.rc)
-      if (e) return e;
-    sums.resize((size_t)nb);
-    for (int b = 0; b < nb; b++) {
-      ProveJob& j = *B.pj[b];
-      if (j.err.code) return fail(j.err.code, j.err.msg);
-      sums[b].S = xyzz_add_ni(j.S, j.in1[0]);
-      sums[b].H = j.r_zero ? P1::identity() : xyzz_add_ni(j.H, j.in1[1]);
-      sums[b].V = xyzz_add_ni(j.V0, j.in2);
-      sums[b].W = xyzz_add_ni(j.W, j.in1[3]);
-      sums[b].U = xyzz_add_ni(ures[b], j.in1[4]);
-    }
+    *job_out = Bp;
     return ZK_OK;
   }
   int groth16_batch_wait(int handle, void* pi_a, void* pi_b, void* pi_c) override {
     if (handle < 0 || handle >= NBATCH || !bjobs_[handle].active) return fail(ZK_ERR_BAD_INPUT, "no batch in flight on this handle");
-    BatchJobX& B = bjobs_[handle];
+    BatchJob& B = bjobs_[handle];
     if (!pi_a || !pi_b || !pi_c) {
-      abort_batch(B);
+      abort(B);
       return fail(ZK_ERR_BAD_INPUT, "null pointer");
     }
-    const int nb = B.nb;
-    std::vector<BatchSums> sums;
-    int rc = batch_join(B, sums);
+    int rc = join(B, "zk_groth16_batch_wait");
     if (rc) return rc;
-    for (int b = 0; b < nb; b++) {
-      ProveJob& j = *B.pj[b];
-      const P1 &S = sums[b].S, &H = sums[b].H, &W = sums[b].W, &U = sums[b].U;
-      const P2& V = sums[b].V;
-      rc = assemble_job(j, S, H, V, W, U, (char*)pi_a + (size_t)b * n * sizeof(Jacobian<Fq_>),
-                        (char*)pi_b + (size_t)b * n * sizeof(Jacobian<Fq2_>), (char*)pi_c + (size_t)b * n * sizeof(Jacobian<Fq_>));
-      if (rc) return rc;
-    }
+    for (int b = 0; b < B.nb; b++)
+      assemble_job(B.pt[b], B.pt[b].sums(), (char*)pi_a + (size_t)b * n * sizeof(Jacobian<Fq_>),
+                   (char*)pi_b + (size_t)b * n * sizeof(Jacobian<Fq2_>), (char*)pi_c + (size_t)b * n * sizeof(Jacobian<Fq_>));
     return ZK_OK;
   }
 

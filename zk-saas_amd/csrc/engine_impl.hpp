@@ -4,6 +4,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <deque>
 #include <memory>
 
 #include "engine.hpp"
@@ -49,20 +50,17 @@ class Engine : public IEngine {
     t = l_;
     n = 4 * l_;
     device = device_;
+    for (int i = 0; i < NJOBS; i++) jobs_[i].slot = i, jobs_[i].ws0 = ws_job(i, 0);
+    for (int i = 0; i < NBATCH; i++) bjobs_[i].slot = i, bjobs_[i].ws0 = ws_batch(i, 0);
   }
   ~Engine() override {
     for (auto& j : jobs_)
-      if (j.active) abort_job(j);
-    for (auto& b : bjobs_) {
-      if (b.active) abort_batch(b);
-      if (b.ev_in) (void)hipEventDestroy(b.ev_in);
-      for (hipEvent_t e_ : b.ev_acc)
-        if (e_) (void)hipEventDestroy(e_);
-      if (b.own_streams)
-        for (hipStream_t s_ : b.st)
-          if (s_) (void)hipStreamDestroy(s_);
-    }
+      if (j.active) abort(j);
+    for (auto& b : bjobs_)
+      if (b.active) abort(b);
     pool_.reset();                                   // joins the host workers before anything they use goes away
+    for (hipStream_t s_ : streams_)                  // (the jobs destroy their own events and streams: ~JobCore, ~BatchJob)
+      if (s_) (void)hipStreamDestroy(s_);
     TableRegistry::inst().forget_owner(this);
     for (auto& kv : gentabs_) (void)hipFree(kv.second);
     for (auto& kv : gtabs_) {
@@ -372,6 +370,12 @@ class Engine : public IEngine {
   using Fq2_ = Fp2<typename Cfg::FqP>;
   using P1 = XYZZ<Fq_>;
   using P2 = XYZZ<Fq2_>;
+  // the five MSM totals of one proof, in-mask terms included; crosses the net as bytes (engine_dist.inc.hpp sum_over_ranks)
+  struct MsmSums {
+    P1 S, H, W, U;
+    P2 V;
+  };
+  static_assert(std::is_trivially_copyable<MsmSums>::value && sizeof(MsmSums) <= NET_PAYLOAD, "payload");
   // ---- the class body continues in four fragments, by primitive (round 5) ----
 #include "engine_fft.inc.hpp"        // PSS, fft1, king of d_fft, deg_red, d_pp
 #include "engine_points.inc.hpp"     // MSM entry points, group-element PSS / deg_red, front end, wire formats, options
@@ -389,11 +393,6 @@ class Engine : public IEngine {
     const char* pe = "llhlhh";
     for (int i = 0; i < 6; i++)
       ZK_HIP(hipStreamCreateWithPriority(&streams_[i], hipStreamNonBlocking, pe[i] == 'h' ? hi : lo));
-    for (int i = 0; i < NJOBS; i++) {
-      ZK_HIP(hipEventCreateWithFlags(&ev_in_[i], hipEventDisableTiming));
-      ZK_HIP(hipEventCreateWithFlags(&ev_gate_[i], hipEventDisableTiming));
-      for (hipEvent_t& e : ev_sorted_[i]) ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
     // host workers: the MSM tasks block on their events while the scalar-multiple tasks run
     int nthreads = host_threads_;                        // zk_ctx_set_option("host_threads"), before the first proof
     if (nthreads <= 0) {
@@ -407,9 +406,6 @@ class Engine : public IEngine {
   }
   std::unique_ptr<HostPool> pool_;
   HostPool* host_pool() override { return pool_.get(); }
-  hipEvent_t ev_in_[NJOBS] = {nullptr, nullptr};
-  hipEvent_t ev_gate_[NJOBS] = {nullptr, nullptr};
-  hipEvent_t ev_sorted_[NJOBS][NROLES] = {};     // by MsmRole: the "all sorts first" barrier of a proof (prove_begin_impl)
   int h_first_log_m_ = 20;      // zk_ctx_set_option("h_first_log_m"): see prove_begin_impl
   int host_threads_ = 0;        // zk_ctx_set_option("host_threads"): workers of the host pool (0 = by the core count)
   hipStream_t streams_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -371,12 +371,14 @@
     };
     Jacobian<Fq2_> jv;
     memcpy(&jv, sums[2], sizeof(jv));
-    return assemble_points(crs, r, s, j1(sums[0]), j1(sums[1]), jacobian_to_xyzz(jv), j1(sums[3]), j1(sums[4]), mk, n, pi_a,
-                           pi_b, pi_c);
+    return assemble_points(crs, r, s, MsmSums{j1(sums[0]), j1(sums[1]), j1(sums[3]), j1(sums[4]), jacobian_to_xyzz(jv)}, mk,
+                           n, pi_a, pi_b, pi_c);
   }
   // the same for `np` parties whose out-masks are rows 0..np-1 of mk->msm_out[*]
-  int assemble_points(const zk_crs_share* crs, const Fr& r, const Fr& s, const P1& S, const P1& H, const P2& V, const P1& W,
-                      const P1& U, const zk_groth16_masks* mk, int np, void* pi_a, void* pi_b, void* pi_c) {
+  int assemble_points(const zk_crs_share* crs, const Fr& r, const Fr& s, const MsmSums& t, const zk_groth16_masks* mk,
+                      int np, void* pi_a, void* pi_b, void* pi_c) {
+    const P1 &S = t.S, &H = t.H, &W = t.W, &U = t.U;
+    const P2& V = t.V;
     const bool r_zero = r.is_zero();
     P1 d1 = aff1(crs->delta_g1);
     P1 rN = host_scalar_mul<FrP, Fq_>(d1, r), sK = host_scalar_mul<FrP, Fq_>(d1, s),
@@ -427,46 +429,26 @@
     if (first < 0 || count <= 0 || first + count > n) return fail(ZK_ERR_BAD_INPUT, "bad party range");
     ProveJob& j = jobs_[0];
     if (j.active) return fail(ZK_ERR_BAD_INPUT, "zk_groth16_msms_begin called twice");
-    j.slot = 0;
     Fr r = skip_h ? Fr::zero() : Fr::one();          // only r == 0 matters here (H skipped, prove.rs:96-98)
-    int rc = prove_begin(j, crs, nullptr, nullptr, nullptr, a_share, ax_share, r, Fr::one(), 0, mk, 0, false, first,
-                         count, st);
-    if (rc) {
-      Status keep = last;
-      abort_job(j);
-      last = keep;
-    }
-    return rc;
+    return prove_begin(j, crs, nullptr, nullptr, nullptr, a_share, ax_share, r, Fr::one(), 0, mk, 0, false, first, count, st);
   }
   int msms_finish(const void* h_share, void* const* out, hipStream_t st) override {
     ProveJob& j = jobs_[0];
-    if (!j.active || j.full) return fail(ZK_ERR_BAD_INPUT, "zk_groth16_msms_finish without begin");
+    if (!j.active || j.pt.full || j.sharded) return fail(ZK_ERR_BAD_INPUT, "zk_groth16_msms_finish without begin");
     if (!h_share || !out) {
-      abort_job(j);
+      abort(j);
       return fail(ZK_ERR_BAD_INPUT, "null pointer");
     }
     int rc = prove_launch_u(j, h_share, st);
-    if (rc) {
-      Status keep = last;
-      abort_job(j);
-      last = keep;
-      return rc;
-    }
-    P1 S, H, W, U;
-    P2 V;
-    rc = prove_join(j, &S, &H, &V, &W, &U);
+    if (rc) return bail(j, rc);
+    rc = join(j, "zk_groth16_msms_finish");
     if (rc) return rc;
-    Jacobian<Fq_> jj;
-    jj = xyzz_to_jacobian(S);
-    memcpy(out[0], &jj, sizeof(jj));
-    jj = xyzz_to_jacobian(H);
-    memcpy(out[1], &jj, sizeof(jj));
-    Jacobian<Fq2_> j2 = xyzz_to_jacobian(V);
-    memcpy(out[2], &j2, sizeof(j2));
-    jj = xyzz_to_jacobian(W);
-    memcpy(out[3], &jj, sizeof(jj));
-    jj = xyzz_to_jacobian(U);
-    memcpy(out[4], &jj, sizeof(jj));
+    const MsmSums t = j.pt.sums();
+    msm_.write_jacobian(out[0], t.S);
+    msm_.write_jacobian(out[1], t.H);
+    msm_.write_jacobian(out[2], t.V);
+    msm_.write_jacobian(out[3], t.W);
+    msm_.write_jacobian(out[4], t.U);
     return ZK_OK;
   }
 

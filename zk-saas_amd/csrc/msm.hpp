@@ -1542,7 +1542,7 @@ struct MsmPending {
 };
 
 // Ordering between the accumulate kernels of concurrent launches (the Groth16 prover runs the G2 accumulate ahead of the
-// G1 ones: see engine_impl.hpp prove_begin).  The signalling launch records `signal_ev` right after its accumulate
+// G1 ones: see engine_groth16.inc.hpp batch_begin).  The signalling launch records `signal_ev` right after its accumulate
 // kernel and then raises `signal_flag`; a waiting launch (its sort work still runs ahead) spins on `wait_flag` on the
 // host -- so that the event it then waits for on its stream is this proof's record, not a stale one -- before its own
 // accumulate kernel.
