@@ -1,5 +1,5 @@
 """Window geometry, signed-digit recoding and scalar construction of the Pippenger MSM, restated in plain Python
-integers from the comments in csrc/msm_impl.hpp / csrc/msm.hpp (nothing is imported from the library): the tests
+integers from the comments in csrc/msm_plan.hpp (MsmWindows) / csrc/msm.hpp (nothing is imported from the library): the tests
 choose the digits the sort kernels see instead of hoping that random scalars reach them.
 
 A launch spreads T = BITS + 1 bits (room for the signed-digit carry) evenly over nwin = ceil(T / c_req) windows:

@@ -365,7 +365,7 @@ def test_table_msm_with_wide_sort_entries_equals_the_table_free_msm(log_n):
     free = aff(msm(pp, ZK_G1, pts, sc, n))
     api.msm_precompute(pp, ZK_G1, pts, n)
     try:
-        # window bits by the vector's length (csrc/msm.hpp table_c_auto): 17 bits = 15 windows below 2^22 points, 20 = 13 above
+        # window bits by the vector's length (csrc/msm_plan.hpp table_c_auto): 17 bits = 15 windows below 2^22 points, 20 = 13 above
         assert api.msm_table_info(pp, ZK_G1, pts) == ({"window_bits": 17, "windows": 15} if log_n < 22 else
                                                       {"window_bits": 20, "windows": 13})
         assert aff(msm(pp, ZK_G1, pts, sc, n)) == free

@@ -101,7 +101,7 @@ def test_a_wait_that_cannot_be_met_is_an_error_not_a_hang(capfd):
 
 def test_an_expired_standalone_msm_wait_wedges_the_context():
     """zk_msm's wait is bounded and wedges the context like the prover's: a table-free G1 MSM over 2^23 points takes ~12.7 ms
-    (csrc/msm.hpp, table_c_auto), more than ten times a 1 ms deadline.  Every MSM entry point and the prover then fail at
+    (csrc/msm_plan.hpp, table_c_auto), more than ten times a 1 ms deadline.  Every MSM entry point and the prover then fail at
     once, and a fresh context gives the first result."""
     from gpu_util import dec_jacobian
     from oracle.curve import g1

@@ -4,45 +4,44 @@
 // d_msm (dmsm/mod.rs:59-102).  The result of an MSM is a unique group element, so the algorithm below is
 // free to differ from arkworks' (SURVEY.md F6); what is reproduced is the value.
 //
-// Pipeline (all on one stream; DESIGN.md "MSM"):
-//   1. digits+count : scalar -> canonical integer -> signed c-bit digits; histogram per (window, |digit|)
-//   2. scan         : exclusive scan of {count, #segments} pairs
-//   3. scatter      : counting sort of point indices by bucket (sign in bit 31)
-//   4. (gone)       : round 2 cut buckets into segments and ordered them by length; see "balanced partition"
-//   5. accumulate   : equal contiguous ranges of the sorted entries, one per lane, mixed XYZZ additions   <- dominant
-//   6. finalize     : buckets that straddle a lane boundary are summed from the lanes' edge partials
-//   7. reduce       : sum_b (b+1) * bucket_b per window with per-lane suffix sums + an LDS tree across the
-//                     workgroup ("wavefront-level bucket reduction"); one (S, A) pair per workgroup
-//   8. host         : combines the few (S, A) pairs per window and folds windows high -> low
-//                     (254 sequential doublings: latency-bound on any one lane, cheap on a CPU core).
+// Pipeline (all on one stream; DESIGN.md "MSM"; the launch plan -- windows, lanes, sort split, workspace -- is
+// msm_plan.hpp's, the launches are msm_impl.hpp's):
+//   1. zero        : one launch clears the counters of the sort and the heavy-bucket counter
+//   2. sort        : scalar -> canonical integer -> signed digits of evenly spread windows -> point indices grouped by
+//                    bucket (sign in bit 31), identity bases and zero digits left out.  Two paths:
+//                      two-level sort ("big sort"): hist -> scatter (staged in LDS, or direct on small launches) -> binsort,
+//                                                   which also writes offsets[] and every lane's first bucket
+//                      atomics sort (small launches): digits pass 0 (count) -> three-launch scan -> lane starts ->
+//                                                   digits pass 1 (scatter)
+//   3. accumulate  : equal contiguous ranges of the sorted entries, one per lane (per lane quad in G2), mixed XYZZ
+//                    additions; see "balanced partition"                                                   <- dominant
+//   4. heavy       : buckets spread over more than FIN_SEQ lanes are summed by workgroups ("HEAVY LIST")
+//   5. finalize    : buckets that straddle a lane boundary are summed from the lanes' edge partials
+//   6. reduce A    : row and column sums of every bucket set, indexed by digit magnitude ("finalize / reduce")
+//   7. reduce B    : the c bit slices of those weighted sums per bucket set, written straight to the slot's pinned host
+//                    buffer, with the sorts' entry counts (zk_msm_stats) behind them
+//   8. host        : msm_fold_batch waits for the slot's event and folds slices and windows high -> low in one Horner walk
+//                    (254 sequential doublings: latency-bound on any one lane, cheap on a CPU core).
 #pragma once
-#include <atomic>
-#include <future>
-#include <map>
-#include <thread>
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <future>
+#include <map>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "ec.hpp"
 #include "engine.hpp"
+#include "msm_plan.hpp"
 #include "ntt.hpp"
 #include "quad.hpp"
 
 namespace zk {
 #if defined(__HIPCC__)
-
-constexpr size_t MSM_RANGE_MIN = 20, MSM_RANGE = 64;        // entries per accumulate lane: fewest (small MSMs), most
-                                                            // (SHA-256 proof, same box, round 5: 14 -> 622-626, 26 -> 629-630
-                                                            // against 646-649 proofs/s at 20)
-constexpr size_t MSM_RANGE_MIN_G2 = 16, MSM_RANGE_G2 = 64;  // ... per lane quad of the extension-field kernel (32 until
-                                                            // round 4; C5: 1.303 s at 32, 1.286 at 64, 1.280 at 128)
-constexpr uint32_t FIN_SEQ = 16;      // a bucket spread over more accumulate lanes than this is summed by a workgroup
 
 // The four MSMs of a proof, in the order of its "all sorts first" barrier (engine_groth16.inc.hpp prove_begin_impl):
 // S and H (one launch over both base vectors), W, V (G2), U (over h).  ROLE_NAME's first letters spell the batch's chain.
@@ -89,8 +88,7 @@ __device__ __forceinline__ T* zk_yshift(T* p, size_t bytes) {
 // witnesses of several proofs (zk_groth16_prove_batch).  Vector b of the batch gets its own bucket sets: everything
 // downstream of the sort sees `nb * sets_per` bucket sets where a single MSM has `sets_per` (1 with a fixed-base table,
 // one per window without), so the sort, accumulate, finalize and reduce launches are paid once per batch and every
-// launch carries nb times the lanes.
-constexpr int MSM_MAXB = 16;
+// launch carries nb times the lanes.  (MSM_MAXB: msm_plan.hpp)
 template <class F>
 struct MsmScalars {
   const F* p[MSM_MAXB];   // scalar vector b of the batch, npts elements each
@@ -292,17 +290,7 @@ ZK_D uint32_t msm_range_len(uint32_t entries, uint32_t nlanes, uint32_t tmin, ui
 //             bucket of every accumulate lane that starts inside the bin (msm_lane_start_kernel's job on this path);
 //             then chunks of THR*EPT entries are ranked into an LDS stage in bucket order and streamed to sorted[]
 // The order inside a bucket is arbitrary, as before; bucket sums do not depend on it.
-constexpr int BIG_HI = 8;                 // top bucket bits of a bin when nothing else decides (msm_big_hi)
-constexpr int BIG_MAX_BINS = 8192;
-constexpr int BIG_THREADS = 256;          // histogram tiles; scatter / binsort: 256 (small launches) or 1024
-constexpr int BIG_PTS_PER_THREAD = 8;     // most points per thread (scalars are held in registers by the scatter)
-constexpr int BIG_EPT = 16;               // entries per thread and chunk of the bin sort
-constexpr size_t BIG_LDS_MAX = 156 * 1024;
-inline int msm_big_hi(size_t nsets) {
-  int hi = BIG_HI;
-  while (hi > 0 && (nsets << hi) > (size_t)BIG_MAX_BINS) hi--;
-  return hi;
-}
+// (BIG_* constants, msm_big_hi and msm_bins_words, the layout of the bins block: msm_plan.hpp)
 
 // signed-digit walk over one scalar (shared by all sort kernels): fn(window, bucket index, negative)
 template <class FrP, class Fn>
@@ -372,9 +360,6 @@ __device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* sh /* 
   *total = tot;
   return pre + inc - v;
 }
-
-// Layout of the bins block (uint32): counts[nbins], ticket, base[nbins + 1], cursor[nbins]
-ZK_HD size_t msm_bins_words(size_t nbins) { return 3 * nbins + 2; }
 
 // scalar of (vector vb of the batch, point i); identity bases give zero (no digit, no entry)
 template <class FrP>
@@ -847,10 +832,7 @@ __global__ __launch_bounds__(THR) void msm_binsort_kernel(const uint32_t* __rest
 
 // -------------------------------------------------------------------------------------------------- scan
 // Exclusive scan of the per-key counts over `len` keys in three launches: offsets[k] = first sorted entry of key k,
-// offsets[len] = number of entries.
-constexpr int ISCAN_THREADS = 256;
-constexpr int ISCAN_PER = 8;
-constexpr int ISCAN_BLOCK = ISCAN_THREADS * ISCAN_PER;
+// offsets[len] = number of entries.  (ISCAN_THREADS x ISCAN_PER = ISCAN_BLOCK keys per workgroup: msm_plan.hpp)
 
 ZK_D uint32_t block_scan_u32(uint32_t v, uint32_t* sh, uint32_t* total) {
   int tid = threadIdx.x;
@@ -1031,9 +1013,7 @@ ZK_D void msm_report_heavy(uint32_t* __restrict__ heavy, uint32_t k, uint32_t L)
   heavy[2 + 2 * slot] = k;
   heavy[3 + 2 * slot] = (uint32_t)old;
 }
-// capacity of the list (entries) and of hpart[] (virtual workgroups) for a launch of nlanes accumulate lanes
-inline size_t msm_heavy_cap(size_t nlanes) { return nlanes / FIN_SEQ + 8; }
-inline size_t msm_heavy_vcap(size_t nlanes) { return nlanes / FIN_SEQ + nlanes / 256 + 8; }
+// (capacity of the list and of hpart[]: msm_plan.hpp msm_heavy_cap / msm_heavy_vcap)
 
 // Base fields whose running sums the accumulate kernel keeps as lazy residues (field.hpp, LAZY_OK) instead of the
 // canonical form.  Same-box A/B on BN254 (profiles/r04_acc_lazy_ab.txt): d_msm 8 x 2^20 12.40 against 12.78 ms (-3 %),
@@ -1487,7 +1467,7 @@ struct KernelField<Fp2T<P, false>> {
 };
 
 // ---------------------------------------------------------------------------------------------------- host
-// One workspace slot = device scratch + a pinned host buffer for the (S, A) pairs + the event that marks the end of
+// One workspace slot = device scratch + a pinned host buffer for the bit slices of the bucket sums + the event that marks the end of
 // the slot's last launch.  Independent MSMs run on different slots / streams.  A slot is busy from the first enqueue of
 // a launch until wait() has seen its event: it holds the launch's tables until then and refuses other launches.
 struct MsmSlot {
@@ -1529,15 +1509,10 @@ struct MsmBatchArg {
   const void* p[16] = {nullptr};
 };
 
-// The launch geometry of an MSM (or two sharing one sort) whose (S, A) pairs are on their way to the slot's pinned
-// buffer.  msm_fold() waits for the slot and folds on the host.
+// An MSM (or two over the same scalars) whose bit slices are on their way to the slot's pinned buffer: what the host
+// fold needs of the launch's plan.  msm_fold() waits for the slot and folds on the host.
 struct MsmPending {
-  int kwin = 0, c = 0, wide = 0, nb = 1, lo_bits = 0;
-  bool tabbed = false;                           // fixed-base table: one bucket set, every window c bits wide
-  int batch = 1;                                 // scalar vectors of the launch (results: [base vector][batch])
-  size_t stats_off = 0, offered = 0;             // statistics: where the sorts' entry counts land in the pinned buffer;
-  int nsorts = 1;                                // (point, window) pairs offered to the sort
-  bool g2 = false;
+  MsmFoldGeo fold;
   MsmSlot* slot = nullptr;                       // nullptr: nothing was launched (no points), the results are identities
 };
 
@@ -1568,73 +1543,10 @@ struct MsmTuning {
   // 23 / 27 / 33 KB, a loss at every size -- the gather-bound accumulate needs its waves more, profiles/r06_acc_lds_sweep.txt.)
 };
 
-// Window width: minimise nwin * (npts + 4 * buckets) -- mixed additions plus the per-bucket reduction work --
-// with nwin = ceil((BITS+1)/c) windows of evenly spread width (see msm_launch); ties go to the wider window
-// (more buckets = more lanes with shorter chains).
-template <class FrP>
-inline int msm_pick_c(size_t npts, bool g2 = false, int c_force = 0) {
-  if (c_force >= 2 && c_force <= 20) return c_force;      // zk_ctx_set_option "msm_c" / "msm_c_g2" (tests force widths)
-  int best = 4;
-  double best_cost = 1e300;
-  for (int c = 4; c <= 20; c++) {                     // > 17 only pays from ~2^25 points on (cost model below)
-    int nwin = (FrP::BITS + c) / c;
-    int ceff = (FrP::BITS + nwin) / nwin;          // widest window after spreading BITS+1 bits over nwin windows
-    // per-bucket work is priced at 4 additions up to 17 bits (tuned on 10^5..10^7 points) and at 10 above: measured
-    // on BLS12-381, 20-bit windows lose 13% at 2^24 points and win 8% at 2^26
-    double cost = (double)nwin * ((double)npts + (ceff > 17 ? 10.0 : 4.0) * (double)((size_t)1 << (ceff - 1)));
-    if (cost <= best_cost) {
-      best_cost = cost;
-      best = c;
-    }
-  }
-  return best;
-}
-
-// Accumulate lanes of a launch with at most `max_entries` sorted entries (msm.hpp "balanced partition"): entries per
-// lane `t` and the lane count that covers max_entries at that length.  Measured on batches of 1 / 2 / 4 / 8 119k-point
-// MSMs alone on the chip (1.9 M .. 15 M entries; the chip holds 196 608 lanes at three waves per SIMD, 262 144 at the four
-// the BN254 kernel is compiled for since round 4;
-// profiles/r03_range_sweep.txt): what matters is how many ROUNDS of waves a launch makes -- >= 1.6 rounds run at
-// 98-116 G multiplications/s, exactly one round at 79 (a grid that just fills the chip leaves the dispatcher no slack and
-// all its waves march in step), fewer than one underfills -- while every lane boundary costs one full addition (14
-// multiplications; 42 in G2) in the finalize kernel.  So: ~2.4 rounds, but never fewer than `lo` entries per lane (small
-// launches: the MSMs of ONE proof run four at a time and fill the chip together) nor more than `hi`.
-struct MsmLanes {
-  uint32_t nlanes, tmin, cap;
-};
-inline MsmLanes msm_pick_lanes(size_t max_entries, int waves, bool pair, int lanes_per_range = 0) {
-  if (!lanes_per_range) lanes_per_range = pair ? 2 : 1;
-  const size_t cap = (size_t)1024 * waves * (64 / lanes_per_range);
-  const size_t lo = pair ? MSM_RANGE_MIN_G2 : MSM_RANGE_MIN;
-  const size_t hi = pair ? MSM_RANGE_G2 : MSM_RANGE;
-  size_t t = std::min(hi, std::max(lo, (size_t)((double)max_entries / (2.4 * (double)cap))));
-  size_t nl = std::max<size_t>(1, (max_entries + t - 1) / t);
-  // between one and two rounds at this length msm_range_len splits the entries over TWO rounds of shorter ranges: the
-  // launch needs the lanes of two rounds then (found by the 2^18-point BLS12-381 prover test: 4.4 M entries at 20 per
-  // lane made 222 823 lanes, the two-round length of 12 covered 2.7 M entries and the rest was never added)
-  if (max_entries >= cap * t && max_entries < 2 * cap * t && (max_entries + 2 * cap - 1) / (2 * cap) >= 12)
-    nl = std::max(nl, 2 * cap);
-  return MsmLanes{(uint32_t)nl, (uint32_t)t, (uint32_t)cap};
-}
-
-template <class FrP>
-inline void msm_plan_of(size_t npts, bool g2, int* out, int c_force = 0) {
-  const int c_req = msm_pick_c<FrP>(npts ? npts : 1, g2, c_force);
-  const int T = FrP::BITS + 1;
-  const int nwin = (T + c_req - 1) / c_req;
-  out[0] = (T + nwin - 1) / nwin;
-  out[1] = nwin;
-  {
-    const size_t entries = npts * (size_t)nwin;
-    out[2] = (int)msm_pick_lanes(entries, g2 ? 2 : 3, g2).tmin;     // sorted entries (= mixed additions) per accumulate lane
-  }
-  out[3] = g2 ? 28 : 10;
-}
-
-// Enqueue the whole device pipeline of one MSM on `st` (digits .. reduce), the asynchronous copy of the (S, A) pairs
-// into the slot's pinned buffer and the slot's event; no host synchronisation.  bases2 (optional): a second base
-// vector multiplied by the SAME scalars (Groth16's a_query and b_g1_query over the witness shares): one sort, and
-// every later launch covers both through blockIdx.y.  Defined in msm_impl.hpp, instantiated once per (curve, group) in
+// Enqueue the whole device pipeline of one MSM on `st` (zero .. reduce B, which writes the bit slices into the slot's
+// pinned buffer) and the slot's event; no host synchronisation.  bases2 (optional): a second base vector multiplied
+// by the SAME scalars (Groth16's a_query and b_g1_query over the witness shares): one sort (one per vector when they
+// may hold identities), and every later launch covers both through blockIdx.y.  Defined in msm_impl.hpp, instantiated once per (curve, group) in
 // its own translation unit (msm_<curve>_g<k>.hip) so that the heavy kernels compile in parallel.
 template <class FrP, class Fld>
 int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* bases, const void* bases2,
@@ -1660,45 +1572,40 @@ int msm_table_launch(IEngine* eng, const void* bases, size_t len, int c, int nwi
 // results: [base vector v < nvec][scalar vector b < batch] at results[v * batch + b]
 template <class Fld>
 int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
-  const int batch = p.batch;
+  const MsmFoldGeo& f = p.fold;
+  const int batch = f.batch;
   for (int i = 0; i < nvec * batch; i++) results[i] = XYZZ<Fld>::identity();
   if (!p.slot) return ZK_OK;
   hipError_t he = p.slot->wait(eng);
   if (he == hipErrorNotReady)      // the slot stays busy (the kernels may still run); the caller wedges the context
-    return eng->fail(ZK_ERR_GENERIC, std::string("msm fold: the completion event of a ") + (p.g2 ? "G2" : "G1") +
+    return eng->fail(ZK_ERR_GENERIC, std::string("msm fold: the completion event of a ") + (f.g2 ? "G2" : "G1") +
                                          " MSM chain did not signal within the deadline (zk_ctx_set_option wait_deadline_ms)");
   if (he != hipSuccess) return eng->hip_fail(he, "msm event");
-  const int kwin = p.kwin, c = p.c, wide = p.wide, lo_bits = p.lo_bits, nslices = p.c;
-  const int hb = c - 1 - lo_bits;                  // row slices 0..hb come first, then lo_bits column slices
+  const int kwin = f.kwin, lo_bits = f.lo_bits, nslices = f.win.c;
+  const int hb = f.win.c - 1 - lo_bits;                  // row slices 0..hb come first, then lo_bits column slices
   const XYZZ<Fld>* hall = (const XYZZ<Fld>*)p.slot->pinned;
   {
     // statistics (zk_msm_stats): mixed additions performed = sorted entries, per base vector
-    const uint32_t* cnt = (const uint32_t*)((const char*)p.slot->pinned + p.stats_off);
+    const uint32_t* cnt = (const uint32_t*)((const char*)p.slot->pinned + f.stats_off);
     uint64_t adds = 0;
-    for (int v = 0; v < p.nb; v++) adds += cnt[2 * (p.nsorts == 2 ? v : 0)];
-    eng->msm_adds[p.g2 ? 1 : 0].fetch_add(adds, std::memory_order_relaxed);
-    eng->msm_offered[p.g2 ? 1 : 0].fetch_add(p.offered, std::memory_order_relaxed);
+    for (int v = 0; v < f.nb; v++) adds += cnt[2 * (f.nsorts == 2 ? v : 0)];
+    eng->msm_adds[f.g2 ? 1 : 0].fetch_add(adds, std::memory_order_relaxed);
+    eng->msm_offered[f.g2 ? 1 : 0].fetch_add(f.offered, std::memory_order_relaxed);
   }
-  if (nvec > p.nb) nvec = p.nb;
+  if (nvec > f.nb) nvec = f.nb;
   // windows [w_lo, w_hi] of one vector, high to low, doublings only INSIDE the range:
   // sum_w 2^(start_w - start_w_lo) X_w with X_w = sum_j 2^(j + lo_bits) TR_j + sum_j 2^j TC_j
   auto fold_range = [&](const XYZZ<Fld>* h, int w_hi, int w_lo) -> XYZZ<Fld> {
     XYZZ<Fld> total = XYZZ<Fld>::identity();
     for (int w = w_hi; w >= w_lo; w--) {
       const XYZZ<Fld>* sl = h + (size_t)w * nslices;
-      const int cw = (p.tabbed || w < wide) ? c : c - 1;
-      for (int t = cw - 1; t >= 0; t--) {
+      for (int t = f.win.width(w) - 1; t >= 0; t--) {      // (with a table: one bucket set, w = 0, c bits)
         total = xyzz_dbl_ni(total);
         const XYZZ<Fld>& s = t >= lo_bits ? sl[t - lo_bits] : sl[hb + 1 + t];
         if (!s.is_identity()) total = xyzz_add_ni(total, s);
       }
     }
     return total;
-  };
-  auto width_of = [&](int w_hi, int w_lo) {
-    int bits = 0;
-    for (int w = w_hi; w >= w_lo; w--) bits += (p.tabbed || w < wide) ? c : c - 1;
-    return bits;
   };
   // Table-free MSMs have one bucket set per window: ~250 doublings + c additions per window on one host thread
   // (0.4 ms for G2, the gap between two table-free proofs).  With the context's worker pool the windows are folded in
@@ -1738,7 +1645,7 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
   // the part holding the top window can hold little else; lower parts take more windows.  Greedy partition from the top
   // for the smallest cost bound that needs no more than max_parts parts.
   std::vector<int> start(kwin + 1, 0);             // bit position of window w
-  for (int w = 0; w < kwin; w++) start[w + 1] = start[w] + width_of(w, w);
+  for (int w = 0; w <= kwin; w++) start[w] = f.win.start(w);
   constexpr double ADD_COST = 0.6;                 // one addition in units of a doubling
   auto partition = [&](double bound, int* hi_w, int* lo_w) {
     int np = 0, w = kwin - 1;
@@ -1790,7 +1697,7 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
 // single scalar vector: result (and result2 for the second base vector of the launch)
 template <class Fld>
 int msm_fold(IEngine* eng, MsmPending& p, XYZZ<Fld>* result, XYZZ<Fld>* result2) {
-  if (p.slot && p.batch != 1) return eng->fail(ZK_ERR_GENERIC, "msm_fold on a batched launch");
+  if (p.slot && p.fold.batch != 1) return eng->fail(ZK_ERR_GENERIC, "msm_fold on a batched launch");
   XYZZ<Fld> r[2];
   int rc = msm_fold_batch<Fld>(eng, p, r, result2 ? 2 : 1);
   *result = r[0];
@@ -1831,7 +1738,13 @@ class MsmRunner {
   using Fq = Fp<typename Cfg::FqP>;
   using Fq2 = Fp2<typename Cfg::FqP>;
 
-  void plan(size_t npts, bool g2, int* out) const { msm_plan_of<FrP>(npts, g2, out, g2 ? c_g2 : c_g1); }
+  void plan(size_t npts, bool g2, int* out) const {
+    MsmPlanIn in;
+    in.scalar_bits = FrP::BITS, in.scalar_bytes = (int)sizeof(Fr), in.coord_bytes = (int)(g2 ? sizeof(Fq2) : sizeof(Fq));
+    in.g2 = g2, in.acc_waves = g2 ? SPLIT_WAVES<typename Cfg::FqP> : ACC_WAVES<Fq>;
+    in.npts = npts, in.c_force = g2 ? c_g2 : c_g1, in.bigsort_min = bigsort_min;
+    msm_plan_of(in, out);
+  }
   int c_g1 = 0, c_g2 = 0;        // zk_ctx_set_option "msm_c" / "msm_c_g2": forced window bits of table-free MSMs (0 = cost model)
 
   // launch on workspace slot `ws` (ws_job, ws_batch, ...); the result is collected with msm_fold / msm_fold_batch.  A
@@ -2009,34 +1922,16 @@ class MsmRunner {
   }
 
   // ---- fixed-base tables (zk_msm_precompute): process-wide registry keyed by address (engine.hpp TableRegistry)
-  // Window bits of new tables: 0 = by the vector's length (below), else what zk_ctx_set_option "msm_table_c" /
-  // "msm_table_c_g2" asked for (validated there: 0 or 8..22).  A table folds all windows into ONE set of 2^(c-1) buckets, so a
-  // bucket receives len * nwin / 2^(c-1) entries: once that is more than FIN_SEQ (16) accumulate ranges long, every
-  // bucket goes through the heavy-bucket path meant for degenerate scalars and the MSM is 2-3x slower than table-free
-  // (measured, tools/tab_c3.py, G1 d_msm over 2^19 / 2^20 / 2^23 points: c = 16 2.53 / 3.48 / 18.8 ms, c = 17 1.10 /
-  // 1.95 / 20.7, c = 20 1.45 / 2.2 / 11.8; table-free 1.59 / 2.77 / 12.7; below 2^19 points c = 16 is best: 0.78 against
-  // 1.15 ms table-free at 2^18).  G1: 15 bits (17 windows, 16 384 buckets) up to 2^17 points -- the SHA-256 proof's four G1
-  // MSMs: 6 % more mixed additions than 16 bits but half the buckets in the reduction every chain ends with: 634 / 649 /
-  // 653 / 651 vs 630 / 639 / 638 / 638 proofs/s, same box, round 5; 14 bits already sends every bucket down the heavy path:
-  // 512-542 --, 16 bits below 2^19 points, 18 below 2^22 (re-rounded to evenly spread windows: 17 bits
-  // = 15 windows on BN254's 254-bit Fr, 18 bits on BLS12-381's 255-bit Fr), 20 (13 windows) from there.
-  // G2: 15 bits = 17 windows, 16 384 buckets below 2^20 points (6 % more mixed additions than 16 bits but half the
-  // buckets in the G2 reduction, the latency chain a proof ends with: 458-477 vs 423-453 proofs/s, same box), 19 (14
-  // windows) from there (2^21 points: 11.1 ms against 17.8 at 15 bits and 11.8 table-free).
+  // Window bits of new tables: 0 = by the vector's length (msm_plan.hpp table_c_auto), else what zk_ctx_set_option
+  // "msm_table_c" / "msm_table_c_g2" asked for (validated there: 0 or 8..22).
   int table_c = 0;
   int table_c_g2 = 0;
-  static int table_c_auto(size_t len, bool g2) {
-    if (g2) return len < ((size_t)1 << 20) ? 15 : 19;
-    return len <= ((size_t)1 << 17) ? 15 : len < ((size_t)1 << 19) ? 16 : len < ((size_t)1 << 22) ? 18 : 20;
-  }
   template <class Fld>
   int precompute_t(IEngine* eng, const void* bases, size_t len, hipStream_t st) {
     if (!bases || !len) return eng->fail(ZK_ERR_BAD_INPUT, "null base vector");
-    const int T = FrP::BITS + 1;
     const int tc_opt = IsExtField<Fld>::value ? table_c_g2 : table_c;
-    const int tc = tc_opt > 0 ? tc_opt : table_c_auto(len, IsExtField<Fld>::value);
-    const int nwin = (T + tc - 1) / tc;
-    const int c = (T + nwin - 1) / nwin;
+    const MsmWindows win = MsmWindows::of(FrP::BITS, tc_opt > 0 ? tc_opt : table_c_auto(len, IsExtField<Fld>::value));
+    const int nwin = win.nwin, c = win.c;
     if ((size_t)nwin * len >= ((size_t)1 << 31)) return eng->fail(ZK_ERR_BAD_INPUT, "base vector too long for a table");
     auto t = std::make_shared<MsmTable>();
     t->base = (const char*)bases;
@@ -2044,7 +1939,7 @@ class MsmRunner {
     t->elem = sizeof(Affine<Fld>);
     t->c = c;
     t->nwin = nwin;
-    t->wide = T - nwin * (c - 1);
+    t->wide = win.wide;
     t->bits = FrP::BITS;
     t->device = eng->device;
     t->owner = eng;
