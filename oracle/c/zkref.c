@@ -442,6 +442,69 @@ void zkref_fft1(const pss_t* P, fe* px, size_t len, const fe* gen) {
     }
   }
 }
+/* out = a + b element-wise (the `share + in_mask` of dfft/mod.rs:254-258 on whole vectors) */
+void zkref_vec_add(const field_t* F, const fe* a, const fe* b, size_t n, fe* out) {
+  for (size_t i = 0; i < n; i++) fe_add(&out[i], &a[i], &b[i], F);
+}
+/* A second statement of fft1 that shares no butterfly with the loops above: single outputs of the closed form (DESIGN.md
+ * "fft1")  out[k] = sum_i x[i] * w_n^(rev(i) * (k + 1)),  w_n = gen^l,  rev = bit reversal on log2(len) bits,  i.e. the
+ * polynomial with coefficients y[j] = x[rev(j)] evaluated at z = w_n^(k+1) by Horner.  ks[nk] are the wanted outputs, spread
+ * over up to 16 threads; each thread walks the input once per group of up to EVAL_GROUP of its points. */
+#define EVAL_GROUP 8
+typedef struct {
+  const pss_t* P;
+  const fe* px;
+  size_t len;
+  const fe* wn;
+  const u64* ks;
+  size_t lo, hi;
+  fe* out;
+} eval_job;
+static void* fft1_eval_run(void* a) {
+  eval_job* J = (eval_job*)a;
+  const field_t* F = &J->P->F;
+  const int logn = ilog2(J->len);
+  for (size_t g0 = J->lo; g0 < J->hi; g0 += EVAL_GROUP) {
+    const int cnt = (int)(J->hi - g0 < EVAL_GROUP ? J->hi - g0 : EVAL_GROUP);
+    fe z[EVAL_GROUP], acc[EVAL_GROUP];
+    for (int c = 0; c < cnt; c++) {
+      fe_pow_u64(&z[c], J->wn, J->ks[g0 + c] + 1, F);
+      memset(&acc[c], 0, sizeof(fe));
+    }
+    for (size_t j = J->len; j-- > 0;) {
+      size_t r = 0, ra = 0;
+      for (int b = 0; b < logn; b++) r |= ((j >> b) & 1) << (logn - 1 - b);
+      if (j >= 16) {                               /* the walk jumps through the whole vector: fetch ahead */
+        for (int b = 0; b < logn; b++) ra |= (((j - 16) >> b) & 1) << (logn - 1 - b);
+        __builtin_prefetch(&J->px[ra]);
+      }
+      const fe* xi = &J->px[r];
+      for (int c = 0; c < cnt; c++) {
+        fe_mul(&acc[c], &acc[c], &z[c], F);
+        fe_add(&acc[c], &acc[c], xi, F);
+      }
+    }
+    for (int c = 0; c < cnt; c++) J->out[g0 + c] = acc[c];
+  }
+  return NULL;
+}
+void zkref_fft1_eval(const pss_t* P, const fe* px, size_t len, const fe* gen, const u64* ks, size_t nk, int nthreads,
+                     fe* out) {
+  fe wn;
+  fe_pow_u64(&wn, gen, (u64)P->l, &P->F);
+  if (nthreads > 16) nthreads = 16;
+  if (nthreads < 1) nthreads = 1;
+  if ((size_t)nthreads > nk) nthreads = nk ? (int)nk : 1;
+  pthread_t th[16];
+  eval_job jobs[16];
+  for (int t = 0; t < nthreads; t++) {
+    jobs[t] = (eval_job){P, px, len, &wn, ks, nk * t / nthreads, nk * (t + 1) / nthreads, out};
+    if (nthreads > 1) pthread_create(&th[t], NULL, fft1_eval_run, &jobs[t]);
+    else fft1_eval_run(&jobs[t]);
+  }
+  if (nthreads > 1)
+    for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
+}
 /* dfft/mod.rs:210-237 */
 static void fft2(const pss_t* P, fe** s1p, fe** s2p, size_t dom_size, const fe* gen) {
   const field_t* F = &P->F;

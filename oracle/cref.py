@@ -101,6 +101,31 @@ class CPss:
         lib().zkref_fft1(C.byref(self.ct), self._p(a), C.c_size_t(len(vec)), self.fr.mont(gen))
         return self.fr.dec(a)
 
+    def fft1_arrays(self, arr, gen):
+        """zkref_fft1 in place on a uint64 array [len][4] of Montgomery residues (gen is an int); returns arr.  The call
+        releases the GIL, so several vectors can run on Python threads."""
+        assert arr.dtype == np.uint64 and arr.flags.c_contiguous and arr.shape[1:] == (NL,)
+        lib().zkref_fft1(C.byref(self.ct), self._p(arr), C.c_size_t(arr.shape[0]), self.fr.mont(gen))
+        return arr
+
+    def add_arrays(self, a, b):
+        """a + b element-wise on uint64 arrays [len][4] of Montgomery residues (zkref_vec_add); returns a new array."""
+        assert a.shape == b.shape and a.dtype == b.dtype == np.uint64 and a.flags.c_contiguous and b.flags.c_contiguous
+        out = np.empty_like(a)
+        lib().zkref_vec_add(C.byref(self.fr.ct), self._p(a), self._p(b), C.c_size_t(a.shape[0]), self._p(out))
+        return out
+
+    def fft1_eval_arrays(self, arr, gen, ks, threads=16):
+        """Outputs ks of fft1(arr) from the closed form out[k] = sum_i x[i] w_n^(rev(i) (k + 1)) (zkref_fft1_eval: Horner
+        over the bit-reversed input, no butterfly); arr uint64 [len][4] is left as it is.  Returns uint64 [len(ks)][4]."""
+        assert arr.dtype == np.uint64 and arr.flags.c_contiguous and arr.shape[1:] == (NL,)
+        kk = np.ascontiguousarray(ks, dtype=np.uint64)
+        assert kk.size == 0 or int(kk.max()) < arr.shape[0]
+        out = np.zeros((kk.size, NL), dtype=np.uint64)
+        lib().zkref_fft1_eval(C.byref(self.ct), self._p(arr), C.c_size_t(arr.shape[0]), self.fr.mont(gen), self._p(kk),
+                              C.c_size_t(kk.size), int(threads), self._p(out))
+        return out
+
     def d_fft_arrays(self, shares, mbyl, gen, size_inv, g, rearrange, in_mask, out_mask, seed):
         """shares: uint64 array [n*mbyl][4] modified in place (gen, size_inv, g are ints)."""
         lib().zkref_d_fft(C.byref(self.ct), self._p(shares), C.c_size_t(mbyl), self.fr.mont(gen),

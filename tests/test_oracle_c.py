@@ -65,6 +65,58 @@ def test_fft1_and_deg_red():
     assert cp.deg_red(mul, masks, 11) == od.deg_red(mul, masks, o, seed=11)
 
 
+@pytest.mark.parametrize("name,l", [("bn254", 1), ("bn254", 2), ("bn254", 4), ("bn254", 8), ("bls12_381", 2),
+                                    ("bls12_377", 2)])
+def test_fft1_arrays_and_the_closed_form_evaluator_equal_both_butterfly_oracles(name, l):
+    """The two references of tests/test_gpu_ntt_sizes.py pinned on each other and on the Python oracle: zkref_fft1 on
+    numpy residues (CPss.fft1_arrays) == oracle.dist.fft1_in_place == zkref_fft1_eval (Horner over the bit-reversed input,
+    no butterfly) at ALL outputs, for vector lengths 1 .. 256, both directions, every thread count up to the cap and
+    unsorted, repeated positions."""
+    cp = CPss(name, l)
+    o = cp.opp
+    for log_n in (0, 1, 2, 3, 5, 8):
+        n = 1 << log_n
+        dom = Domain(CURVES[name], n * l)
+        v = rand_vec(60 + log_n, n, o.p)
+        if log_n == 3:
+            v[0], v[1], v[-1] = 0, o.p - 1, 1
+        for gen in (dom.group_gen, dom.group_gen_inv):
+            want = od.fft1_in_place(list(v), o, gen)
+            a = cp.fr.enc(v)
+            keep = a.copy()
+            assert cp.fr.dec(cp.fft1_arrays(a, gen)) == want
+            assert cp.fft1(v, gen) == want
+            for threads in (1, 3, 16, 40):
+                got = cp.fft1_eval_arrays(keep, gen, np.arange(n), threads=threads)
+                assert np.array_equal(got, a), (log_n, threads)
+            ks = [n - 1, 0, n // 2, n - 1]
+            assert np.array_equal(cp.fft1_eval_arrays(keep, gen, ks, threads=2), a[ks])
+            assert np.array_equal(keep, cp.fr.enc(v))                       # the evaluator leaves its input alone
+    assert cp.fft1_eval_arrays(cp.fr.enc([5]), 1, [], threads=4).shape == (0, 4)
+
+
+@pytest.mark.parametrize("name", ["bn254", "bls12_377", "bls12_381"])
+def test_add_arrays_equals_python_integers(name):
+    cp = CPss(name, 2)
+    p = cp.opp.p
+    a, b = rand_vec(70, 40, p), rand_vec(71, 40, p)
+    a[:4], b[:4] = [0, p - 1, p - 1, 1], [0, p - 1, 1, p - 1]
+    assert cp.fr.dec(cp.add_arrays(cp.fr.enc(a), cp.fr.enc(b))) == [(x + y) % p for x, y in zip(a, b)]
+
+
+def test_closed_form_evaluator_equals_fft1_on_a_two_pass_size_with_many_points_per_thread():
+    """2^12 elements, 200 positions: more than one group of eight per thread, against zkref_fft1's full output."""
+    cp = CPss("bn254", 2)
+    n = 1 << 12
+    dom = Domain(BN254, 2 * n)
+    rng = np.random.default_rng(3)
+    a = rng.integers(0, 1 << 62, size=(n, 4), dtype=np.uint64)
+    a[:, 3] &= np.uint64((1 << 60) - 1)
+    full = cp.fft1_arrays(a.copy(), dom.group_gen_inv)
+    ks = rng.integers(0, n, size=200)
+    assert np.array_equal(cp.fft1_eval_arrays(a, dom.group_gen_inv, ks), full[ks])
+
+
 @pytest.mark.parametrize("name,threads", [("bn254", 1), ("bn254", 3), ("bls12_381", 1)])
 def test_d_pp_c_matches_python_oracle(name, threads):
     """zkref_d_pp (dpp/mod.rs:15-87 in C, one inverse() per element) == oracle/dist.py d_pp, and the reference's own
@@ -189,26 +241,27 @@ def test_tuned_king_gives_the_reference_kings_shares():
 
 def test_threaded_d_fft_equals_the_serial_restatement():
     """zkref_d_fft_mt (parties' local stages on n threads, matrix king over several) is what the 2^24 checks of
-    tests/test_gpu_configs.py run: same shares as zkref_d_fft, masks and coset shift included, on both scalar fields."""
+    tests/test_gpu_configs.py run: same shares as zkref_d_fft, masks and coset shift included, on both scalar fields and at every packing factor
+    (tests/test_gpu_ntt_sizes.py takes it as the reference for l = 1, 4, 8 from m = 2^18 up)."""
     import numpy as np
     from oracle.cref import CPss
     from oracle.field import Domain
     from oracle.params import CURVES
-    for cv in ("bn254", "bls12_381"):
-        cp, c = CPss(cv, 2), CURVES[cv]
+    for cv, l in (("bn254", 2), ("bls12_381", 2), ("bn254", 1), ("bn254", 4), ("bn254", 8)):
+        cp, c = CPss(cv, l), CURVES[cv]
         m = 1 << 10
         dom = Domain(c, m)
         rng = np.random.default_rng(1)
 
         def rand():
-            a = rng.integers(0, 1 << 62, size=(cp.n * (m // 2), 4), dtype=np.uint64)
+            a = rng.integers(0, 1 << 62, size=(cp.n * (m // l), 4), dtype=np.uint64)
             a[:, 3] &= np.uint64((1 << 60) - 1)
             return a
         a, im, om = rand(), rand(), rand()
         g = Domain(c, 2 * m).element(1)
         for inverse in (True, False):
             x, y = a.copy(), a.copy()
-            args = (m // 2, dom.group_gen_inv if inverse else dom.group_gen, dom.size_inv if inverse else None,
+            args = (m // l, dom.group_gen_inv if inverse else dom.group_gen, dom.size_inv if inverse else None,
                     g if inverse else None, inverse, im, om, 7)
             cp.d_fft_arrays(x, *args)
             cp.d_fft_arrays_mt(y, *args, king_threads=4)

@@ -122,12 +122,12 @@
     if (rc) return rc;
     Fr* data = (Fr*)shares;
     size_t nvec = (size_t)1 << log_n;
-    if ((log_n < NTT_TILE_BITS_SMALL || force_simple_ntt) && src.p[0]) {
+    if (log_n < NTT_TILE_BITS_SMALL && src.p[0]) {
       for (size_t y = 0; y < batch; y += src.per)
         ZK_HIP(hipMemcpyAsync(data + y * nvec, src.p[y / src.per], (size_t)src.per * nvec * sizeof(Fr),
                               hipMemcpyDeviceToDevice, st));
     }
-    if (log_n < NTT_TILE_BITS_SMALL || force_simple_ntt) {
+    if (log_n < NTT_TILE_BITS_SMALL) {
       for (int s = 1; s <= log_n; s++) {
         size_t work = (nvec / 2) * batch;
         ntt_stage_simple_kernel<Fr><<<dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st>>>(data, log_n, s, tw,
@@ -147,6 +147,7 @@
     constexpr size_t TILE = (size_t)1 << TB;
     const size_t nvec = (size_t)1 << log_n;
     NttPlan plan = make_ntt_plan(log_n, TB);
+    if (plan.npass == 0) return fail(ZK_ERR_BAD_INPUT, "transform too large for the four-pass plan");
     for (int p = 0; p < plan.npass; p++) {
       const NttPass& ps = plan.pass[p];
       int rbits = ps.s1 - ps.s0;

@@ -410,7 +410,6 @@ class Engine : public IEngine {
   int host_threads_ = 0;        // zk_ctx_set_option("host_threads"): workers of the host pool (0 = by the core count)
   hipStream_t streams_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool streams_ready_ = false;
-  bool force_simple_ntt = false;
   bool ntt_attr_set_[2] = {false, false};
   bool dpp_attr_set_[2] = {false, false};
   std::map<std::string, void*> base_tables_;

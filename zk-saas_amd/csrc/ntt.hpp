@@ -38,10 +38,14 @@ struct NttPlan {
 
 inline int ntt_tile_bits(int log_n) { return log_n <= NTT_SMALL_MAX_LOG_N ? NTT_TILE_BITS_SMALL : NTT_TILE_BITS; }
 
-// tb = tile bits; passes after the first take at most tb - 2 stages so that a tile keeps >= 4 adjacent columns
+// tb = tile bits; passes after the first take at most tb - 2 stages so that a tile keeps >= 4 adjacent columns.
+// Valid for tb >= 3 and 0 <= k <= tb + 3 (tb - 2), the sizes that fit the four passes of NttPlan (k <= 26 on the small
+// tile, k <= 38 on the large one; the engine asks for tb = 8 at k = 8..14 and tb = 11 above).  Outside that domain the
+// plan comes back EMPTY (npass = 0) and nothing is written past pass[] / parts[]; fft1_tiled turns it into ZK_ERR_BAD_INPUT.
 inline NttPlan make_ntt_plan(int k, int tb = NTT_TILE_BITS) {
   NttPlan p{};
   p.log_n = k;
+  if (tb < 3 || k < 0 || k > tb + 3 * (tb - 2)) return p;
   if (k <= tb) {
     p.npass = 1;
     p.pass[0] = {0, k, 0};
@@ -296,7 +300,8 @@ __global__ __launch_bounds__((1 << TB) / 4, TB >= 10 ? 4 : 16) void ntt_pass_ker
 }
 
 // Small / generic path: one launch per stage, one thread per butterfly, straight from HBM.
-// Used for n < 2048 and as an independent on-device cross-check of the tiled path.
+// Used for n < 256 (log_n below NTT_TILE_BITS_SMALL), where a vector is smaller than the smallest tile; every larger
+// size takes ntt_pass_kernel.  tests/test_gpu_ntt_sizes.py compares both paths with the C oracle at every size.
 template <class F>
 __global__ void ntt_stage_simple_kernel(F* __restrict__ data, int log_n, int s, const F* __restrict__ tw_full,
                                         int log_l, size_t batch) {
