@@ -543,6 +543,38 @@ int zk_d_msm_parties(zk_ctx* ctx, int group, const void* bases_d, const void* sc
                      const uint32_t* parties, int nparties, const void* in_mask, const void* out_mask, void* out,
                      void* stream);
 
+/* ---- the verifier: pairings and Groth16 verification on the device (BN254 and BLS12-381) --------------------
+ * A BLS12-377 context returns ZK_ERR_BAD_INPUT ("no pairing parameters") from every function of this section.
+ *
+ * zk_multi_pairing = ark-ec Pairing::multi_pairing: out[i] = final_exp(prod_j miller(P[i][j], Q[i][j])), i < count, j < k.
+ * p_affine_d [count][k] G1 affine, q_affine_d [count][k] G2 affine, gt_out_d [count][12] Fq (Montgomery), coefficient
+ * order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... = arkworks' Fp12 in memory = snarkjs' [2][3][2] nesting.  An identity in
+ * either slot of a pair contributes 1.  Points are taken as given (no curve or subgroup check).  The BN254 final
+ * exponentiation raises to the exponent of the Fuentes-Castaneda chain that arkworks and snarkjs use, so the values are
+ * theirs; BLS12-381 uses the exact (q^12 - 1) / r.  Returns when the result is in gt_out_d. */
+int zk_multi_pairing(zk_ctx* ctx, const void* p_affine_d, const void* q_affine_d, size_t k, size_t count, void* gt_out_d,
+                     void* stream);
+/* Parity access to the lane-split Fq12 tower the pairing kernels run on (like zk_fq_selftest): a_d, b_d, out_d [len][12]
+ * Fq in the order above; op 0 mul, 1 sqr, 2 inverse, 3 conjugate, 4 / 5 / 6 Frobenius^1..3, 7 cyclotomic squaring (a in
+ * the cyclotomic subgroup), 8 a * (l0 + lS w^S + l3 w^3) with l0, lS, l3 = the first three Fq2 of b (the line of a Miller
+ * step; S = 1 on BN254's D-type twist, 2 on BLS12-381's M-type twist).  b_d may be NULL for ops 1..7. */
+int zk_fq12_selftest(zk_ctx* ctx, int op, const void* a_d, const void* b_d, size_t len, void* out_d, void* stream);
+/* ark_groth16 prepare_verifying_key / verify_proof (groth16/examples/sha256.rs:400-415).
+ * zk_groth16_vk_prepare: host affine points (gamma_abc_g1: n_abc of them); e(alpha, beta) is computed here, once.
+ * zk_groth16_verify: proofs_affine = [count][8 |Fq| limbs], exactly what zk_groth16_reconstruct writes (A | B | C), host;
+ * public_inputs = [count][n_inputs] Fr in Montgomery form, host, WITHOUT the leading 1; n_inputs + 1 != n_abc returns
+ * ZK_ERR_BAD_INPUT ("malformed verifying key").  Per proof: acc = abc[0] + sum_i x_i abc[i + 1];
+ * ok[i] = (final_exp(miller(A, B) miller(acc, -gamma) miller(C, -delta)) == e(alpha, beta)).  A point of a proof that is
+ * not on its curve (or a coordinate that is not below q) gives ok[i] = 0, not an error.  As in verify_proof there is NO
+ * G2 subgroup check (nor a G1 one): a caller that needs it decompresses with validation first.  Every step runs on the
+ * device; the call returns with ok filled, and its wait honours the option wait_deadline_ms. */
+typedef struct zk_vk zk_vk;
+int zk_groth16_vk_prepare(zk_ctx* ctx, const void* alpha_g1, const void* beta_g2, const void* gamma_g2,
+                          const void* delta_g2, const void* gamma_abc_g1, size_t n_abc, zk_vk** out);
+void zk_groth16_vk_free(zk_vk* vk);
+int zk_groth16_verify(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affine, const void* public_inputs, size_t n_inputs,
+                      size_t count, uint8_t* ok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,146 @@
+"""The verifier timed on one GPU: us per proof of zk_groth16_verify and us per pairing of zk_multi_pairing (k = 1) at
+count = 1, 16, 256 and 4096 on BN254 and BLS12-381.
+usage: python tools/verify_bench.py [--counts 1,16,256,4096] [--curves bn254,bls12_381] [--reps 7] [--out FILE] [--cpu-oracle]
+Per (curve, call, count): one warm-up call, then `reps` timed calls (host clock around a call that returns with the
+result on the host or in device memory after its own wait), reported as median, min and max; the per-kernel share comes
+from the library's HIP-event slots (pairing_miller_kernel, pairing_final_exp_kernel) over the same calls.  The proofs are
+real ones of a small circuit (one public input), repeated to fill the batch; every verdict is checked.  Spread between
+machines is not measured by one run: run it on two and state both.  --cpu-oracle also times the Python oracle's
+verify_proof on this machine's CPU (the only verifier the project had before), one proof.
+A kernel profile of the same calls: rocprofv3 --kernel-trace --stats -d DIR -- python tools/verify_bench.py --reps 2"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import zksaas_amd as zk
+from zksaas_amd import groth16 as zg
+from zksaas_amd.api import ZK_G1, ZK_G2, multi_pairing
+
+
+def small_r1cs(P, nc=11):
+    """a chain of nc multiplication gates with one public output"""
+    from zksaas_amd.sha256_circuit import R1CS
+    w = [1, 0, 7, 5]
+    A, B, Cm = [], [], []
+    for _ in range(nc - 1):
+        k = len(w)
+        w.append((w[k - 1] + 3) * (w[k - 1] + w[k - 2]) % P)
+        A.append([(1, k - 1), (3, 0)])
+        B.append([(1, k - 1), (1, k - 2)])
+        Cm.append([(1, k)])
+    A.append([(1, len(w) - 1)])
+    B.append([(1, 0)])
+    Cm.append([(1, 1)])
+    w[1] = w[-1]
+    return R1CS(2, len(w) - 2, A, B, Cm), w
+
+
+def slots(pp):
+    out = {}
+    for slot in range(pp.lib.zk_profile_slots()):
+        name = pp.lib.zk_profile_name(slot).decode()
+        if not name.startswith("pairing_"):
+            continue
+        ms, units, calls = C.c_double(), C.c_double(), C.c_long()
+        pp._check(pp.lib.zk_profile_read(pp.h, slot, C.byref(ms), C.byref(units), C.byref(calls)))
+        if calls.value:
+            out[name] = round(ms.value / calls.value * 1e3, 1)          # us per launch
+    return out
+
+
+def timed(pp, fn, reps):
+    fn()                                                              # warm-up: code objects, allocations
+    pp._check(pp.lib.zk_profile_enable(pp.h, 1))
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    k = slots(pp)
+    pp._check(pp.lib.zk_profile_enable(pp.h, 0))
+    return ts, k
+
+
+def run(curve, counts, reps):
+    pp = zk.PackedSharingParams(curve, 2)
+    P = zk.fields.FR[curve]
+    r1, w = small_r1cs(P)
+    setup = zg.SetupScalars(curve, r1, 11, 12, 13, 14, 15)
+    crs = zg.Crs(pp, setup)
+    wit = zg.Witness(pp, curve, r1, w, seed=5)
+    aff, _ = zg.reconstruct(pp, zg.prove(pp, crs, wit, 21, 22, seed=9), want_bytes=False)
+    vk = zg.verifying_key(pp, setup)
+    pvk = zg.PreparedVk(pp, vk)
+    rows = []
+    for count in counts:
+        proofs = np.tile(aff, (count, 1))
+        xs = [[w[1]]] * count
+        res = []
+        ts, k = timed(pp, lambda: res.append(zg.verify(pp, pvk, proofs, xs)), reps)
+        assert all(all(r) for r in res), "a valid proof was rejected"
+        rows.append(row(curve, "zk_groth16_verify", count, ts, k))
+        sc = pp.upload_fr([3 + i for i in range(count)])
+        p1, q2 = zg.base_points(pp, ZK_G1, sc, count), zg.base_points(pp, ZK_G2, sc, count)
+        out = zk.DeviceBuffer(pp, count * 12 * pp.fq.nbytes)
+        ts, k = timed(pp, lambda: multi_pairing(pp, p1, q2, 1, count, out=out), reps)
+        rows.append(row(curve, "zk_multi_pairing k=1", count, ts, k))
+        for b in (sc, p1, q2, out):
+            b.free()
+    return rows, (pp, vk, aff, w)
+
+
+def row(curve, call, count, ts, kernels):
+    med = statistics.median(ts)
+    r = {"curve": curve, "call": call, "count": count, "reps": len(ts), "median_ms": round(med * 1e3, 3),
+         "min_ms": round(min(ts) * 1e3, 3), "max_ms": round(max(ts) * 1e3, 3), "us_per_item": round(med / count * 1e6, 2),
+         "kernels_us_per_launch": kernels}
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def cpu_oracle(curve, pp, vk, aff, w):
+    from oracle import pairing as op
+    from oracle.curve import g1
+    from oracle.params import CURVES
+    c = CURVES[curve]
+    v = pp.fq.decode(np.asarray(aff).reshape(-1, pp.fq.nl))
+    proof = ((v[0], v[1]), ((v[2], v[3]), (v[4], v[5])), (v[6], v[7]))
+    ovk = op.VerifyingKey(vk["alpha_g1"], vk["beta_g2"], vk["gamma_g2"], vk["delta_g2"], vk["gamma_abc_g1"])
+    t0 = time.perf_counter()
+    ok = op.verify_proof(c, ovk, proof, [w[1]], g1(c))
+    return {"curve": curve, "call": "oracle.pairing.verify_proof (CPU, Python ints)", "count": 1, "ok": ok,
+            "us_per_item": round((time.perf_counter() - t0) * 1e6, 0)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--counts", default="1,16,256,4096")
+    ap.add_argument("--curves", default="bn254,bls12_381")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--cpu-oracle", action="store_true")
+    a = ap.parse_args()
+    out = {"tool": "tools/verify_bench.py", "reps": a.reps, "rows": []}
+    for curve in a.curves.split(","):
+        rows, (pp, vk, aff, w) = run(curve, [int(c) for c in a.counts.split(",")], a.reps)
+        out["rows"] += rows
+        if a.cpu_oracle:
+            r = cpu_oracle(curve, pp, vk, aff, w)
+            print(json.dumps(r), flush=True)
+            out["rows"].append(r)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -27,6 +27,7 @@ SYMBOLS = [
     "zk_net_parties", "zk_dist_groth16_prove_async", "zk_dist_groth16_wait", "zk_fq_selftest",
     "zk_dist_deg_red_points", "zk_dist_libsnark_h", "zk_deg_red_host", "zk_d_pp_host", "zk_circom_h_host",
     "zk_groth16_prove_host",
+    "zk_multi_pairing", "zk_fq12_selftest", "zk_groth16_vk_prepare", "zk_groth16_vk_free", "zk_groth16_verify",
 ]
 
 _lib = None
@@ -199,5 +200,11 @@ def load():
     lib.zk_profile_name.argtypes = [i32]
     lib.zk_profile_name.restype = C.c_char_p
     lib.zk_profile_read.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long)]
+    lib.zk_multi_pairing.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+    lib.zk_fq12_selftest.argtypes = [vp, i32, vp, vp, sz, vp, vp]
+    lib.zk_groth16_vk_prepare.argtypes = [vp, vp, vp, vp, vp, vp, sz, C.POINTER(vp)]
+    lib.zk_groth16_vk_free.argtypes = [vp]
+    lib.zk_groth16_vk_free.restype = None
+    lib.zk_groth16_verify.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]
     _lib = lib
     return lib

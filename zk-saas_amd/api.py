@@ -411,3 +411,24 @@ def vec_scale(pp, x_d, k, length, stream=None):
 def vec_mul_sub(pp, out_d, a_d, b_d, c_d, length, stream=None):
     pp._check(pp.lib.zk_vec_mul_sub(pp.h, _ptr(out_d), _ptr(a_d), _ptr(b_d), _ptr(c_d), length, stream))
     return out_d
+
+
+FQ12_OPS = {"mul": 0, "sqr": 1, "inverse": 2, "conj": 3, "frobenius1": 4, "frobenius2": 5, "frobenius3": 6,
+            "cyclotomic_sqr": 7, "line_mul": 8}
+
+
+def multi_pairing(pp, p_affine_d, q_affine_d, k, count, out=None, stream=None):
+    """zk_multi_pairing (ark-ec Pairing::multi_pairing): out[i] = final_exp(prod_j miller(P[i][j], Q[i][j])) for
+    [count][k] affine G1 / G2 points on the device.  Returns a DeviceBuffer of [count][12] Fq (Montgomery) in the
+    coefficient order of arkworks' Fp12."""
+    out = out or DeviceBuffer(pp, max(1, count) * 12 * pp.fq.nbytes)
+    pp._check(pp.lib.zk_multi_pairing(pp.h, _ptr(p_affine_d), _ptr(q_affine_d), k, count, out.ptr, stream))
+    return out
+
+
+def fq12_selftest(pp, op, a_d, b_d, length, out=None, stream=None):
+    """zk_fq12_selftest: one operation of the lane-split Fq12 tower on [length][12] Fq; op is a key of FQ12_OPS."""
+    out = out or DeviceBuffer(pp, max(1, length) * 12 * pp.fq.nbytes)
+    pp._check(pp.lib.zk_fq12_selftest(pp.h, FQ12_OPS[op] if isinstance(op, str) else int(op), _ptr(a_d), _ptr(b_d), length,
+                                      out.ptr, stream))
+    return out

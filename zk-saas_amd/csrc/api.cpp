@@ -8,10 +8,12 @@
 
 #include "../../include/zksaas.h"
 #include "engine.hpp"
+#include "pairing.hpp"
 #include "prng.hpp"
 
 struct zk_ctx {
   zk::IEngine* eng;
+  int curve;
 };
 struct zk_net {
   zk::Net net;
@@ -51,7 +53,7 @@ int zk_ctx_create(int curve, int l, int device, zk_ctx** out) {
     default: return ZK_ERR_BAD_INPUT;
   }
   if (!e) return ZK_ERR_GENERIC;
-  zk_ctx* c = new (std::nothrow) zk_ctx{e};
+  zk_ctx* c = new (std::nothrow) zk_ctx{e, curve};
   if (!c) {
     delete e;
     return ZK_ERR_GENERIC;
@@ -735,7 +737,8 @@ static const char* const kSlotNames[zk::PROF_NSLOTS] = {"ntt_pass_kernel", "king
                                                          "msm_finalize+reduce<G2>", "dpp_tile_kernel", "dpp_carry_kernel",
                                                          "dpp_finish_kernel", "host:prove_launch", "host:prove_wait",
                                                          "host:prove_tail", "host:launch.submit", "host:launch.circom_h",
-                                                         "host:launch.u_msm"};
+                                                         "host:launch.u_msm", "pairing_miller_kernel",
+                                                         "pairing_final_exp_kernel"};
 int zk_profile_enable(zk_ctx* ctx, int on) {
   CTX_OR_FAIL();
   e->prof.reset();
@@ -785,6 +788,43 @@ int zk_groth16_prove(zk_ctx* ctx, const zk_crs_share* crs, const void* qap_a_d, 
   CTX_OR_FAIL();
   return e->groth16_prove(crs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m, masks, seed, pi_a,
                           pi_b, pi_c, S(stream));
+}
+
+// ---- the verifier (pairing.hpp): the kernels are compiled per curve in pairing_<curve>.hip ----
+#define PAIRING_OR_FAIL()                                                                       \
+  CTX_OR_FAIL();                                                                                \
+  zk::IPairing* pr = ctx->curve == ZK_BN254 ? zk::pairing_bn254()                               \
+                     : ctx->curve == ZK_BLS12_381 ? zk::pairing_bls381() : nullptr;             \
+  if (!pr) return e->fail(ZK_ERR_BAD_INPUT, "no pairing parameters for this curve")
+int zk_multi_pairing(zk_ctx* ctx, const void* p_affine_d, const void* q_affine_d, size_t k, size_t count, void* gt_out_d,
+                     void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->multi_pairing(e, p_affine_d, q_affine_d, k, count, gt_out_d, S(stream));
+}
+int zk_fq12_selftest(zk_ctx* ctx, int op, const void* a_d, const void* b_d, size_t len, void* out_d, void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->fq12_selftest(e, op, a_d, b_d, len, out_d, S(stream));
+}
+int zk_groth16_vk_prepare(zk_ctx* ctx, const void* alpha_g1, const void* beta_g2, const void* gamma_g2,
+                          const void* delta_g2, const void* gamma_abc_g1, size_t n_abc, zk_vk** out) {
+  PAIRING_OR_FAIL();
+  if (!out) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+  *out = nullptr;
+  zk_vk* vk = new (std::nothrow) zk_vk();
+  if (!vk) return e->fail(ZK_ERR_GENERIC, "out of memory");
+  const int rc = pr->vk_prepare(e, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc, vk);
+  if (rc) {
+    delete vk;
+    return rc;
+  }
+  *out = vk;
+  return ZK_OK;
+}
+void zk_groth16_vk_free(zk_vk* vk) { delete vk; }
+int zk_groth16_verify(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affine, const void* public_inputs, size_t n_inputs,
+                      size_t count, uint8_t* ok, void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->verify(e, vk, proofs_affine, public_inputs, n_inputs, count, ok, S(stream));
 }
 
 }  // extern "C"

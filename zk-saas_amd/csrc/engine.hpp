@@ -35,7 +35,9 @@ enum ProfSlot { PROF_NTT_PASS = 0, PROF_KING, PROF_MSM_ACC_G1, PROF_MSM_ACC_G2, 
                 // last chain (the U-MSM); then -> return
                 PROF_HOST_LAUNCH, PROF_HOST_WAIT, PROF_HOST_TAIL,
                 // parts of the first: entry -> MSM tasks handed to the pool; circom_h's launches; the U-MSM's launches + host terms
-                PROF_HOST_SUBMIT, PROF_HOST_H, PROF_HOST_U, PROF_NSLOTS };
+                PROF_HOST_SUBMIT, PROF_HOST_H, PROF_HOST_U,
+                // the verifier (pairing.hpp): Miller loops + group product, then the final exponentiation; units = pairs / groups
+                PROF_MILLER, PROF_FINAL_EXP, PROF_NSLOTS };
 
 struct Profiler {
   bool on = false;

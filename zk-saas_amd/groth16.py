@@ -294,6 +294,53 @@ def verifying_key(pp, setup):
     return {"alpha_g1": p1[0], "gamma_abc_g1": p1[1:], "beta_g2": p2[0], "gamma_g2": p2[1], "delta_g2": p2[2]}
 
 
+class PreparedVk:
+    """zk_groth16_vk_prepare (ark_groth16 prepare_verifying_key): the verifying key on the device with e(alpha, beta)
+    computed once.  vk_dict is what verifying_key() returns (affine coordinate ints; None = the identity)."""
+
+    def __init__(self, pp, vk_dict):
+        self.pp = pp
+        self.n_abc = len(vk_dict["gamma_abc_g1"])
+        p1 = lambda p: [0, 0] if p is None else [p[0], p[1]]
+        p2 = lambda p: [0, 0, 0, 0] if p is None else [p[0][0], p[0][1], p[1][0], p[1][1]]
+        alpha = _affine_codec(pp, p1(vk_dict["alpha_g1"]), False)
+        g2 = [_affine_codec(pp, p2(vk_dict[k]), True) for k in ("beta_g2", "gamma_g2", "delta_g2")]
+        abc = _affine_codec(pp, [c for p in vk_dict["gamma_abc_g1"] for c in p1(p)], False)
+        self.h = C.c_void_p()
+        pp._check(pp.lib.zk_groth16_vk_prepare(pp.h, alpha.ctypes.data, g2[0].ctypes.data, g2[1].ctypes.data,
+                                               g2[2].ctypes.data, abc.ctypes.data, self.n_abc, C.byref(self.h)))
+
+    def free(self):
+        if self.h:
+            self.pp.lib.zk_groth16_vk_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def verify(pp, pvk, proofs, public_inputs, stream=None):
+    """zk_groth16_verify (ark_groth16 Groth16::verify_proof, sha256.rs:400-415) on the device.  proofs: a list of
+    reconstruct()'s `affine` arrays (or one [count][8 nl] array); public_inputs: per proof the list of Fr ints without
+    the leading 1.  Returns list[bool]; a proof with a point off its curve is False.  No subgroup check is made."""
+    nl = pp.fq.nl
+    pr = np.ascontiguousarray(np.asarray(proofs, dtype=np.uint64).reshape(-1, 8 * nl))
+    count = pr.shape[0]
+    if len(public_inputs) != count:
+        raise ValueError("one list of public inputs per proof")
+    n_inputs = len(public_inputs[0]) if count else 0
+    if any(len(x) != n_inputs for x in public_inputs):
+        raise ValueError("every proof takes the same number of public inputs")
+    xs = np.ascontiguousarray(pp.fr.encode([v for x in public_inputs for v in x]))
+    ok = np.zeros(max(1, count), dtype=np.uint8)
+    pp._check(pp.lib.zk_groth16_verify(pp.h, pvk.h, pr.ctypes.data, xs.ctypes.data if xs.size else None, n_inputs, count,
+                                       ok.ctypes.data, stream))
+    return [bool(v) for v in ok[:count]]
+
+
 def prove(pp, crs, wit, r, s, masks=None, seed=0, stream=None):
     """dsha256 (sha256.rs:32-129) for all parties. Returns (pi_a [n][3nl], pi_b [n][6nl], pi_c [n][3nl]) Jacobian."""
     nl = pp.fq.nl
