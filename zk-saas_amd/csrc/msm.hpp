@@ -1295,8 +1295,10 @@ __global__ __launch_bounds__(64) void msm_heavy_kernel(const XYZZ<Fld>* __restri
     const uint32_t l0 = o0 / T, l1 = (o1 - 1) / T;
     const uint32_t chunk = (l1 - l0 + S - 1) / S;
     const uint32_t first = l0 + 1 + s * chunk, last = first + chunk - 1 < l1 ? first + chunk - 1 : l1;
-    Fld acc = (s == 0 && vl == 0) ? qload(tail + l0, q) : qidentity<Fld>(q);
-    for (uint32_t l = first + (uint32_t)vl; l <= last; l += (uint32_t)nq) acc = qadd(acc, qload(head + l, q), q);
+    // a quad's sum starts from the first point it loads, not from an identity seed (quad.hpp qaccum)
+    bool have = s == 0 && vl == 0;
+    Fld acc = have ? qload(tail + l0, q) : qidentity<Fld>(q);
+    for (uint32_t l = first + (uint32_t)vl; l <= last; l += (uint32_t)nq) qaccum(acc, have, head + l, q);
     acc = wg_quad_sum(acc, sh, vl, q, nq);
     if (vl == 0) qstore(S == 1 ? buckets + kh : hpart + v, q, acc);
     __syncthreads();
@@ -1335,7 +1337,8 @@ __global__ __launch_bounds__(FIN_THREADS) void msm_finalize_kernel(const XYZZ<Fl
       const uint32_t vb = heavy[3 + 2 * h], S = (h + 1 < nh ? heavy[3 + 2 * (h + 1)] : V) - vb;
       if (S == 1) continue;                             // (workgroup-uniform)
       Fld acc = qidentity<Fld>(q);
-      for (uint32_t j = (uint32_t)vl; j < S; j += FIN_THREADS / 4) acc = qadd(acc, qload(hpart + vb + j, q), q);
+      bool have = false;
+      for (uint32_t j = (uint32_t)vl; j < S; j += FIN_THREADS / 4) qaccum(acc, have, hpart + vb + j, q);
       acc = wg_quad_sum(acc, sh, vl, q, FIN_THREADS / 4);
       if (vl == 0) qstore(buckets + heavy[2 + 2 * h], q, acc);
       __syncthreads();
@@ -1375,17 +1378,18 @@ __global__ __launch_bounds__(QUAD_THREADS, 2) void msm_reduce_a_kernel(const XYZ
   const int q = threadIdx.x & 3, vl = threadIdx.x >> 2;
   const uint32_t g = blockIdx.x * (uint32_t)((int)blockDim.x / 4 / nvl) + (uint32_t)(vl / nvl);
   const uint32_t sub = (uint32_t)(vl & (nvl - 1));
-  Fld acc = qidentity<Fld>(q);
+  Fld acc = qidentity<Fld>(q);                      // a quad without a bucket keeps it
+  bool have = false;                                // ... the others start from their first bucket (quad.hpp qaccum)
   if (g <= HI) {                                    // row hi = g: lo runs over the row
     for (uint32_t lo = sub; lo < LO; lo += (uint32_t)nvl) {
       uint32_t k = g * LO + lo;
-      if (k >= 1 && k <= B) acc = qadd(acc, qload(wb + (k - 1), q), q);
+      if (k >= 1 && k <= B) qaccum(acc, have, wb + (k - 1), q);
     }
   } else if (g < ngroups) {                         // column lo = g - HI - 1: hi runs over the column
     const uint32_t lo = g - HI - 1;
     for (uint32_t hi = sub; hi <= HI; hi += (uint32_t)nvl) {
       uint32_t k = hi * LO + lo;
-      if (k >= 1 && k <= B) acc = qadd(acc, qload(wb + (k - 1), q), q);
+      if (k >= 1 && k <= B) qaccum(acc, have, wb + (k - 1), q);
     }
   }
   acc = wg_quad_sum(acc, sh, vl, q, nvl);
@@ -1414,14 +1418,17 @@ __global__ __launch_bounds__(QUAD_THREADS, 2) void msm_reduce_b_kernel(const XYZ
   const int q = threadIdx.x & 3, vl = threadIdx.x >> 2;
   const int j = (int)blockIdx.x * ((int)blockDim.x / 4 / nvl) + vl / nvl;
   const uint32_t sub = (uint32_t)(vl & (nvl - 1));
+  // the quads of a slice share out the indices that HAVE bit j (msm_plan.hpp msm_slice_index): every quad gets a point
+  // while there are any, instead of half the quads two and the other half none
   Fld acc = qidentity<Fld>(q);
+  bool have = false;
   if (j <= hb) {
-    for (uint32_t hi = sub; hi <= HI; hi += (uint32_t)nvl)
-      if ((hi >> j) & 1u) acc = qadd(acc, qload(rc + hi, q), q);
+    const uint32_t cnt = msm_slice_count(HI + 1, j);              // rows 0..HI; row HI = 2^hb belongs to slice hb alone
+    for (uint32_t t = sub; t < cnt; t += (uint32_t)nvl) qaccum(acc, have, rc + msm_slice_index(t, j), q);
   } else if (j < nslices) {
     const int jj = j - hb - 1;
-    for (uint32_t lo = sub; lo < LO; lo += (uint32_t)nvl)
-      if ((lo >> jj) & 1u) acc = qadd(acc, qload(rc + HI + 1 + lo, q), q);
+    const uint32_t cnt = msm_slice_count(LO, jj);
+    for (uint32_t t = sub; t < cnt; t += (uint32_t)nvl) qaccum(acc, have, rc + HI + 1 + msm_slice_index(t, jj), q);
   }
   acc = wg_quad_sum(acc, sh, vl, q, nvl);
   if (sub == 0 && j < nslices) qstore(out0 + (size_t)blockIdx.y * nslices + j, q, acc);

@@ -37,6 +37,24 @@ constexpr int ISCAN_THREADS = 256;
 constexpr int ISCAN_PER = 8;
 constexpr int ISCAN_BLOCK = ISCAN_THREADS * ISCAN_PER;
 
+// Bit slices of reduce stage B (msm.hpp msm_reduce_b_kernel): slice j sums the rows (or columns) whose index has bit j
+// set.  The quads of a slice enumerate exactly those indices -- the t-th of them is t with a 1 inserted at bit position
+// j -- instead of walking every index and skipping half.  Host and device: the kernel and tests/native read the same map.
+#if defined(__HIPCC__)
+#define ZK_PLAN_HD __host__ __device__
+#else
+#define ZK_PLAN_HD
+#endif
+ZK_PLAN_HD constexpr uint32_t msm_slice_index(uint32_t t, int j) {
+  return ((t >> j) << (j + 1)) | (1u << j) | (t & ((1u << j) - 1u));
+}
+// how many indices in [0, n) have bit j set (rows: n = HI + 1, so that the single index HI = 2^hb falls to slice hb alone;
+// columns: n = LO)
+ZK_PLAN_HD constexpr uint32_t msm_slice_count(uint32_t n, int j) {
+  const uint32_t rem = n & ((2u << j) - 1u);
+  return ((n >> (j + 1)) << j) + (rem > (1u << j) ? rem - (1u << j) : 0u);
+}
+
 // capacity of the heavy list (entries) and of hpart[] (virtual workgroups) for a launch of nlanes accumulate lanes
 // (msm.hpp "HEAVY LIST")
 inline size_t msm_heavy_cap(size_t nlanes) { return nlanes / FIN_SEQ + 8; }

@@ -68,56 +68,75 @@ ZK_D void qstore(XYZZ<Fld>* p, int q, const Fld& c) {
   store_elem(reinterpret_cast<Fld*>(p) + q, c);
 }
 
+// 2 a for a point spread over a quad (dbl-2008-s-1: U = 2Y, V = U^2, W = U V, S = X V, M = 3 X^2, X3 = M^2 - 2S,
+// Y3 = M (S - X3) - W Y, ZZ3 = V ZZ, ZZZ3 = W ZZZ) in three rounds of one multiplication per lane:
+//   round 1   XX = X X         V = U U          -                 -
+//   round 2   S = X V          W = U V          ZZ3 = ZZ V        MM = M M
+//   round 3   M (S - X3)       W Y              -                 ZZZ3 = W ZZZ
+// Out of line: qadd branches here (quad-uniformly) when its operands turn out equal, which well-spread scalars never
+// produce, so that the additions of every tail kernel do not carry the doubling's operand selects.  `a` must not be the
+// identity.  By value: the limbs travel in registers.
+template <class Fld>
+__device__ __noinline__ Fld qdbl(Fld ca, int q) {
+  const Fld cu = qsel(q == 1, ca.dbl(), ca);                           // X   U   ZZ   ZZZ
+  const Fld m2 = cu * cu;                                              // XX  V   -    -
+  const Fld XX = qperm<0, 0, 0, 0>(m2);
+  const Fld M = XX.dbl() + XX;
+  const Fld m3 = qsel(q == 3, M, cu) * qsel(q == 3, M, qperm<1, 1, 1, 1>(m2));     // S  W  ZZ3  MM
+  const Fld W = qperm<1, 1, 1, 1>(m3), S = qperm<0, 0, 0, 0>(m3);
+  const Fld X3 = qperm<3, 3, 3, 3>(m3) - S.dbl();                      // MM - 2S
+  const Fld m4 = qsel(q == 0, M, W) * qsel(q == 0, S - X3, ca);        // M(S-X3)  WY  -  ZZZ3
+  const Fld Y3 = qperm<0, 0, 0, 0>(m4) - qperm<1, 1, 1, 1>(m4);
+  return qsel(q == 0, X3, qsel(q == 1, Y3, qsel(q == 2, m3, m4)));
+}
+
 // a + b for points spread over quads (ca, cb: this lane's coordinate of a and of b); every lane returns its
-// coordinate of the sum.  q = lane & 3.
-//
-// Equal points (P = R = 0 after round 1) are doubled IN THE SAME three remaining rounds by switching operands
-// (dbl-2008-s-1: U = 2Y, V = U^2, W = U V, S = X V, M = 3 X^2, X3 = M^2 - 2S, Y3 = M (S - X3) - W Y, ZZ3 = V ZZ,
-// ZZZ3 = W ZZZ), so the rare case costs a few selects instead of a second code path:
-//   round 2   XX = X X         V = U U          -                 -
-//   round 3   S = X V          W = U V          ZZ3 = ZZ V        MM = M M
-//   round 4   M (S - X3)       W Y              -                 ZZZ3 = W ZZZ
+// coordinate of the sum.  q = lane & 3.  Equal points (P = R = 0 after round 1) leave for qdbl.  The zero tests run in the
+// lane that holds the value and ONE dword is broadcast (not the value, to be tested by all four lanes).
 template <class Fld>
 ZK_D Fld qadd(const Fld& ca, const Fld& cb, int q) {
   const bool even = (q & 1) == 0;
-  const bool za = qperm<2, 2, 2, 2>(ca).is_zero();
-  const bool zb = qperm<2, 2, 2, 2>(cb).is_zero();
+  const uint32_t zab = qperm_u32<2, 2, 2, 2>((ca.is_zero() ? 1u : 0u) | (cb.is_zero() ? 2u : 0u));   // lane 2: ZZ1, ZZ2
+  const bool za = (zab & 1u) != 0, zb = (zab & 2u) != 0;
   // round 1
   Fld A = qsel(even, qperm<0, 0, 1, 1>(ca), qperm<0, 0, 1, 1>(cb));   // X1  X2  Y1   Y2
   Fld B = qsel(even, qperm<2, 2, 3, 3>(cb), qperm<2, 2, 3, 3>(ca));   // ZZ2 ZZ1 ZZZ2 ZZZ1
   const Fld m1 = A * B;                                                // U1  U2  S1   S2
   const Fld d = qperm<1, 1, 3, 3>(m1) - qperm<0, 0, 2, 2>(m1);         // P   P   R    R
-  const bool pz = qperm<0, 0, 0, 0>(d).is_zero();
-  const bool rz = qperm<2, 2, 2, 2>(d).is_zero();
-  const bool D = pz && rz && !za && !zb;                               // doubling (quad-uniform)
-  const Fld cu = qsel(q == 1, ca.dbl(), ca);                           // X   U   ZZ   ZZZ
+  const uint32_t dz = d.is_zero() ? 1u : 0u;
+  const bool pz = qperm_u32<0, 0, 0, 0>(dz) != 0, rz = qperm_u32<2, 2, 2, 2>(dz) != 0;
+  if (pz && rz && !za && !zb) return qdbl(ca, q);                      // equal points (quad-uniform)
   // round 2
-  A = qsel(D, cu, qsel(even, d, qperm<0, 2, 2, 3>(ca)));               // P   ZZ1 R    ZZZ1   | X  U  -  -
-  B = qsel(D, cu, qsel(even, d, qperm<0, 2, 2, 3>(cb)));               // P   ZZ2 R    ZZZ2   | X  U  -  -
-  const Fld m2 = A * B;                                                // PP  ZZ12 RR  ZZZ12  | XX V  -  -
-  const Fld XX = qperm<0, 0, 0, 0>(m2);
-  const Fld M = XX.dbl() + XX;                                         // used by the doubling only
+  A = qsel(even, d, qperm<0, 2, 2, 3>(ca));                            // P   ZZ1 R    ZZZ1
+  B = qsel(even, d, qperm<0, 2, 2, 3>(cb));                            // P   ZZ2 R    ZZZ2
+  const Fld m2 = A * B;                                                // PP  ZZ12 RR  ZZZ12
   // round 3
-  A = qsel(D, qsel(q == 3, M, cu), qsel(q == 2, qperm<0, 1, 1, 3>(m2), qsel(q == 1, d, m1)));   // U1 P ZZ12 - | X U ZZ M
-  B = qsel(D, qsel(q == 3, M, qperm<1, 1, 1, 1>(m2)), XX);                                       // PP          | V V V  M
-  const Fld m3 = A * B;                                                // Q   PPP ZZ3  -      | S  W  ZZ3 MM
-  const Fld m3_1 = qperm<1, 1, 1, 1>(m3);                              // PPP                 | W
-  const Fld m3_0 = qperm<0, 0, 0, 0>(m3);                              // Q                   | S
-  const Fld T = qsel(D, qperm<3, 3, 3, 3>(m3), qperm<2, 2, 2, 2>(m2)) - m3_0.dbl();     // RR - 2Q | MM - 2S
-  const Fld X3f = qsel(D, T, T - m3_1);                                              // RR - 2Q - PPP | MM - 2S
+  A = qsel(q == 2, qperm<0, 1, 1, 3>(m2), qsel(q == 1, d, m1));        // U1  P   ZZ12 -
+  const Fld m3 = A * qperm<0, 0, 0, 0>(m2);                            // Q   PPP ZZ3  -
+  const Fld m3_1 = qperm<1, 1, 1, 1>(m3);                              // PPP
+  const Fld m3_0 = qperm<0, 0, 0, 0>(m3);                              // Q
+  const Fld X3f = qperm<2, 2, 2, 2>(m2) - m3_0.dbl() - m3_1;           // RR - 2Q - PPP
   // round 4
-  A = qsel(D, qsel(q == 0, M, m3_1),                                                 // M  W  -  W
-           qsel(q == 1, qperm<2, 2, 2, 2>(d), qsel(q == 0, qperm<2, 2, 2, 2>(m1), m2)));   // S1 R (RR) ZZZ12
-  B = qsel(D, qsel(q == 0, m3_0 - X3f, ca),                                          // S-X3  Y  -  ZZZ
-           qsel(q == 1, m3_0 - X3f, m3_1));                                          // PPP Q-X3 PPP PPP
-  const Fld m4 = A * B;                                                // S1PPP R(Q-X3) - ZZZ3 | M(S-X3) WY - ZZZ3
-  const Fld m4_0 = qperm<0, 0, 0, 0>(m4), m4_1 = qperm<1, 1, 1, 1>(m4);
-  const Fld Y3 = qsel(D, m4_0 - m4_1, m4_1 - m4_0);
+  A = qsel(q == 1, qperm<2, 2, 2, 2>(d), qsel(q == 0, qperm<2, 2, 2, 2>(m1), m2));   // S1 R (RR) ZZZ12
+  B = qsel(q == 1, m3_0 - X3f, m3_1);                                  // PPP Q-X3 PPP PPP
+  const Fld m4 = A * B;                                                // S1PPP R(Q-X3) - ZZZ3
+  const Fld Y3 = qperm<1, 1, 1, 1>(m4) - qperm<0, 0, 0, 0>(m4);
   Fld r = qsel(q == 0, X3f, qsel(q == 1, Y3, qsel(q == 2, m3, m4)));
   if (pz && !rz) r = qidentity<Fld>(q);                                // inverse points
   if (zb) r = ca;
   if (za) r = cb;
   return r;
+}
+
+// acc += *p for a running sum that starts EMPTY (`have` false, acc = the identity): the first point is taken as it is
+// loaded -- qadd(identity, P) would run all four rounds and then return P's limbs -- and only the following ones are
+// added.  `have` must be quad-uniform.
+template <class Fld>
+ZK_D void qaccum(Fld& acc, bool& have, const XYZZ<Fld>* p, int q) {
+  const Fld e = qload(p, q);
+  if (have) acc = qadd(acc, e, q);
+  else acc = e;
+  have = true;
 }
 
 // ---- mixed addition of an EXTENSION-field point shared by a QUAD of lanes, ONE BASE-FIELD VALUE PER LANE (round 4)
