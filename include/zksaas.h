@@ -178,6 +178,13 @@ int zk_pss_pack_points(zk_ctx* ctx, int group, const void* points_d, size_t nchu
                        void* shares_d, void* stream);
 int zk_base_mul(zk_ctx* ctx, int group, const void* base_affine, const void* scalars_d, size_t len,
                 void* out_affine_d, void* stream);
+/* zk_base_mul_few: the same product for a FEW scalars (the share scalars of MsmMask::sample, dmsm/mod.rs:34-38: 2 n per
+ * mask): a group of 8 lanes per scalar over the base's 8-bit window table, folded in a tree -- zk_base_mul gives a lane a
+ * whole scalar, which is right at 2^17 scalars and a serial chain at 64.  scalars_d: Montgomery Fr (device), base_affine:
+ * host; out_jacobian_d: len JACOBIAN points (device; no inversion; a zero scalar gives Z = 0).  len above 4096 returns
+ * ZK_ERR_BAD_INPUT: use zk_base_mul. */
+int zk_base_mul_few(zk_ctx* ctx, int group, const void* base_affine, const void* scalars_d, size_t len,
+                    void* out_jacobian_d, void* stream);
 
 /* ---- Groth16 composition (groth16/src/ext_wit.rs, prove.rs, examples/sha256.rs:32-129) -------------------
  * All n parties' shares live on this device.  Mask slots may be NULL (the *::zero() masks).
@@ -282,6 +289,20 @@ int zk_ctx_set_option(zk_ctx* ctx, const char* name, long long value);
  * is a random multiple of gen).  gen_affine: the group generator (host, affine Montgomery); in_mask / out_mask
  * (HOST) receive n Jacobian points each. */
 int zk_msm_mask_sample(zk_ctx* ctx, int group, const void* gen_affine, uint64_t seed, void* in_mask, void* out_mask);
+/* zk_groth16_deal_masks: ALL preprocessing material of nproofs proofs in one call (groth16/examples/sha256.rs:226-291:
+ * six FftMask::sample, one DegRedMask::sample, five MsmMask::sample per proof).  masks[b] names the DESTINATIONS, of
+ * exactly the kinds zk_groth16_prove reads (fft_in/out[k], degred_in/out: device [n][m/l] Fr; msm_in/out[k]: host, n
+ * Jacobian points, k = 2 in G2), so the filled structs go to zk_groth16_prove / _async / _batch as they are.  A slot
+ * whose two pointers are NULL is skipped (it stays the ::zero() mask); one NULL pointer of a pair, a G2 slot without
+ * g2_gen_affine or on a curve without G2 -> ZK_ERR_BAD_INPUT.  FFT masks k < 3 are FftMask::sample with rearrange, g =
+ * the 2m-th root of unity and the inverse transform (the three d_ifft of ext_wit.rs:127-142), k >= 3 the plain forward
+ * form; the DegRedMask is over m/l chunks; the MsmMasks are multiples of the generators (scalar form of
+ * zk_msm_mask_sample), computed on the device: one launch for all share scalars, one zk_base_mul_few launch per group.
+ * Replay mode: proof b draws what the single samplers draw with seed + 16 b (the stride of zk_groth16_prove_batch) + k
+ * for FFT mask k, + 6 for deg_red, + 7 + k for MSM mask k; otherwise fresh nonces, none used twice.  Any nproofs >= 1
+ * (16 proofs per internal pass).  Returns with the host points written and the device masks ordered on `stream`. */
+int zk_groth16_deal_masks(zk_ctx* ctx, int nproofs, int log2_m, const void* g1_gen_affine, const void* g2_gen_affine,
+                          uint64_t seed, const zk_groth16_masks* masks, void* stream);
 
 /* ---- circom front end (what the reference takes from ark-circom + groth16/src/qap.rs) ------------------
  * zk_r1cs_qap: qap.rs:42-89 (`qap::<F, D>()` for the circom reduction): A and B as CSR on the device
@@ -296,6 +317,17 @@ int zk_r1cs_qap(zk_ctx* ctx, const void* a_row_ptr_d, const void* a_col_d, const
                 const void* b_row_ptr_d, const void* b_col_d, const void* b_val_d, const void* w_d,
                 size_t num_variables, size_t num_constraints, size_t num_instance, int log_m, void* a_out_d,
                 void* b_out_d, void* c_out_d, void* stream);
+/* zk_groth16_deal_witness: a device-resident assignment w_d -> the five share vectors zk_groth16_prove takes (QAP::pss,
+ * groth16/src/qap.rs:91-135, and the two pack_from_witness of sha256.rs:131-156, 205-224) without a trip through the
+ * host: zk_r1cs_qap (same CSR arguments), bit reversal and pack at order 1 with seeds seed + 0, 1, 2 -> qap_a/b/c_d
+ * [n][m/l]; w[1..] packed with seed + 3 -> a_share_d [n][len_a], w[ni..] with seed + 4 -> ax_share_d [n][len_w], both
+ * straight from w_d with the last chunk's tail read as zero.  len_a = ceil((nv - 1) / l) and len_w = ceil((nv - ni) / l)
+ * are written to *len_a / *len_w (either may be NULL); with all five outputs NULL that is all the call does (size query). */
+int zk_groth16_deal_witness(zk_ctx* ctx, const void* a_row_ptr_d, const void* a_col_d, const void* a_val_d,
+                            const void* b_row_ptr_d, const void* b_col_d, const void* b_val_d, const void* w_d,
+                            size_t num_variables, size_t num_constraints, size_t num_instance, int log_m, uint64_t seed,
+                            void* qap_a_d, void* qap_b_d, void* qap_c_d, void* a_share_d, void* ax_share_d, size_t* len_a,
+                            size_t* len_w, void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

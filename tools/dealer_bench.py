@@ -12,6 +12,13 @@ kernel executes them, and `frac_issue_bound` = products / s over the multiplier'
   msm_table_build   zk_msm_precompute over the five packed query vectors
   fft_mask_sample   `FftMask::sample` (`dfft/mod.rs:30-85`) at 2^15 and 2^20
   degred_mask_sample / msm_mask_sample   `deg_red.rs:40-66`, `dmsm/mod.rs:21-47`
+  proof_masks       the twelve masks of a proof at the SHA-256 proof's size (log_m = 15, sha256.rs:226-291): ms per mask set
+                    through the twelve single sampler calls (`twelve_calls`), through zk_groth16_deal_masks at nproofs = 1 and
+                    8 (`deal_b1`, `deal_b8`: median, min and max of the repetitions, per set), mask sets per second, and the
+                    MsmMask part alone on the host (five zk_msm_mask_sample) against the device (deal_masks with only the MSM
+                    slots set) -- all in this process, every path writing into buffers allocated before the clock starts
+  witness_deal      ms per witness of the SHA-256 circuit: the former composition (zk_r1cs_qap, zk_bitrev, zk_pss_pack, the
+                    witness downloaded, sliced and padded in Python and uploaded again) against zk_groth16_deal_witness
 """
 import json
 import os
@@ -42,6 +49,111 @@ def timed(pp, fn, reps):
         ts.append(time.perf_counter() - t0)
     ts.sort()
     return ts[len(ts) // 2]
+
+
+def timed_spread(pp, fn, reps):
+    """median, min, max of `reps` synchronised calls (after one warm-up call)"""
+    fn()
+    pp.sync()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        pp.sync()
+        ts.append(time.perf_counter() - t0)
+    ts.sort()
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def ms3(t, per=1):
+    return {"ms": round(t[0] / per * 1e3, 4), "min_ms": round(t[1] / per * 1e3, 4), "max_ms": round(t[2] / per * 1e3, 4)}
+
+
+def twelve_call_masks(pp, log_m, seed, g1, g2, pm, w2m):
+    """The composition zk_groth16_deal_masks replaces: six zk_fft_mask_sample, one zk_degred_mask_sample, five
+    zk_msm_mask_sample (ProofMasks before the batched dealer), written into the preallocated buffers of `pm` -- no
+    allocation, no root-of-unity power and no generator encoding inside, as for the batched call it is compared with.
+    w2m: the encoded 2m-th root of unity."""
+    lib, h = pp.lib, pp.h
+    for k in range(6):
+        pp._check(lib.zk_fft_mask_sample(h, int(k < 3), w2m.ctypes.data if k < 3 else None, int(k < 3), log_m, seed + k,
+                                         pm.fft[k].in_mask.ptr, pm.fft[k].out_mask.ptr, None))
+    pp._check(lib.zk_degred_mask_sample(h, (1 << log_m) // pp.l, seed + 6, pm.degred.in_mask.ptr, pm.degred.out_mask.ptr, None))
+    twelve_call_msm(pp, seed, g1, g2, pm)
+
+
+def twelve_call_msm(pp, seed, g1, g2, pm):
+    for k in range(5):
+        pp._check(pp.lib.zk_msm_mask_sample(pp.h, api.ZK_G2 if k == 2 else api.ZK_G1, (g2 if k == 2 else g1).ctypes.data, seed + 7 + k,
+                                            pm.msm[k].in_mask.ctypes.data, pm.msm[k].out_mask.ctypes.data))
+
+
+def proof_masks_entry(pp, reps):
+    import ctypes as C
+    log_m = 15
+    g1, g2 = (np.ascontiguousarray(g, dtype=np.uint64).reshape(-1) for g in zg.generators(pp))
+    w2m = pp.fr.encode_one(zg._root_of_unity(pp.curve, log_m + 1))
+    out = {"log_m": log_m}
+    old_pm = zg.ProofMasks.__new__(zg.ProofMasks)
+    old_pm._alloc(pp, log_m)
+    out["twelve_calls"] = ms3(timed_spread(pp, lambda: twelve_call_masks(pp, log_m, 77, g1, g2, old_pm, w2m), reps))
+    for nb in (1, 8):
+        sets, arr = [], (zg.Masks * nb)()
+        for b in range(nb):
+            pm = zg.ProofMasks.__new__(zg.ProofMasks)
+            pm._alloc(pp, log_m)
+            C.memmove(C.byref(arr, b * C.sizeof(zg.Masks)), C.byref(pm.ct), C.sizeof(zg.Masks))
+            sets.append(pm)
+        t = timed_spread(pp, lambda: api.deal_masks(pp, nb, log_m, g1, g2, 77, arr), reps)
+        e = ms3(t, nb)
+        e["mask_sets_per_s"] = round(nb / t[0], 1)
+        out["deal_b%d" % nb] = e
+        if nb == 8:                                   # the MsmMask part alone: only the MSM slots set
+            for b in range(nb):
+                for k in range(6):
+                    arr[b].fft_in[k] = arr[b].fft_out[k] = None
+                arr[b].degred_in = arr[b].degred_out = None
+            t = timed_spread(pp, lambda: api.deal_masks(pp, nb, log_m, g1, g2, 77, arr), reps)
+            out["msm_mask_device_b8"] = ms3(t, nb)
+        else:
+            one = zg.Masks()
+            C.memmove(C.byref(one), C.byref(arr[0]), C.sizeof(one))
+            for k in range(6):
+                one.fft_in[k] = one.fft_out[k] = None
+            one.degred_in = one.degred_out = None
+            out["msm_mask_device_b1"] = ms3(timed_spread(pp, lambda: api.deal_masks(pp, 1, log_m, g1, g2, 77, one), reps))
+        del sets
+    out["msm_mask_host"] = ms3(timed_spread(pp, lambda: twelve_call_msm(pp, 77, g1, g2, old_pm), reps))
+    out["speedup_b1"] = round(out["twelve_calls"]["ms"] / out["deal_b1"]["ms"], 2)
+    out["speedup_b8"] = round(out["twelve_calls"]["ms"] / out["deal_b8"]["ms"], 2)
+    # the pass condition: one call beats the twelve by more than the spread of the repetitions (slowest repetition of the
+    # one against the fastest of the twelve), and a set of a batch of 8 costs no more than a set dealt alone
+    out["b1_faster_beyond_spread"] = out["deal_b1"]["max_ms"] < out["twelve_calls"]["min_ms"]
+    out["b8_no_dearer_than_b1"] = out["deal_b8"]["ms"] <= out["deal_b1"]["ms"]
+    return out
+
+
+def witness_deal_entry(pp, reps):
+    from zksaas_amd import circom
+    from zksaas_amd import sha256_circuit as sc
+    r1, w = sc.build(1, 2, pp.fr.p)
+    dev = circom.DeviceR1cs(pp, r1)
+    w_d = pp.upload_fr(w)
+    ni = r1.num_instance_variables
+
+    def old():
+        m = 1 << dev.log_m
+        for k, d in enumerate(dev.qap(w_d)):
+            pp._check(pp.lib.zk_bitrev(pp.h, d.ptr, dev.log_m, None))
+            pp.pack(d, m // pp.l, 5 + k, order=1)
+        wl = pp.download_fr(w_d, r1.num_variables)
+        for vals, sd in ((wl[1:], 8), (wl[ni:], 9)):
+            vals = list(vals)
+            vals += [0] * (-len(vals) % pp.l)
+            pp.pack(pp.upload_fr(vals), len(vals) // pp.l, sd)
+    return {"circuit": "sha256", "log_m": dev.log_m, "num_variables": r1.num_variables,
+            "r1cs_qap_bitrev_pack_python_padding": ms3(timed_spread(pp, old, max(2, reps // 2))),
+            "deal_witness": ms3(timed_spread(pp, lambda: zg.Witness(pp, pp.curve, r1, w_d, 5, dev_r1cs=dev), reps))}
 
 
 def entry(dt, units, unit_name, products_per_unit, limbs, **extra):
@@ -146,6 +258,9 @@ def run(curve, quick, reps):
     gen = zg._affine_codec(pp, list(zg.G1_GEN[pp.curve]), False)
     dt = timed(pp, lambda: zk.MsmMask.sample(pp, api.ZK_G1, gen, 11), reps)
     out["msm_mask_sample_g1"] = {"ms": round(dt * 1e3, 4)}
+    out["proof_masks"] = proof_masks_entry(pp, max(reps, 9))
+    if curve == "bn254":                              # (the SHA-256 circuit is built over BN254's scalar field)
+        out["witness_deal"] = witness_deal_entry(pp, reps)
     return out
 
 

@@ -242,6 +242,32 @@ class MsmMask:
         return MsmMask(im, om)
 
 
+BASE_MUL_FEW_MAX = 4096       # zk_base_mul_few's bound on the number of scalars (zk_base_mul above it)
+
+
+def base_mul_few(pp, group, base_affine, scalars_d, length, out=None, stream=None):
+    """zk_base_mul_few: scalars_d[i] * base for a FEW scalars (at most BASE_MUL_FEW_MAX), a group of lanes per scalar;
+    base_affine: Montgomery limbs of an affine point (host).  Returns a DeviceBuffer of `length` Jacobian points."""
+    nl = pp.fq.nl * (2 if group == ZK_G2 else 1)
+    base = np.ascontiguousarray(base_affine, dtype=np.uint64).reshape(-1)
+    if base.size != 2 * nl:
+        raise ValueError("base must be an affine point (%d limbs)" % (2 * nl))
+    out = out or DeviceBuffer(pp, max(1, length) * 3 * nl * 8)
+    pp._check(pp.lib.zk_base_mul_few(pp.h, group, base.ctypes.data, _ptr(scalars_d), length, _ptr(out), stream))
+    return out
+
+
+def deal_masks(pp, nproofs, log2_m, g1_gen_affine, g2_gen_affine, seed, masks_ct, stream=None):
+    """zk_groth16_deal_masks: fills the destination buffers named by `masks_ct` (a ctypes array of nproofs
+    zk_groth16_masks, or one struct when nproofs == 1) with the twelve masks of every proof; proof b is dealt what the
+    single samplers deal with seed + 16 b (replay mode).  A slot with two NULL pointers is skipped.  Returns with the
+    host points written and the device masks ordered on `stream`."""
+    g1 = None if g1_gen_affine is None else np.ascontiguousarray(g1_gen_affine, dtype=np.uint64).reshape(-1)
+    g2 = None if g2_gen_affine is None else np.ascontiguousarray(g2_gen_affine, dtype=np.uint64).reshape(-1)
+    pp._check(pp.lib.zk_groth16_deal_masks(pp.h, nproofs, log2_m, None if g1 is None else g1.ctypes.data,
+                                           None if g2 is None else g2.ctypes.data, seed, C.byref(masks_ct), stream))
+
+
 def d_fft(pp, shares_d, fft_mask, rearrange, log2_m, seed=0, out=None, stream=None):
     """dfft/mod.rs:99-134 for all parties; shares_d [n][m/l].  Result in `out` (or back in shares_d if None)."""
     pp._check(pp.lib.zk_d_fft(pp.h, _ptr(shares_d), _ptr(fft_mask.in_mask), _ptr(fft_mask.out_mask), int(rearrange),

@@ -776,6 +776,26 @@ int zk_base_mul(zk_ctx* ctx, int group, const void* base_affine, const void* sca
   CTX_OR_FAIL();
   return e->base_mul(group, base_affine, scalars_d, len, out_affine_d, S(stream));
 }
+int zk_base_mul_few(zk_ctx* ctx, int group, const void* base_affine, const void* scalars_d, size_t len,
+                    void* out_jacobian_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->base_mul_few(group, base_affine, scalars_d, len, out_jacobian_d, S(stream));
+}
+int zk_groth16_deal_masks(zk_ctx* ctx, int nproofs, int log2_m, const void* g1_gen_affine, const void* g2_gen_affine,
+                          uint64_t seed, const zk_groth16_masks* masks, void* stream) {
+  CTX_OR_FAIL();
+  return e->groth16_deal_masks(nproofs, log2_m, g1_gen_affine, g2_gen_affine, seed, masks, S(stream));
+}
+int zk_groth16_deal_witness(zk_ctx* ctx, const void* a_row_ptr_d, const void* a_col_d, const void* a_val_d,
+                            const void* b_row_ptr_d, const void* b_col_d, const void* b_val_d, const void* w_d,
+                            size_t num_variables, size_t num_constraints, size_t num_instance, int log_m, uint64_t seed,
+                            void* qap_a_d, void* qap_b_d, void* qap_c_d, void* a_share_d, void* ax_share_d, size_t* len_a,
+                            size_t* len_w, void* stream) {
+  CTX_OR_FAIL();
+  return e->groth16_deal_witness(a_row_ptr_d, a_col_d, a_val_d, b_row_ptr_d, b_col_d, b_val_d, w_d, num_variables,
+                                 num_constraints, num_instance, log_m, seed, qap_a_d, qap_b_d, qap_c_d, a_share_d,
+                                 ax_share_d, len_a, len_w, S(stream));
+}
 int zk_circom_h(zk_ctx* ctx, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
                 const zk_groth16_masks* masks, uint64_t seed, void* h_d, void* stream) {
   CTX_OR_FAIL();

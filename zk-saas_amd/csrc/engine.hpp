@@ -374,6 +374,14 @@ class IEngine {
   virtual int pss_pack_points(int group, const void* points, size_t nchunks, int nv, void* shares, hipStream_t st) = 0;
   virtual int base_mul(int group, const void* base_affine, const void* scalars, size_t len, void* out_affine,
                        hipStream_t st) = 0;
+  virtual int base_mul_few(int group, const void* base_affine, const void* scalars, size_t len, void* out_jacobian,
+                           hipStream_t st) = 0;
+  virtual int groth16_deal_masks(int nproofs, int log_m, const void* g1_gen_affine, const void* g2_gen_affine,
+                                 uint64_t seed, const zk_groth16_masks* masks, hipStream_t st) = 0;
+  virtual int groth16_deal_witness(const void* pa, const void* ca, const void* va, const void* pb, const void* cb,
+                                   const void* vb, const void* w, size_t nvars, size_t nc, size_t ni, int log_m,
+                                   uint64_t seed, void* qa, void* qb, void* qc, void* a_share, void* ax_share,
+                                   size_t* len_a, size_t* len_w, hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,

@@ -12,6 +12,24 @@
     ZK_HIP(hipGetLastError());
     return ZK_OK;
   }
+  // pack (order 0) of `count` secrets padded with zeros to nchunks * l
+  template <int L>
+  int pack_count_l(const Fr* sec, size_t count, size_t nch, uint64_t seed, Fr* shares, hipStream_t st) {
+    dim3 grid((unsigned)((nch + KING_THREADS - 1) / KING_THREADS)), block(KING_THREADS);
+    pss_pack_count_kernel<FrP, L><<<grid, block, 0, st>>>(sec, count, nch, rs(seed), pmat_, pack2_, shares);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+  }
+  int pss_pack_count(const Fr* sec, size_t count, uint64_t seed, Fr* shares, hipStream_t st) {
+    const size_t nch = (count + l - 1) / l;
+    if (!nch) return ZK_OK;
+    switch (l) {
+      case 1: return pack_count_l<1>(sec, count, nch, seed, shares, st);
+      case 2: return pack_count_l<2>(sec, count, nch, seed, shares, st);
+      case 4: return pack_count_l<4>(sec, count, nch, seed, shares, st);
+      default: return pack_count_l<8>(sec, count, nch, seed, shares, st);
+    }
+  }
   int pss_pack(const void* secrets, size_t nchunks, int order, uint64_t seed, bool det, void* shares,
                hipStream_t st) override {
     if (nchunks == 0) return ZK_OK;

@@ -974,6 +974,194 @@
     return fail(ZK_ERR_BAD_INPUT, "bad group");
   }
 
+  // ---------------------------------------------------------------- zk_groth16_deal_masks
+  // All twelve masks of `nproofs` proofs (sha256.rs:226-291), in passes of up to DEAL_BATCH proofs (deal_pass_size) of
+  // eight launches each, whatever the pass holds.  The five MsmMasks take three -- deal_msm_scalars_kernel, then
+  // base_mul_few_kernel once over the G1 and once over the G2 share scalars -- and go to the caller's host buffers through
+  // pinned staging while the five launches of the FFT and deg_red masks (deal_fr_masks_l) run on the same stream.
+  static constexpr int DEAL_BATCH = DEGRED_BATCH;
+  static constexpr size_t DEAL_WS_BYTES = (size_t)1 << 30;     // cap on the FFT masks' working memory per pass
+  // proofs per pass: DEAL_BATCH (the batch limit of the king / deg_red kernels), fewer when 30 nb m elements of working
+  // memory (the value vectors [l][6 nb][m/l] and the kings' output [n][6 nb][m/l]) would pass DEAL_WS_BYTES
+  int deal_pass_size(int log_m) const {
+    const size_t per_proof = (size_t)6 * (l + n) * (((size_t)1 << log_m) / l) * sizeof(Fr);
+    return (int)std::max<size_t>(1, std::min<size_t>(DEAL_BATCH, DEAL_WS_BYTES / per_proof));
+  }
+  template <int L>
+  int deal_fr_masks_l(int nb, int log_m, uint64_t seed, const zk_groth16_masks* mk, hipStream_t st) {
+    const int log_lc = log_m - ilog2(l);
+    const size_t Lc = (size_t)1 << log_lc;
+    const uint32_t items = 6 * (uint32_t)nb;
+    DealFftArg<Fr> fa{};
+    DealDegredArg<Fr> da{};
+    bool any_fft = false, any_dr = false;
+    for (int b = 0; b < nb; b++) {
+      for (int k = 0; k < 6; k++) {
+        const int y = (k / 3) * 3 * nb + 3 * b + k % 3;
+        fa.in_mask[y] = (Fr*)mk[b].fft_in[k];
+        fa.out_mask[y] = (Fr*)mk[b].fft_out[k];
+        any_fft = any_fft || fa.in_mask[y];
+      }
+      da.in_mask[b] = (Fr*)mk[b].degred_in;
+      da.out_mask[b] = (Fr*)mk[b].degred_out;
+      any_dr = any_dr || da.in_mask[b];
+    }
+    const unsigned kt = (unsigned)KING_THREADS;
+    if (any_fft) {
+      DevBuf& hwork_ = ws(st)->hwork;
+      ZK_HIP(hwork_.ensure((size_t)items * (l + n) * Lc * sizeof(Fr)));
+      Fr* vals = (Fr*)hwork_.p;                       // [l][items][Lc]
+      Fr* kout = vals + (size_t)items * l * Lc;       // [n][items][Lc]
+      deal_fft_fill_pack_kernel<FrP, L><<<dim3((unsigned)((Lc + kt - 1) / kt), items), dim3(kt), 0, st>>>(
+          fa, (uint32_t)nb, (uint32_t)log_lc, rs(seed, 2ull * items), pmat_, pack2_, vals);
+      ZK_HIP(hipGetLastError());
+      const Fr w2m = root_of_unity(log_m + 1);
+      for (int cfg = 0; cfg < 2; cfg++) {
+        KingBatch<Fr> kb{};
+        kb.stride = Lc;
+        kb.row_pitch = (size_t)items * Lc;
+        kb.items_per = 3;
+        kb.seed_step = 16;
+        kb.seed_xor = rng_replay_ ? 0x2222ull : 0ull;
+        const size_t off = (size_t)cfg * 3 * nb * Lc;
+        int rc = king_dispatch_batch(vals + off, kb, 3 * nb, l, log_m, cfg == 0, ident_, cfg == 0 ? &w2m : nullptr, 0,
+                                     cfg == 0, seed + 3 * cfg, kout + off, true, st);
+        if (rc) return rc;
+      }
+      deal_fft_scatter_kernel<Fr><<<dim3((unsigned)(((size_t)n * Lc + 255) / 256), items), dim3(256), 0, st>>>(kout, fa, items, Lc,
+                                                                                                           (uint32_t)n);
+      ZK_HIP(hipGetLastError());
+    }
+    if (any_dr) {
+      deal_degred_kernel<FrP, L><<<dim3((unsigned)((Lc + kt - 1) / kt), (unsigned)nb), dim3(kt), 0, st>>>(
+          da, Lc, rs(seed, 3ull * nb), pmat_, pack2_);
+      ZK_HIP(hipGetLastError());
+    }
+    return ZK_OK;
+  }
+  int deal_masks_chunk(int nb, int log_m, const void* g1_gen, const void* g2_gen, uint64_t seed, const zk_groth16_masks* mk,
+                       hipStream_t st) {
+    using Fq = Fp<typename Cfg::FqP>;
+    using Fq2 = Fp2<typename Cfg::FqP>;
+    using J1 = Jacobian<Fq>;
+    using J2 = Jacobian<Fq2>;
+    bool any1 = false, any2 = false;
+    for (int b = 0; b < nb; b++)
+      for (int k = 0; k < 5; k++)
+        if (mk[b].msm_in[k]) (k == 2 ? any2 : any1) = true;
+    StreamWs* w_ = ws(st);
+    const size_t per = (size_t)nb * 2 * n;                     // share scalars (= points) of one mask slot over the chunk
+    const size_t sc_bytes = 5 * per * sizeof(Fr), p1_bytes = 4 * per * sizeof(J1), p2_bytes = per * sizeof(J2);
+    if (any1 || any2) {
+      ZK_HIP(w_->deal.ensure(sc_bytes + p1_bytes + p2_bytes));
+      if (w_->deal_pin_bytes < p1_bytes + p2_bytes) {
+        if (w_->deal_pin) (void)hipHostFree(w_->deal_pin);
+        w_->deal_pin = nullptr, w_->deal_pin_bytes = 0;
+        ZK_HIP(hipHostMalloc(&w_->deal_pin, p1_bytes + p2_bytes, hipHostMallocDefault));
+        w_->deal_pin_bytes = p1_bytes + p2_bytes;
+      }
+      if (!w_->deal_ev) ZK_HIP(hipEventCreateWithFlags(&w_->deal_ev, hipEventDisableTiming));
+      Fr* sc = (Fr*)w_->deal.p;
+      char* pts = (char*)w_->deal.p + sc_bytes;
+      const unsigned total = (unsigned)(5 * per);
+      deal_msm_scalars_kernel<FrP><<<dim3((total + 63) / 64), dim3(64), 0, st>>>(rs(seed, 15ull * (uint64_t)nb), nb, l, t, n,
+                                                                                pmat_, sc);
+      ZK_HIP(hipGetLastError());
+      if (any1) {
+        int rc = base_mul_few_t<Fq>(g1_gen, sc, 4 * per, pts, st);
+        if (rc) return rc;
+        ZK_HIP(hipMemcpyAsync(w_->deal_pin, pts, p1_bytes, hipMemcpyDeviceToHost, st));
+      }
+      if constexpr (Cfg::HAS_G2) {
+        if (any2) {
+          int rc = base_mul_few_t<Fq2>(g2_gen, sc + 4 * per, per, pts + p1_bytes, st);
+          if (rc) return rc;
+          ZK_HIP(hipMemcpyAsync((char*)w_->deal_pin + p1_bytes, pts + p1_bytes, p2_bytes, hipMemcpyDeviceToHost, st));
+        }
+      }
+      ZK_HIP(hipEventRecord(w_->deal_ev, st));
+    }
+    // the Fr masks of the chunk: one draw + pack launch for the 6 nb FFT value vectors and in-masks, one king launch per
+    // configuration (k < 3: the d_ifft with the coset shift w_2m and rearranged output; k >= 3: the plain d_fft) over 3 nb
+    // items, one launch that hands the kings' output to the callers' out-mask buffers, one launch for the DegRedMasks
+    int rc = 0;
+    switch (l) {
+      case 1: rc = deal_fr_masks_l<1>(nb, log_m, seed, mk, st); break;
+      case 2: rc = deal_fr_masks_l<2>(nb, log_m, seed, mk, st); break;
+      case 4: rc = deal_fr_masks_l<4>(nb, log_m, seed, mk, st); break;
+      default: rc = deal_fr_masks_l<8>(nb, log_m, seed, mk, st); break;
+    }
+    if (rc) return rc;
+    if (any1 || any2) {
+      ZK_HIP(hipEventSynchronize(w_->deal_ev));
+      for (int kk = 0; kk < 5; kk++) {
+        const int k = deal_msm_slot(kk);
+        const size_t psz = k == 2 ? sizeof(J2) : sizeof(J1);
+        const char* src = (const char*)w_->deal_pin + (k == 2 ? p1_bytes : (size_t)kk * per * sizeof(J1));
+        for (int b = 0; b < nb; b++) {
+          if (!mk[b].msm_in[k]) continue;
+          memcpy((void*)mk[b].msm_in[k], src + (size_t)(2 * b) * n * psz, (size_t)n * psz);
+          memcpy((void*)mk[b].msm_out[k], src + (size_t)(2 * b + 1) * n * psz, (size_t)n * psz);
+        }
+      }
+    }
+    return ZK_OK;
+  }
+  int groth16_deal_masks(int nproofs, int log_m, const void* g1_gen, const void* g2_gen, uint64_t seed,
+                         const zk_groth16_masks* mk, hipStream_t st) override {
+    if (nproofs < 1 || !mk) return fail(ZK_ERR_BAD_INPUT, "zk_groth16_deal_masks: nproofs < 1 or null masks");
+    if (log_m < ilog2(l) || log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    for (int b = 0; b < nproofs; b++) {
+      const zk_groth16_masks& m = mk[b];
+      bool half = (m.degred_in != nullptr) != (m.degred_out != nullptr);
+      for (int k = 0; k < 6; k++) half = half || (m.fft_in[k] != nullptr) != (m.fft_out[k] != nullptr);
+      for (int k = 0; k < 5; k++) half = half || (m.msm_in[k] != nullptr) != (m.msm_out[k] != nullptr);
+      if (half) return fail(ZK_ERR_BAD_INPUT, "zk_groth16_deal_masks: a mask slot needs both pointers or none");
+      for (int k = 0; k < 5; k++) {
+        if (!m.msm_in[k]) continue;
+        if (k == 2 && (!Cfg::HAS_G2 || !g2_gen)) return fail(ZK_ERR_BAD_INPUT, "zk_groth16_deal_masks: no G2 generator for the G2 mask");
+        if (k != 2 && !g1_gen) return fail(ZK_ERR_BAD_INPUT, "zk_groth16_deal_masks: no G1 generator");
+      }
+    }
+    const int pass = deal_pass_size(log_m);
+    for (int b0 = 0; b0 < nproofs; b0 += pass) {
+      int rc = deal_masks_chunk(std::min(pass, nproofs - b0), log_m, g1_gen, g2_gen, seed + 16ull * (uint64_t)b0, mk + b0, st);
+      if (rc) return rc;
+    }
+    return ZK_OK;
+  }
+
+  // ---------------------------------------------------------------- zk_groth16_deal_witness
+  // QAP::pss (qap.rs:91-135) and the two pack_from_witness (sha256.rs:131-156) from a device-resident witness: r1cs_qap,
+  // bit reversal and pack at order 1 with seeds + 0, 1, 2, then w[1:] (seed + 3) and w[ni:] (seed + 4) packed straight from
+  // w_d with a zero tail.  With all five outputs NULL only the two chunk counts are returned.
+  int groth16_deal_witness(const void* pa, const void* ca, const void* va, const void* pb, const void* cb, const void* vb,
+                           const void* w, size_t nvars, size_t nc, size_t ni, int log_m, uint64_t seed, void* qa, void* qb,
+                           void* qc, void* a_share, void* ax_share, size_t* len_a, size_t* len_w, hipStream_t st) override {
+    if (nvars < 1 || ni < 1 || ni > nvars) return fail(ZK_ERR_BAD_INPUT, "bad R1CS dimensions");
+    const size_t la = (nvars - 1 + l - 1) / l, lw = (nvars - ni + l - 1) / l;
+    if (len_a) *len_a = la;
+    if (len_w) *len_w = lw;
+    if (!qa && !qb && !qc && !a_share && !ax_share) return ZK_OK;          // size query
+    if (!qa || !qb || !qc || (la && !a_share) || (lw && !ax_share) || !w) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (log_m < ilog2(l) || log_m > 30) return fail(ZK_ERR_BAD_INPUT, "bad domain size");
+    const size_t m = (size_t)1 << log_m;
+    DevBuf& hwork_ = ws(st)->hwork;
+    ZK_HIP(hwork_.ensure(3 * m * sizeof(Fr)));
+    Fr* abc = (Fr*)hwork_.p;
+    int rc = r1cs_qap(pa, ca, va, pb, cb, vb, w, nvars, nc, ni, log_m, abc, abc + m, abc + 2 * m, st);
+    if (rc) return rc;
+    void* const q[3] = {qa, qb, qc};
+    for (int k = 0; k < 3; k++) {
+      rc = bitrev(abc + k * m, log_m, st);
+      if (!rc) rc = pss_pack(abc + k * m, m / l, 1, seed + k, false, q[k], st);
+      if (rc) return rc;
+    }
+    rc = pss_pack_count((const Fr*)w + 1, nvars - 1, seed + 3, (Fr*)a_share, st);
+    if (rc) return rc;
+    return pss_pack_count((const Fr*)w + ni, nvars - ni, seed + 4, (Fr*)ax_share, st);
+  }
+
   // ---------------------------------------------------------------- libsnark_h (ext_wit.rs:14-102)
   // 3 x d_ifft with the coset shift g = F::GENERATOR (rearranged) -> 3 x d_fft (rearranged) -> (a*b - c) / Z(g) ->
   // d_ifft with g^-1.  Seven masks (or NULL arrays for FftMask::zero).

@@ -435,8 +435,16 @@ class Engine : public IEngine {
   struct StreamWs {
     DevBuf scratch, king_tmp, hwork;
     int* err = nullptr;
+    // zk_groth16_deal_masks: share scalars and mask points on the device, the points' pinned staging copy and the event
+    // that marks its arrival
+    DevBuf deal;
+    void* deal_pin = nullptr;
+    size_t deal_pin_bytes = 0;
+    hipEvent_t deal_ev = nullptr;
     ~StreamWs() {
       if (err) (void)hipFree(err);
+      if (deal_pin) (void)hipHostFree(deal_pin);
+      if (deal_ev) (void)hipEventDestroy(deal_ev);
     }
   };
   std::mutex ws_mu_;

@@ -16,10 +16,9 @@
 
   // ---------------------------------------------------------------- fixed-base multiplication (dealer)
   static constexpr size_t BASE_MUL_WIDE_FROM = (size_t)1 << 19;      // scalars per call from which 16-bit windows pay
+  // the 8-bit table of a base, table[w][d-1] = d * 256^w * Base, built on the host once per base and kept
   template <class Fld>
-  int base_mul_t(const void* base_affine, const void* scalars, size_t len, void* out_affine, hipStream_t st) {
-    if (!len) return ZK_OK;
-    if (!base_affine || !scalars || !out_affine) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+  int base_table8(const void* base_affine, Affine<Fld>** out) {
     const int nwin = (FrP::BITS + 7) / 8;
     std::string key((const char*)base_affine, sizeof(Affine<Fld>));
     Affine<Fld>* table = nullptr;
@@ -29,7 +28,6 @@
       if (it != base_tables_.end()) table = (Affine<Fld>*)it->second;
     }
     if (!table) {
-      // table[w][d-1] = d * 256^w * Base, built on the host
       Affine<Fld> base;
       memcpy(&base, base_affine, sizeof(base));
       std::vector<Affine<Fld>> h((size_t)nwin * 255);
@@ -45,8 +43,24 @@
       ZK_HIP(hipMalloc((void**)&table, h.size() * sizeof(Affine<Fld>)));
       ZK_HIP(hipMemcpy(table, h.data(), h.size() * sizeof(Affine<Fld>), hipMemcpyHostToDevice));
       std::lock_guard<std::mutex> lk(mu_);
-      base_tables_[key] = table;
+      auto ins = base_tables_.emplace(key, table);
+      if (!ins.second) {                 // another thread built the same table meanwhile: keep the first
+        (void)hipFree(table);
+        table = (Affine<Fld>*)ins.first->second;
+      }
     }
+    *out = table;
+    return ZK_OK;
+  }
+  template <class Fld>
+  int base_mul_t(const void* base_affine, const void* scalars, size_t len, void* out_affine, hipStream_t st) {
+    if (!len) return ZK_OK;
+    if (!base_affine || !scalars || !out_affine) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    const int nwin = (FrP::BITS + 7) / 8;
+    std::string key((const char*)base_affine, sizeof(Affine<Fld>));
+    Affine<Fld>* table = nullptr;
+    int trc = base_table8<Fld>(base_affine, &table);
+    if (trc) return trc;
     if (len >= BASE_MUL_WIDE_FROM) {
       // 16-bit windows (half the mixed additions per scalar), widened on the device from the 8-bit table once per base
       const int nwin16 = (nwin + 1) / 2;
@@ -86,6 +100,29 @@
     if (group == ZK_G1) return base_mul_t<Fq>(base_affine, scalars, len, out_affine, st);
     if (group == ZK_G2) {
       if constexpr (Cfg::HAS_G2) return base_mul_t<Fq2>(base_affine, scalars, len, out_affine, st);     // (quad-split kernel: G2 units only)
+      else return fail(ZK_ERR_BAD_INPUT, "G2 is not available for this curve");
+    }
+    return fail(ZK_ERR_BAD_INPUT, "group must be ZK_G1 or ZK_G2");
+  }
+  // zk_base_mul_few: a group of lanes per scalar (base_mul_few.hpp), Jacobian output, at most FEW_MAX_LEN scalars
+  template <class Fld>
+  int base_mul_few_t(const void* base_affine, const void* scalars, size_t len, void* out_jac, hipStream_t st) {
+    if (len > FEW_MAX_LEN)
+      return fail(ZK_ERR_BAD_INPUT, "zk_base_mul_few takes at most " + std::to_string(FEW_MAX_LEN) + " scalars (use zk_base_mul)");
+    if (!len) return ZK_OK;
+    if (!base_affine || !scalars || !out_jac) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    Affine<Fld>* table = nullptr;
+    int rc = base_table8<Fld>(base_affine, &table);
+    if (rc) return rc;
+    return base_mul_few_launch<FrP, Fld>(this, scalars, len, table, (FrP::BITS + 7) / 8, out_jac, st);
+  }
+  int base_mul_few(int group, const void* base_affine, const void* scalars, size_t len, void* out_jac,
+                   hipStream_t st) override {
+    using Fq = Fp<typename Cfg::FqP>;
+    using Fq2 = Fp2<typename Cfg::FqP>;
+    if (group == ZK_G1) return base_mul_few_t<Fq>(base_affine, scalars, len, out_jac, st);
+    if (group == ZK_G2) {
+      if constexpr (Cfg::HAS_G2) return base_mul_few_t<Fq2>(base_affine, scalars, len, out_jac, st);
       else return fail(ZK_ERR_BAD_INPUT, "G2 is not available for this curve");
     }
     return fail(ZK_ERR_BAD_INPUT, "group must be ZK_G1 or ZK_G2");

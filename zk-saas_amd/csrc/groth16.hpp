@@ -160,6 +160,46 @@ __global__ __launch_bounds__(128) void pss_pack_points_jsf_kernel(const Affine<F
   store_elem(shares + t, xyzz_to_affine(acc));
 }
 
+// Share scalars of the MSM masks of a batch of proofs (zk_groth16_deal_masks; MsmMask::sample, dmsm/mod.rs:21-47, in the
+// scalar form of Engine::msm_mask_sample_t): out[((kk * nproofs + b) * 2 + io) * n + p] = sum_j P[p][j] sec[j], with
+// sec = (x_0..x_{l-1} | t randoms) for the in-mask (io = 0) and (-(sum x) l times | t randoms) for the out-mask.  kk walks
+// the masks in the order 0, 1, 3, 4, 2, so the G1 scalars are contiguous and the G2 mask comes last.  One lane per share.
+// Replay stream (key == nullptr): mask k of proof b draws from seed + 16 b + 7 + k, ^ 0x1111 and ^ 0x2222, as the single
+// calls do; production stream: the three nonces base + 3 (5 b + k) + {0, 1, 2} (the caller reserved 15 nproofs of them).
+ZK_HD constexpr int deal_msm_slot(int kk) { return kk < 2 ? kk : (kk < 4 ? kk + 1 : 2); }
+template <class FrP>
+__global__ __launch_bounds__(64) void deal_msm_scalars_kernel(RngSeed base, int nproofs, int l, int t, int n,
+                                                             const Fp<FrP>* __restrict__ Pm, Fp<FrP>* __restrict__ out) {
+  using F = Fp<FrP>;
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (uint32_t)(5 * nproofs * 2 * n)) return;
+  const int p = (int)(idx % (uint32_t)n), io = (int)((idx / (uint32_t)n) & 1u);
+  const int b = (int)((idx / (uint32_t)(2 * n)) % (uint32_t)nproofs), k = deal_msm_slot((int)(idx / (uint32_t)(2 * n * nproofs)));
+  RngSeed r0, r1, r2;
+  if (!base.key) {
+    const uint64_t s = base.seed + 16ull * (uint64_t)b + 7ull + (uint64_t)k;
+    r0 = RngSeed{s, nullptr}, r1 = RngSeed{s ^ 0x1111ull, nullptr}, r2 = RngSeed{s ^ 0x2222ull, nullptr};
+  } else {
+    const uint64_t nn = base.seed + 3ull * (uint64_t)(5 * b + k);
+    r0 = RngSeed{nn, base.key}, r1 = RngSeed{nn + 1, base.key}, r2 = RngSeed{nn + 2, base.key};
+  }
+  const F* row = Pm + (size_t)p * (l + t);
+  F acc = F::zero();
+  if (io == 0) {
+    for (int j = 0; j < l; j++) acc = acc + load_elem(row + j) * rand_fp<FrP>(r0, (uint64_t)j);
+  } else {
+    F sum = F::zero(), coef = F::zero();
+    for (int j = 0; j < l; j++) {
+      sum = sum + rand_fp<FrP>(r0, (uint64_t)j);
+      coef = coef + load_elem(row + j);
+    }
+    acc = coef * sum.neg();
+  }
+  const RngSeed rr = io ? r2 : r1;
+  for (int j = 0; j < t; j++) acc = acc + load_elem(row + l + j) * rand_fp<FrP>(rr, (uint64_t)j);
+  store_elem(out + idx, acc);
+}
+
 #endif  // __HIPCC__
 
 // Host-side scalar multiplication k * P (k in Montgomery form), plain double-and-add over XYZZ.

@@ -34,6 +34,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "base_mul_few_map.hpp"
 #include "ec.hpp"
 #include "engine.hpp"
 #include "msm_plan.hpp"
@@ -1568,6 +1569,10 @@ int pack_points_split_launch(IEngine* eng, const void* points, size_t nchunks, i
 template <class FrP, class Fld>
 int base_mul_split_launch(IEngine* eng, const void* scalars, size_t len, const void* table, int nwin, int wb, void* out,
                           hipStream_t st);
+// fixed-base multiplication of a few scalars, a group of lanes per scalar (base_mul_few.hpp; G1 and G2); table: the 8-bit
+// table of Engine::base_mul_t, out: len Jacobian points (device)
+template <class FrP, class Fld>
+int base_mul_few_launch(IEngine* eng, const void* scalars, size_t len, const void* table, int nwin, void* out, hipStream_t st);
 // zk_msm_precompute's table kernel (same translation units)
 template <class FrP, class Fld>
 int msm_table_launch(IEngine* eng, const void* bases, size_t len, int c, int nwin, int wide, void* table,

@@ -2,6 +2,7 @@
 // translation units, each of which instantiates them for one (scalar field, coordinate field) pair: the Pippenger
 // kernels are the most expensive part of the build and compile in parallel this way.
 #pragma once
+#include "base_mul_few.hpp"
 #include "msm.hpp"
 #include "pack_split.hpp"
 
@@ -349,11 +350,24 @@ int base_mul_split_launch(IEngine* eng, const void* scalars, size_t len, const v
   }
 }
 
+template <class FrP, class Fld>
+int base_mul_few_launch(IEngine* eng, const void* scalars, size_t len, const void* table, int nwin, void* out, hipStream_t st) {
+  using KF = typename KernelField<Fld>::type;
+  if (!len) return ZK_OK;
+  if (len > FEW_MAX_LEN || nwin > FEW_MAX_WIN) return eng->fail(ZK_ERR_BAD_INPUT, "base_mul_few: too many scalars or windows");
+  base_mul_few_kernel<FrP, KF><<<dim3((unsigned)few_blocks(len)), dim3(FEW_BLOCK), 0, st>>>(
+      (const Fp<FrP>*)scalars, len, (const Affine<KF>*)table, nwin, (Jacobian<KF>*)out);
+  hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return eng->hip_fail(he, "base_mul_few_kernel");
+  return ZK_OK;
+}
+
 #define ZK_INSTANTIATE_MSM(FRP, FLD)                                                                              \
   template int msm_launch<FRP, FLD>(IEngine*, MsmSlot&, const MsmTuning&, const void*, const void*, const void*, \
                                     size_t, const Fp<FRP>*, size_t, hipStream_t, MsmPending*, const MsmBatchArg*);  \
   template int msm_table_launch<FRP, FLD>(IEngine*, const void*, size_t, int, int, int, void*, hipStream_t);     \
   template int pack_points_split_launch<FRP, FLD>(IEngine*, const void*, size_t, int, const uint8_t*, int, const void*, void*, hipStream_t); \
-  template int base_mul_split_launch<FRP, FLD>(IEngine*, const void*, size_t, const void*, int, int, void*, hipStream_t);
+  template int base_mul_split_launch<FRP, FLD>(IEngine*, const void*, size_t, const void*, int, int, void*, hipStream_t); \
+  template int base_mul_few_launch<FRP, FLD>(IEngine*, const void*, size_t, const void*, int, void*, hipStream_t);
 
 }  // namespace zk

@@ -167,6 +167,33 @@ __global__ __launch_bounds__(KING_THREADS) void pss_pack_kernel(const Fp<P>* __r
   for (int p = 0; p < N; p++) store_elem(shares + (size_t)p * nchunks + j, sh[p]);
 }
 
+// pack at order 0 from a source of `count` valid secrets: the tail of the last chunk, up to nchunks * l, reads as zero
+// (pack_from_witness, sha256.rs:131-156, pads the witness this way).  Same shares as pss_pack_kernel over a padded copy.
+template <class P, int L>
+__global__ __launch_bounds__(KING_THREADS) void pss_pack_count_kernel(const Fp<P>* __restrict__ secrets, size_t count,
+                                                                     size_t nchunks, RngSeed seed,
+                                                                     const Fp<P>* __restrict__ Pm /* [n][l+t] */,
+                                                                     const PackL2<Fp<P>>* __restrict__ k2,
+                                                                     Fp<P>* __restrict__ shares /* [n][nchunks] */) {
+  using F = Fp<P>;
+  constexpr int T = L, N = 4 * L;
+  size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nchunks) return;
+  F v[L + T];
+#pragma unroll
+  for (int i = 0; i < L; i++) v[i] = j * L + i < count ? load_elem(secrets + j * L + i) : F::zero();
+  if constexpr (T == 2) {
+    rand_fp_pair<P>(seed, (uint64_t)j * T, &v[L], &v[L + 1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < T; i++) v[L + i] = rand_fp<P>(seed, j * T + i);
+  }
+  F sh[N];
+  pack_chunk<P, L, L + T>(v, Pm, k2, sh);
+#pragma unroll
+  for (int p = 0; p < N; p++) store_elem(shares + (size_t)p * nchunks + j, sh[p]);
+}
+
 // secrets[j*l + i] = sum_s U[i][s] * shares[s][j].
 template <class P, int L>
 __global__ __launch_bounds__(KING_THREADS) void pss_unpack_kernel(const Fp<P>* __restrict__ shares /* [np][nchunks] */,
@@ -218,6 +245,9 @@ struct KingBatch {
   // distance between the rows of two parties, in and out (0: the vector length m/l).  A king round that carries the
   // vectors of a whole batch of proofs has party rows [items][m/l]: stride = m/l, row_pitch = items * m/l
   size_t row_pitch;
+  // XORed into the item's replay stream id after the offset (0 everywhere but in zk_groth16_deal_masks, whose out-masks
+  // draw from (seed + 16 b + k) ^ 0x2222 as FftMask::sample called singly does; never set on the production stream)
+  uint64_t seed_xor;
   ZK_HD uint64_t seed_off(uint32_t y) const {
     return items_per ? (uint64_t)(y / items_per) * seed_step + y % items_per : (uint64_t)y;
   }
@@ -240,7 +270,7 @@ __global__ __launch_bounds__(KING_THREADS, 4) void king_fft2_kernel(
   F* __restrict__ out = out0 + blockIdx.y * kb.stride;
   const F* __restrict__ in_mask = kb.in_mask[blockIdx.y];
   const F* __restrict__ out_mask = kb.out_mask[blockIdx.y];
-  const RngSeed seed = seed0.plus(kb.seed_off(blockIdx.y));
+  const RngSeed seed = RngSeed{(seed0.seed + kb.seed_off(blockIdx.y)) ^ kb.seed_xor, seed0.key};
   constexpr int T = L, N = 4 * L;
   constexpr int LOGL = (L == 1) ? 0 : (L == 2) ? 1 : (L == 4) ? 2 : (L == 8) ? 3 : 4;
   extern __shared__ uint4 smem[];
@@ -557,6 +587,116 @@ __global__ __launch_bounds__(64) void king_degred_coop_kernel(
   F sh = pack_row<F>(Pm, (int)p, s0, s1, r0, r1);
   if (out_mask) sh = sh + load_elem(out_mask + o);
   if (live) store_elem(out + o, sh);
+}
+
+// ---- zk_groth16_deal_masks: the Fr masks of a batch of proofs (sha256.rs:226-291), blockIdx.y = item.
+// FFT masks: item y = cfg * 3 nb + 3 b + k' is FFT mask k = 3 cfg + k' of proof b (cfg 0: the three d_ifft masks, cfg 1: the
+// three d_fft masks -- one king launch per cfg over contiguous items).  Replay stream (key == nullptr): values from
+// seed + 16 b + k, in-mask randomness from that ^ 0x1111 (the king draws ^ 0x2222: KingBatch::seed_xor), as
+// FftMask::sample called singly; production stream: the nonces base + 2 y and base + 2 y + 1.
+constexpr int DEAL_FFT_ITEMS = 6 * DEGRED_BATCH;
+template <class F>
+struct DealFftArg {
+  F* in_mask[DEAL_FFT_ITEMS];      // [n][Lc] each, nullptr: the slot is skipped
+  F* out_mask[DEAL_FFT_ITEMS];
+};
+// Draw + pack in one pass: thread j of item y draws the l values of chunk j (rand_fill_kernel's transposed layout: value
+// j l + i goes to row i), stores them for the king as vals[i][y][j] (party rows of `items` vectors: KingBatch::row_pitch)
+// and writes the in-mask shares pack(order 1) gives for them.
+template <class P, int L>
+__global__ __launch_bounds__(KING_THREADS) void deal_fft_fill_pack_kernel(DealFftArg<Fp<P>> arg, uint32_t nb, uint32_t log_lc,
+                                                                         RngSeed base, const Fp<P>* __restrict__ Pm,
+                                                                         const PackL2<Fp<P>>* __restrict__ k2,
+                                                                         Fp<P>* __restrict__ vals) {
+  using F = Fp<P>;
+  constexpr int T = L, N = 4 * L;
+  const size_t Lc = (size_t)1 << log_lc, j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= Lc) return;
+  const uint32_t y = blockIdx.y, items = 6 * nb;
+  const uint32_t b = (y % (3 * nb)) / 3, k = 3 * (y / (3 * nb)) + y % 3;
+  RngSeed r0, r1;
+  if (!base.key) {
+    const uint64_t s = base.seed + 16ull * b + k;
+    r0 = RngSeed{s, nullptr}, r1 = RngSeed{s ^ 0x1111ull, nullptr};
+  } else {
+    r0 = RngSeed{base.seed + 2ull * y, base.key}, r1 = RngSeed{base.seed + 2ull * y + 1, base.key};
+  }
+  F v[L + T];
+#pragma unroll
+  for (int i = 0; i < L; i++) {
+    v[i] = rand_fp<P>(r0, (uint64_t)j * L + i);
+    store_elem(vals + ((size_t)i * items + y) * Lc + j, v[i]);
+  }
+  F* const dst = arg.in_mask[y];
+  if (!dst) return;
+  if constexpr (T == 2) {
+    rand_fp_pair<P>(r1, (uint64_t)j * T, &v[L], &v[L + 1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < T; i++) v[L + i] = rand_fp<P>(r1, j * T + i);
+  }
+  F sh[N];
+  pack_chunk<P, L, L + T>(v, Pm, k2, sh);
+#pragma unroll
+  for (int p = 0; p < N; p++) store_elem(dst + (size_t)p * Lc + j, sh[p]);
+}
+// the king's output [n][items][Lc] -> the callers' out-mask buffers [n][Lc]
+template <class F>
+__global__ void deal_fft_scatter_kernel(const F* __restrict__ kout, DealFftArg<F> arg, uint32_t items, size_t Lc, uint32_t n) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t y = blockIdx.y;
+  F* const dst = arg.out_mask[y];
+  if (idx >= (size_t)n * Lc || !dst) return;
+  const size_t p = idx / Lc, j = idx % Lc;
+  store_elem(dst + idx, load_elem(kout + (p * items + y) * Lc + j));
+}
+// DegRedMask::sample (deg_red.rs:40-66, gen = 1) of proof b = blockIdx.y: draw the l values of chunk j, pack them (order 0)
+// into the in-mask and their negatives into the out-mask.  Replay: streams seed + 16 b + 6, ^ 0x1111, ^ 0x2222; production:
+// the nonces base + 3 b + {0, 1, 2}.
+template <class F>
+struct DealDegredArg {
+  F* in_mask[DEGRED_BATCH];
+  F* out_mask[DEGRED_BATCH];
+};
+template <class P, int L>
+__global__ __launch_bounds__(KING_THREADS) void deal_degred_kernel(DealDegredArg<Fp<P>> arg, size_t len, RngSeed base,
+                                                                  const Fp<P>* __restrict__ Pm,
+                                                                  const PackL2<Fp<P>>* __restrict__ k2) {
+  using F = Fp<P>;
+  constexpr int T = L, N = 4 * L;
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t b = blockIdx.y;
+  F* const din = arg.in_mask[b];
+  F* const dout = arg.out_mask[b];
+  if (j >= len || !din) return;
+  RngSeed r0, r1, r2;
+  if (!base.key) {
+    const uint64_t s = base.seed + 16ull * b + 6;
+    r0 = RngSeed{s, nullptr}, r1 = RngSeed{s ^ 0x1111ull, nullptr}, r2 = RngSeed{s ^ 0x2222ull, nullptr};
+  } else {
+    r0 = RngSeed{base.seed + 3ull * b, base.key}, r1 = RngSeed{base.seed + 3ull * b + 1, base.key};
+    r2 = RngSeed{base.seed + 3ull * b + 2, base.key};
+  }
+  F v[L + T];
+  F sh[N];
+#pragma unroll
+  for (int i = 0; i < L; i++) v[i] = rand_fp<P>(r0, (uint64_t)j * L + i);
+#pragma unroll 1
+  for (int io = 0; io < 2; io++) {
+    const RngSeed rr = io ? r2 : r1;
+    if constexpr (T == 2) {
+      rand_fp_pair<P>(rr, (uint64_t)j * T, &v[L], &v[L + 1]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < T; i++) v[L + i] = rand_fp<P>(rr, j * T + i);
+    }
+    pack_chunk<P, L, L + T>(v, Pm, k2, sh);
+    F* const dst = io ? dout : din;
+#pragma unroll
+    for (int p = 0; p < N; p++) store_elem(dst + (size_t)p * len + j, sh[p]);
+#pragma unroll
+    for (int i = 0; i < L; i++) v[i] = v[i].neg();
+  }
 }
 
 // (the king-side kernels of d_pp live in dpp.hpp)

@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import fields
+from . import api, fields
 from .api import DeviceBuffer, ZK_G1, ZK_G2, _ptr
 
 G1_GEN = {
@@ -228,50 +228,61 @@ class Crs:
 
 
 class Witness:
-    """QAP::pss (qap.rs:91-135) and pack_from_witness (sha256.rs:131-156) on the device."""
+    """QAP::pss (qap.rs:91-135) and pack_from_witness (sha256.rs:131-156) on the device, in one call
+    (zk_groth16_deal_witness).  `w` is the assignment as a list of ints or as a DeviceBuffer; a device-resident witness
+    is never copied to the host."""
 
-    def __init__(self, pp, curve, r1cs, w, seed, dev_r1cs=None):
+    def __init__(self, pp, curve, r1cs, w, seed, dev_r1cs=None, stream=None):
         from .circom import DeviceR1cs
         dev_r1cs = dev_r1cs or DeviceR1cs(pp, r1cs)
         w_d = w if isinstance(w, DeviceBuffer) else pp.upload_fr(w)
         self.log_m = log_m = dev_r1cs.log_m
         m = 1 << log_m
-        self.qap = []
-        for k, d in enumerate(dev_r1cs.qap(w_d)):              # qap.rs:42-89 on the device
-            pp._check(pp.lib.zk_bitrev(pp.h, d.ptr, log_m, None))
-            self.qap.append(pp.pack(d, m // pp.l, seed + k, order=1))
-        if isinstance(w, DeviceBuffer):
-            w = pp.download_fr(w, r1cs.num_variables)
-        ni = r1cs.num_instance_variables
+        nv, nc, ni = r1cs.num_variables, r1cs.num_constraints, r1cs.num_instance_variables
+        (pa, ca, va), (pb, cb, vb) = dev_r1cs._mats
+        la, lw = C.c_size_t(0), C.c_size_t(0)
 
-        def deal(vals, sd):
-            vals = list(vals)
-            if len(vals) % pp.l:
-                vals += [0] * (pp.l - len(vals) % pp.l)
-            return pp.pack(pp.upload_fr(vals), len(vals) // pp.l, sd), len(vals) // pp.l
+        def call(qa, qb, qc, a_sh, ax_sh):
+            pp._check(pp.lib.zk_groth16_deal_witness(pp.h, pa.ptr, ca.ptr, va.ptr, pb.ptr, cb.ptr, vb.ptr, w_d.ptr, nv, nc,
+                                                     ni, log_m, seed, qa, qb, qc, a_sh, ax_sh, C.byref(la), C.byref(lw),
+                                                     stream))
 
-        self.a_share, self.len_a = deal(w[1:], seed + 3)
-        self.ax_share, self.len_w = deal(w[ni:], seed + 4)
+        call(None, None, None, None, None)                     # size query
+        self.len_a, self.len_w = la.value, lw.value
+        self.qap = [pp.alloc_fr(max(1, pp.n * (m // pp.l))) for _ in range(3)]      # (m < l: the library reports it)
+        self.a_share = pp.alloc_fr(max(1, pp.n * self.len_a))
+        self.ax_share = pp.alloc_fr(max(1, pp.n * self.len_w))
+        call(self.qap[0].ptr, self.qap[1].ptr, self.qap[2].ptr, self.a_share.ptr, self.ax_share.ptr)
+
+
+def generators(pp):
+    """(G1 generator, G2 generator or None) of the context's curve as affine Montgomery rows."""
+    g1 = _affine_codec(pp, list(G1_GEN[pp.curve]), False)
+    gg = G2_GEN.get(pp.curve)
+    g2 = None if gg is None else _affine_codec(pp, [gg[0][0], gg[0][1], gg[1][0], gg[1][1]], True)
+    return g1, g2
 
 
 class ProofMasks:
     """All preprocessing material of one proof, dealt as groth16/examples/sha256.rs:226-291 does: six FftMask (three
     for the d_ifft with the coset shift w_2m and rearranged output, three for the d_fft), one DegRedMask and five
-    MsmMask (A, B-in-G1, B-in-G2, C.w, C.u), all sampled by the library's dealers (zk_fft_mask_sample,
-    zk_degred_mask_sample, zk_msm_mask_sample).  `.ct` is the zk_groth16_masks to pass to prove()."""
+    MsmMask (A, B-in-G1, B-in-G2, C.w, C.u), all dealt on the device by ONE library call (zk_groth16_deal_masks; in
+    replay mode the same elements as zk_fft_mask_sample, zk_degred_mask_sample and zk_msm_mask_sample called singly with
+    seed + k, seed + 6 and seed + 7 + k).  `.ct` is the zk_groth16_masks to pass to prove();
+    ProofMasks.batch deals the masks of several proofs in one call."""
 
-    def __init__(self, pp, log_m, seed):
-        from . import api
-        m = 1 << log_m
-        w2m = _root_of_unity(pp.curve, log_m + 1)
-        self.fft = [api.FftMask.sample(pp, k < 3, w2m if k < 3 else None, 1 if k < 3 else 0, log_m, seed + k)
-                    for k in range(6)]
-        self.degred = api.DegRedMask.sample(pp, m // pp.l, seed + 6)
-        g1 = _affine_codec(pp, list(G1_GEN[pp.curve]), False)
-        gg = G2_GEN[pp.curve]
-        g2 = _affine_codec(pp, [gg[0][0], gg[0][1], gg[1][0], gg[1][1]], True)
-        self.msm = [api.MsmMask.sample(pp, ZK_G2 if k == 2 else ZK_G1, g2 if k == 2 else g1, seed + 7 + k)
-                    for k in range(5)]
+    def __init__(self, pp, log_m, seed, stream=None):
+        self._alloc(pp, log_m)
+        g1, g2 = generators(pp)
+        api.deal_masks(pp, 1, log_m, g1, g2, seed, self.ct, stream)
+
+    def _alloc(self, pp, log_m):
+        cnt = pp.n * ((1 << log_m) // pp.l)
+        nl = pp.fq.nl
+        self.fft = [api.FftMask(pp.alloc_fr(cnt), pp.alloc_fr(cnt)) for _ in range(6)]
+        self.degred = api.DegRedMask(pp.alloc_fr(cnt), pp.alloc_fr(cnt))
+        self.msm = [api.MsmMask(np.zeros((pp.n, 3 * nl * (2 if k == 2 else 1)), dtype=np.uint64),
+                                 np.zeros((pp.n, 3 * nl * (2 if k == 2 else 1)), dtype=np.uint64)) for k in range(5)]
         ct = Masks()
         for k in range(6):
             ct.fft_in[k], ct.fft_out[k] = self.fft[k].in_mask.ptr, self.fft[k].out_mask.ptr
@@ -279,6 +290,21 @@ class ProofMasks:
         for k in range(5):
             ct.msm_in[k], ct.msm_out[k] = self.msm[k].in_mask.ctypes.data, self.msm[k].out_mask.ctypes.data
         self.ct = ct
+
+    @classmethod
+    def batch(cls, pp, log_m, seed, nproofs, stream=None):
+        """The masks of `nproofs` proofs from one zk_groth16_deal_masks call: a list of ProofMasks whose `.ct` entries
+        feed prove_batch; proof b holds what ProofMasks(pp, log_m, seed + 16 * b) holds (replay mode)."""
+        out = []
+        arr = (Masks * nproofs)()
+        for b in range(nproofs):
+            pm = cls.__new__(cls)
+            pm._alloc(pp, log_m)
+            C.memmove(C.byref(arr, b * C.sizeof(Masks)), C.byref(pm.ct), C.sizeof(Masks))
+            out.append(pm)
+        g1, g2 = generators(pp)
+        api.deal_masks(pp, nproofs, log_m, g1, g2, seed, arr, stream)
+        return out
 
 
 def verifying_key(pp, setup):
