@@ -1,6 +1,10 @@
-"""The verifier timed on one GPU: us per proof of zk_groth16_verify and us per pairing of zk_multi_pairing (k = 1) at
-count = 1, 16, 256 and 4096 on BN254 and BLS12-381.
-usage: python tools/verify_bench.py [--counts 1,16,256,4096] [--curves bn254,bls12_381] [--reps 7] [--out FILE] [--cpu-oracle]
+"""The verifier timed on one GPU: us per proof of zk_groth16_verify and of zk_groth16_verify_all (one verdict for the batch)
+and us per pairing of zk_multi_pairing (k = 1) at count = 1, 16, 256, 4096, 16384 and 65536 on BN254 and BLS12-381.
+usage: python tools/verify_bench.py [--counts 1,16,...] [--curves bn254,bls12_381] [--reps 7] [--out FILE] [--cpu-oracle]
+                                    [--alternate]
+--alternate times only the two verifier calls, interleaved rep by rep in one process (per-proof, batch, per-proof, ...) on
+arrays encoded once outside the timed region, so that both see the same clocks and the same neighbours: the yardstick for
+"from which count does the batch call win".  Call a count faster only where the two min-max ranges do not overlap.
 Per (curve, call, count): one warm-up call, then `reps` timed calls (host clock around a call that returns with the
 result on the host or in device memory after its own wait), reported as median, min and max; the per-kernel share comes
 from the library's HIP-event slots (pairing_miller_kernel, pairing_final_exp_kernel) over the same calls.  The proofs are
@@ -87,6 +91,10 @@ def run(curve, counts, reps):
         ts, k = timed(pp, lambda: res.append(zg.verify(pp, pvk, proofs, xs)), reps)
         assert all(all(r) for r in res), "a valid proof was rejected"
         rows.append(row(curve, "zk_groth16_verify", count, ts, k))
+        res = []
+        ts, k = timed(pp, lambda: res.append(zg.verify_all(pp, pvk, proofs, xs)), reps)
+        assert all(res), "a valid batch was rejected"
+        rows.append(row(curve, "zk_groth16_verify_all", count, ts, k))
         sc = pp.upload_fr([3 + i for i in range(count)])
         p1, q2 = zg.base_points(pp, ZK_G1, sc, count), zg.base_points(pp, ZK_G2, sc, count)
         out = zk.DeviceBuffer(pp, count * 12 * pp.fq.nbytes)
@@ -95,6 +103,53 @@ def run(curve, counts, reps):
         for b in (sc, p1, q2, out):
             b.free()
     return rows, (pp, vk, aff, w)
+
+
+def run_alternate(curve, counts, reps):
+    """zk_groth16_verify and zk_groth16_verify_all through the C ABI on the same host arrays, one warm-up each, then `reps`
+    rounds of (per-proof call, batch call); the kernel slots are read in a profiled round of their own after the timed ones"""
+    pp = zk.PackedSharingParams(curve, 2)
+    P = zk.fields.FR[curve]
+    r1, w = small_r1cs(P)
+    setup = zg.SetupScalars(curve, r1, 11, 12, 13, 14, 15)
+    aff, _ = zg.reconstruct(pp, zg.prove(pp, zg.Crs(pp, setup), zg.Witness(pp, curve, r1, w, seed=5), 21, 22, seed=9),
+                            want_bytes=False)
+    pvk = zg.PreparedVk(pp, zg.verifying_key(pp, setup))
+    rows = []
+    for count in counts:
+        proofs = np.ascontiguousarray(np.tile(np.asarray(aff, dtype=np.uint64).reshape(1, -1), (count, 1)))
+        xs = np.ascontiguousarray(np.tile(pp.fr.encode([w[1]]).reshape(1, -1), (count, 1)))
+        ok = np.zeros(count, dtype=np.uint8)
+        allok = C.c_int(0)
+
+        def each():
+            pp._check(pp.lib.zk_groth16_verify(pp.h, pvk.h, proofs.ctypes.data, xs.ctypes.data, 1, count, ok.ctypes.data, None))
+            assert ok.all(), "a valid proof was rejected"
+
+        def batch():
+            pp._check(pp.lib.zk_groth16_verify_all(pp.h, pvk.h, proofs.ctypes.data, xs.ctypes.data, 1, count, None,
+                                                   C.byref(allok), None, None))
+            assert allok.value == 1, "a valid batch was rejected"
+
+        each()
+        batch()
+        t = {"zk_groth16_verify": [], "zk_groth16_verify_all": []}
+        for _ in range(reps):
+            for name, fn in (("zk_groth16_verify", each), ("zk_groth16_verify_all", batch)):
+                t0 = time.perf_counter()
+                fn()
+                t[name].append(time.perf_counter() - t0)
+        for name, fn in (("zk_groth16_verify", each), ("zk_groth16_verify_all", batch)):
+            pp._check(pp.lib.zk_profile_enable(pp.h, 1))
+            fn()
+            k = slots(pp)
+            pp._check(pp.lib.zk_profile_enable(pp.h, 0))
+            rows.append(row(curve, name + " (alternating)", count, t[name], k))
+        a, b = t["zk_groth16_verify"], t["zk_groth16_verify_all"]
+        verdict = "batch faster" if max(b) < min(a) else "per-proof faster" if max(a) < min(b) else "ranges overlap"
+        print(json.dumps({"curve": curve, "count": count, "verdict": verdict,
+                          "ratio_of_medians": round(statistics.median(a) / statistics.median(b), 2)}), flush=True)
+    return rows
 
 
 def row(curve, call, count, ts, kernels):
@@ -122,14 +177,18 @@ def cpu_oracle(curve, pp, vk, aff, w):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--counts", default="1,16,256,4096")
+    ap.add_argument("--counts", default="1,16,256,4096,16384,65536")
     ap.add_argument("--curves", default="bn254,bls12_381")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--cpu-oracle", action="store_true")
+    ap.add_argument("--alternate", action="store_true")
     a = ap.parse_args()
-    out = {"tool": "tools/verify_bench.py", "reps": a.reps, "rows": []}
+    out = {"tool": "tools/verify_bench.py" + (" --alternate" if a.alternate else ""), "reps": a.reps, "rows": []}
     for curve in a.curves.split(","):
+        if a.alternate:
+            out["rows"] += run_alternate(curve, [int(c) for c in a.counts.split(",")], a.reps)
+            continue
         rows, (pp, vk, aff, w) = run(curve, [int(c) for c in a.counts.split(",")], a.reps)
         out["rows"] += rows
         if a.cpu_oracle:

@@ -28,7 +28,7 @@ SYMBOLS = [
     "zk_dist_deg_red_points", "zk_dist_libsnark_h", "zk_deg_red_host", "zk_d_pp_host", "zk_circom_h_host",
     "zk_groth16_prove_host",
     "zk_multi_pairing", "zk_fq12_selftest", "zk_groth16_vk_prepare", "zk_groth16_vk_free", "zk_groth16_verify",
-    "zk_base_mul_few", "zk_groth16_deal_masks", "zk_groth16_deal_witness",
+    "zk_base_mul_few", "zk_groth16_deal_masks", "zk_groth16_deal_witness", "zk_groth16_verify_all",
 ]
 
 _lib = None
@@ -207,6 +207,7 @@ def load():
     lib.zk_groth16_vk_free.argtypes = [vp]
     lib.zk_groth16_vk_free.restype = None
     lib.zk_groth16_verify.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]
+    lib.zk_groth16_verify_all.argtypes = [vp, vp, vp, vp, sz, sz, vp, C.POINTER(i32), vp, vp]
     lib.zk_base_mul_few.argtypes = [vp, i32, vp, vp, sz, vp, vp]
     lib.zk_groth16_deal_masks.argtypes = [vp, i32, i32, vp, vp, u64, vp, vp]
     lib.zk_groth16_deal_witness.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, i32, u64, vp, vp, vp, vp, vp,

@@ -738,7 +738,10 @@ static const char* const kSlotNames[zk::PROF_NSLOTS] = {"ntt_pass_kernel", "king
                                                          "dpp_finish_kernel", "host:prove_launch", "host:prove_wait",
                                                          "host:prove_tail", "host:launch.submit", "host:launch.circom_h",
                                                          "host:launch.u_msm", "pairing_miller_kernel",
-                                                         "pairing_final_exp_kernel"};
+                                                         "pairing_final_exp_kernel", "pairing_rlc_scale_kernel",
+                                                         "pairing_rlc_dot_kernel", "pairing_rlc_sum_kernel",
+                                                         "pairing_rlc_gamma_kernel", "pairing_rlc_finish_kernel",
+                                                         "pairing_gt_fold_kernel"};
 int zk_profile_enable(zk_ctx* ctx, int on) {
   CTX_OR_FAIL();
   e->prof.reset();
@@ -845,6 +848,11 @@ int zk_groth16_verify(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affine, c
                       size_t count, uint8_t* ok, void* stream) {
   PAIRING_OR_FAIL();
   return pr->verify(e, vk, proofs_affine, public_inputs, n_inputs, count, ok, S(stream));
+}
+int zk_groth16_verify_all(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affine, const void* public_inputs,
+                          size_t n_inputs, size_t count, const uint8_t* seed, int* all_ok, void* gt_out, void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->verify_all(e, vk, proofs_affine, public_inputs, n_inputs, count, seed, all_ok, gt_out, S(stream));
 }
 
 }  // extern "C"

@@ -37,7 +37,9 @@ enum ProfSlot { PROF_NTT_PASS = 0, PROF_KING, PROF_MSM_ACC_G1, PROF_MSM_ACC_G2, 
                 // parts of the first: entry -> MSM tasks handed to the pool; circom_h's launches; the U-MSM's launches + host terms
                 PROF_HOST_SUBMIT, PROF_HOST_H, PROF_HOST_U,
                 // the verifier (pairing.hpp): Miller loops + group product, then the final exponentiation; units = pairs / groups
-                PROF_MILLER, PROF_FINAL_EXP, PROF_NSLOTS };
+                PROF_MILLER, PROF_FINAL_EXP,
+                // zk_groth16_verify_all (pairing_rlc.hpp): units = proofs, Fr sums, points summed, table rows, Miller values
+                PROF_RLC_SCALE, PROF_RLC_DOT, PROF_RLC_SUM, PROF_RLC_GAMMA, PROF_RLC_FINISH, PROF_GT_FOLD, PROF_NSLOTS };
 
 struct Profiler {
   bool on = false;

@@ -7,7 +7,8 @@
 #pragma once
 #include "engine.hpp"
 
-// ark_groth16::PreparedVerifyingKey on the device: gamma_abc_g1 with its doubling tables, -gamma_g2, -delta_g2 (affine) and e(alpha, beta)
+// ark_groth16::PreparedVerifyingKey on the device: gamma_abc_g1 with its doubling tables, -gamma_g2, -delta_g2 (affine) and e(alpha, beta);
+// for the batch check alpha and beta themselves, the doubling tables of abc[0] and alpha, and the one of Fq12
 struct zk_vk {
   int curve = 0, device = 0;
   size_t n_abc = 0;
@@ -16,11 +17,16 @@ struct zk_vk {
   void* neg_gamma_d = nullptr;    // G2 affine
   void* neg_delta_d = nullptr;    // G2 affine
   void* alpha_beta_d = nullptr;   // [12] Fq
+  // what zk_groth16_verify_all reads besides (zk_groth16_verify reads none of it)
+  void* rlc_base_d = nullptr;     // [3] G1 affine: the identity, abc[0], alpha
+  void* rlc_table_d = nullptr;    // [2][bits of Fr] XYZZ: 2^k abc[0], 2^k alpha
+  void* beta_d = nullptr;         // G2 affine
+  void* one_d = nullptr;          // [12] Fq: the one of Fq12, what the batch's product is compared with
   ~zk_vk() {
     int cur = -1;                   // zk_groth16_vk_free takes no context: the caller's current device is left as it was
     const bool have = hipGetDevice(&cur) == hipSuccess;
     (void)hipSetDevice(device);
-    for (void* p : {abc_d, abc_table_d, neg_gamma_d, neg_delta_d, alpha_beta_d})
+    for (void* p : {abc_d, abc_table_d, neg_gamma_d, neg_delta_d, alpha_beta_d, rlc_base_d, rlc_table_d, beta_d, one_d})
       if (p) (void)hipFree(p);
     if (have && cur != device) (void)hipSetDevice(cur);
   }
@@ -39,6 +45,8 @@ class IPairing {
                          const void* gamma_abc_g1, size_t n_abc, zk_vk* vk) = 0;
   virtual int verify(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count,
                      uint8_t* ok, hipStream_t st) = 0;
+  virtual int verify_all(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count,
+                         const uint8_t* seed, int* all_ok, void* gt_out, hipStream_t st) = 0;
 };
 
 IPairing* pairing_bn254();

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -281,6 +282,10 @@ __global__ __launch_bounds__(64) void pairing_verify_prep_kernel(
   valid[i] = (uint8_t)(on_g1(pr.A) && on_g1(pr.C) && okb);
 }
 
+}  // namespace zk
+#include "pairing_rlc.hpp"
+namespace zk {
+
 #define ZK_PAIR_HIP(expr)                                \
   do {                                                   \
     hipError_t _e = (expr);                              \
@@ -301,6 +306,11 @@ class PairingImpl : public IPairing {
   struct Workspace {
     std::mutex mu;
     DevBuf proofs, inputs, P, Q, mill, valid, ok;
+    // zk_groth16_verify_all: points (r_i C_i, the levels of the two sums), Fr (r_i, s and s_t), bytes (validity and its
+    // levels, the folded byte, the verdict), Fq12 (the group products, the value after the final exponentiation)
+    DevBuf rlc_pts, rlc_fr, rlc_bytes, rlc_gt;
+    uint8_t host_ok = 0;              // where the verdict and the value land: not the caller's memory, which a call whose
+    F2 host_gt[6];                    // wait deadline passed has already given back
   };
   std::mutex ws_mu_;
   std::map<int, Workspace*> ws_;
@@ -398,12 +408,25 @@ class PairingImpl : public IPairing {
     }
     ZK_PAIR_HIP(hipMemcpy(vk->neg_gamma_d, &ng, sizeof(ng), hipMemcpyHostToDevice));
     ZK_PAIR_HIP(hipMemcpy(vk->neg_delta_d, &nd, sizeof(nd), hipMemcpyHostToDevice));
-    DevBuf a, b;
-    ZK_PAIR_HIP(a.ensure(sizeof(Affine<Fq>)));
-    ZK_PAIR_HIP(b.ensure(sizeof(Affine<F2>)));
-    ZK_PAIR_HIP(hipMemcpy(a.p, alpha_g1, sizeof(Affine<Fq>), hipMemcpyHostToDevice));
-    ZK_PAIR_HIP(hipMemcpy(b.p, beta_g2, sizeof(Affine<F2>), hipMemcpyHostToDevice));
-    return multi_pairing(e, a.p, b.p, 1, 1, vk->alpha_beta_d, nullptr);      // e(alpha, beta), once
+    // the batch check's part: alpha, beta, the doubling tables of abc[0] and alpha (rows 0, 1 of one table), the Fq12 one
+    Affine<Fq> base[3];
+    base[0] = Affine<Fq>{Fq::zero(), Fq::zero()};
+    memcpy(&base[1], gamma_abc_g1, sizeof(Affine<Fq>));
+    memcpy(&base[2], alpha_g1, sizeof(Affine<Fq>));
+    F2 one[6];
+    for (int i = 0; i < 6; i++) one[i] = i ? F2::zero() : F2::one();
+    ZK_PAIR_HIP(hipMalloc(&vk->rlc_base_d, sizeof(base)));
+    ZK_PAIR_HIP(hipMalloc(&vk->rlc_table_d, 2 * FrP::BITS * sizeof(XYZZ<Fq>)));
+    ZK_PAIR_HIP(hipMalloc(&vk->beta_d, sizeof(Affine<F2>)));
+    ZK_PAIR_HIP(hipMalloc(&vk->one_d, sizeof(one)));
+    ZK_PAIR_HIP(hipMemcpy(vk->rlc_base_d, base, sizeof(base), hipMemcpyHostToDevice));
+    ZK_PAIR_HIP(hipMemcpy(vk->beta_d, beta_g2, sizeof(Affine<F2>), hipMemcpyHostToDevice));
+    ZK_PAIR_HIP(hipMemcpy(vk->one_d, one, sizeof(one), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((pairing_abc_table_kernel<Fq, FrP::BITS>), dim3(1), dim3(64), 0, nullptr, (const Affine<Fq>*)vk->rlc_base_d,
+                       (size_t)2, (XYZZ<Fq>*)vk->rlc_table_d);
+    ZK_PAIR_HIP(hipGetLastError());
+    const Affine<Fq>* alpha_d = (const Affine<Fq>*)vk->rlc_base_d + 2;
+    return multi_pairing(e, alpha_d, vk->beta_d, 1, 1, vk->alpha_beta_d, nullptr);      // e(alpha, beta), once
   }
 
   int verify(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count, uint8_t* ok,
@@ -442,6 +465,136 @@ class PairingImpl : public IPairing {
     }
     const int wrc = wait(e, st, "zk_groth16_verify");      // also on an error path: the workspace is handed on after it
     return rc ? rc : wrc;
+  }
+
+ private:
+  static size_t div256(size_t n) { return (n + 255) / 256; }
+  // the sum of in[0 .. n) (and the AND of vin[0 .. n)) by pairing_rlc_sum_kernel, 256 to 1 per launch and at least once;
+  // a / b (va / vb) take the levels in turn: a holds div256(n) entries, b div256(div256(n))
+  static const XYZZ<Fq>* tree_sum(IEngine* e, const XYZZ<Fq>* in, const uint8_t* vin, size_t n, XYZZ<Fq>* a, XYZZ<Fq>* b, uint8_t* va,
+                                  uint8_t* vb, const uint8_t** vout, hipStream_t st) {
+    ProfScope ps(e->prof, PROF_RLC_SUM, st, (double)n);
+    for (;;) {
+      const size_t m = div256(n);
+      hipLaunchKernelGGL(pairing_rlc_sum_kernel<Fq>, dim3((unsigned)m), dim3(256), 0, st, in, vin, n, a, va);
+      in = a, vin = va, n = m;
+      if (n == 1) break;
+      std::swap(a, b);
+      std::swap(va, vb);
+    }
+    if (vout) *vout = vin;
+    return in;
+  }
+
+ public:
+  int verify_all(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count,
+                 const uint8_t* seed, int* all_ok, void* gt_out, hipStream_t st) override {
+    if (int rc = e->check_wedged()) return rc;
+    if (!vk || vk->curve != CURVE || vk->device != e->device)
+      return e->fail(ZK_ERR_BAD_INPUT, "zk_groth16_verify_all: the verifying key was prepared for another context");
+    if (n_inputs + 1 != vk->n_abc) return e->fail(ZK_ERR_BAD_INPUT, "malformed verifying key");
+    if (!all_ok) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (!count) {
+      *all_ok = 1;
+      if (gt_out) {
+        F2 one[6];
+        for (int i = 0; i < 6; i++) one[i] = i ? F2::zero() : F2::one();
+        memcpy(gt_out, one, sizeof(one));
+      }
+      return ZK_OK;
+    }
+    if (!proofs || (n_inputs && !inputs)) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (count > ((size_t)1 << 30)) return e->fail(ZK_ERR_BAD_INPUT, "zk_groth16_verify_all: count too large");
+    uint8_t drawn[32];
+    if (!seed) {
+      FILE* f = fopen("/dev/urandom", "rb");
+      const size_t got = f ? fread(drawn, 1, sizeof(drawn), f) : 0;
+      if (f) fclose(f);
+      if (got != sizeof(drawn)) return e->fail(ZK_ERR_GENERIC, "cannot read /dev/urandom for the batch check's randomizers");
+      seed = drawn;
+    }
+    const RlcKey key = rlc_key(seed);
+    using Proof = ProofAffine<Fq, F2>;
+    using Pt = XYZZ<Fq>;
+    const size_t n_abc = vk->n_abc, npairs = count + 3;
+    const GtFoldPlan plan = gt_fold_plan(npairs);
+    // r_i C_i | the two levels of their sum | the gamma kernel's partial sums (+ s alpha) | the two levels of theirs
+    const size_t c1 = div256(count), c2 = div256(c1), gblk = (n_abc + RLC_GAMMA_ROWS - 1) / RLC_GAMMA_ROWS, g1 = div256(gblk),
+                 g2 = div256(g1);
+    Workspace& ws = workspace(e->device);
+    std::lock_guard<std::mutex> g(ws.mu);
+    ZK_PAIR_HIP(ws.proofs.ensure(count * sizeof(Proof)));
+    ZK_PAIR_HIP(ws.inputs.ensure(count * n_inputs * sizeof(Fr) + 1));
+    ZK_PAIR_HIP(ws.P.ensure(npairs * sizeof(Affine<Fq>)));
+    ZK_PAIR_HIP(ws.Q.ensure(npairs * sizeof(Affine<F2>)));
+    ZK_PAIR_HIP(ws.mill.ensure(npairs * 6 * sizeof(F2)));
+    ZK_PAIR_HIP(ws.rlc_pts.ensure((count + c1 + c2 + gblk + 1 + g1 + g2) * sizeof(Pt)));
+    ZK_PAIR_HIP(ws.rlc_fr.ensure((count + n_abc) * sizeof(Fr)));
+    ZK_PAIR_HIP(ws.rlc_bytes.ensure(count + c1 + c2 + 2));
+    ZK_PAIR_HIP(ws.rlc_gt.ensure((plan.G + 1) * 6 * sizeof(F2)));
+    Pt *cx = (Pt*)ws.rlc_pts.p, *ca = cx + count, *cb = ca + c1, *gpart = cb + c2, *ga = gpart + gblk + 1, *gb = ga + g1;
+    Fr *rfr = (Fr*)ws.rlc_fr.p, *sdot = rfr + count;
+    uint8_t *valid = (uint8_t*)ws.rlc_bytes.p, *va = valid + count, *vb = va + c1, *all_valid = vb + c2, *okd = all_valid + 1;
+    F2 *gfold = (F2*)ws.rlc_gt.p, *gt_d = gfold + plan.G * 6;
+    Affine<Fq>* P = (Affine<Fq>*)ws.P.p;
+    Affine<F2>* Q = (Affine<F2>*)ws.Q.p;
+    int rc = ZK_OK;
+    auto step = [&](hipError_t h, const char* what) {
+      if (!rc && h != hipSuccess) rc = e->hip_fail(h, what);
+    };
+    step(hipMemcpyAsync(ws.proofs.p, proofs, count * sizeof(Proof), hipMemcpyHostToDevice, st), "zk_groth16_verify_all: copy of the proofs");
+    if (n_inputs)
+      step(hipMemcpyAsync(ws.inputs.p, inputs, count * n_inputs * sizeof(Fr), hipMemcpyHostToDevice, st),
+           "zk_groth16_verify_all: copy of the public inputs");
+    if (!rc) {
+      {
+        ProfScope ps(e->prof, PROF_RLC_SCALE, st, (double)count);
+        hipLaunchKernelGGL((pairing_rlc_scale_kernel<PP, FrP>), dim3((unsigned)div256(2 * count)), dim3(256), 0, st,
+                           (const Proof*)ws.proofs.p, key, B1, count, P, Q, cx, rfr, valid);
+      }
+      {
+        ProfScope ps(e->prof, PROF_RLC_DOT, st, (double)n_abc);
+        hipLaunchKernelGGL(pairing_rlc_dot_kernel<FrP>, dim3((unsigned)n_abc), dim3(256), 0, st, (const Fr*)rfr,
+                           (const Fr*)ws.inputs.p, n_inputs, count, sdot);
+      }
+      const uint8_t* vall = nullptr;
+      const Pt* p_delta = tree_sum(e, cx, valid, count, ca, cb, va, vb, &vall, st);
+      {
+        ProfScope ps(e->prof, PROF_RLC_GAMMA, st, (double)n_abc + 1);
+        hipLaunchKernelGGL((pairing_rlc_gamma_kernel<Fq, FrP>), dim3((unsigned)gblk + 1), dim3(64), 0, st, (const Fr*)sdot, n_abc,
+                           (const Pt*)vk->abc_table_d, (const Pt*)vk->rlc_table_d, gpart);
+      }
+      const Pt* p_gamma = gblk == 1 ? gpart : tree_sum(e, gpart, nullptr, gblk, ga, gb, nullptr, nullptr, nullptr, st);
+      {
+        ProfScope ps(e->prof, PROF_RLC_FINISH, st, 3.0);
+        hipLaunchKernelGGL((pairing_rlc_finish_kernel<Fq, F2>), dim3(1), dim3(64), 0, st, p_gamma, p_delta, (const Pt*)(gpart + gblk),
+                           vall, (const Affine<F2>*)vk->neg_gamma_d, (const Affine<F2>*)vk->neg_delta_d,
+                           (const Affine<F2>*)vk->beta_d, count, P, Q, all_valid);
+      }
+      {
+        ProfScope ps(e->prof, PROF_MILLER, st, (double)npairs);
+        hipLaunchKernelGGL(pairing_miller_kernel<PP>, dim3(blocks(npairs)), dim3(256), 0, st, (const Affine<Fq>*)P,
+                           (const Affine<F2>*)Q, npairs, (F2*)ws.mill.p);
+      }
+      {
+        ProfScope ps(e->prof, PROF_GT_FOLD, st, (double)npairs);
+        hipLaunchKernelGGL(pairing_gt_fold_kernel<PP>, dim3(blocks(plan.G)), dim3(256), 0, st, (const F2*)ws.mill.p, npairs, plan.G,
+                           plan.len, gfold);
+      }
+      {
+        ProfScope ps(e->prof, PROF_FINAL_EXP, st, 1.0);
+        hipLaunchKernelGGL(pairing_final_exp_kernel<PP>, dim3(1), dim3(256), 0, st, (const F2*)gfold, plan.G, (size_t)1, digits(),
+                           gt_d, (const F2*)vk->one_d, (const uint8_t*)all_valid, okd);
+      }
+      step(hipGetLastError(), "zk_groth16_verify_all: launch");
+      step(hipMemcpyAsync(&ws.host_ok, okd, 1, hipMemcpyDeviceToHost, st), "zk_groth16_verify_all: copy of the verdict");
+      if (gt_out) step(hipMemcpyAsync(ws.host_gt, gt_d, sizeof(ws.host_gt), hipMemcpyDeviceToHost, st), "zk_groth16_verify_all: copy of the value");
+    }
+    const int wrc = wait(e, st, "zk_groth16_verify_all");      // also on an error path: the workspace is handed on after it
+    if (rc || wrc) return rc ? rc : wrc;
+    *all_ok = ws.host_ok != 0;
+    if (gt_out) memcpy(gt_out, ws.host_gt, sizeof(ws.host_gt));
+    return ZK_OK;
   }
 };
 

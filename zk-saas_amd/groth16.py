@@ -367,6 +367,35 @@ def verify(pp, pvk, proofs, public_inputs, stream=None):
     return [bool(v) for v in ok[:count]]
 
 
+def verify_all(pp, pvk, proofs, public_inputs, seed=None, stream=None, want_gt=False):
+    """zk_groth16_verify_all: one randomized pairing check for the whole batch (count + 3 Miller loops, one final
+    exponentiation).  Arguments as verify(); seed: 32 bytes nobody who made the proofs can predict, fresh per call (None: the
+    library draws them from the operating system).  Returns True when every proof has its points on their curves and the
+    combined equation holds -- for points in the order-r subgroups that is all(verify(...)) except with probability
+    2^-128 over the seed; after a False, verify() names the bad proofs.  want_gt: returns (bool, [12] Fq ints), the value of
+    the equation's left-hand side after the final exponentiation (1, 0, ..., 0 for an accepted batch)."""
+    nl = pp.fq.nl
+    pr = np.ascontiguousarray(np.asarray(proofs, dtype=np.uint64).reshape(-1, 8 * nl))
+    count = pr.shape[0]
+    if len(public_inputs) != count:
+        raise ValueError("one list of public inputs per proof")
+    n_inputs = len(public_inputs[0]) if count else pvk.n_abc - 1
+    if any(len(x) != n_inputs for x in public_inputs):
+        raise ValueError("every proof takes the same number of public inputs")
+    vals = [v for x in public_inputs for v in x]
+    xs = np.ascontiguousarray(pp.fr.encode(vals)) if vals else np.zeros(0, dtype=np.uint64)
+    sd = None
+    if seed is not None:
+        sd = bytes(seed)
+        if len(sd) != 32:
+            raise ValueError("the seed is 32 bytes")
+    ok = C.c_int(0)
+    gt = np.zeros(12 * nl, dtype=np.uint64)
+    pp._check(pp.lib.zk_groth16_verify_all(pp.h, pvk.h, pr.ctypes.data if count else None, xs.ctypes.data if xs.size else None,
+                                           n_inputs, count, sd, C.byref(ok), gt.ctypes.data if want_gt else None, stream))
+    return (bool(ok.value), pp.fq.decode(gt.reshape(12, nl))) if want_gt else bool(ok.value)
+
+
 def prove(pp, crs, wit, r, s, masks=None, seed=0, stream=None):
     """dsha256 (sha256.rs:32-129) for all parties. Returns (pi_a [n][3nl], pi_b [n][6nl], pi_c [n][3nl]) Jacobian."""
     nl = pp.fq.nl
