@@ -328,6 +328,31 @@ int zk_groth16_deal_witness(zk_ctx* ctx, const void* a_row_ptr_d, const void* a_
                             size_t num_variables, size_t num_constraints, size_t num_instance, int log_m, uint64_t seed,
                             void* qap_a_d, void* qap_b_d, void* qap_c_d, void* a_share_d, void* ax_share_d, size_t* len_a,
                             size_t* len_w, void* stream);
+/* zk_groth16_setup_scalars: the circuit-specific setup in the exponent (ark_groth16::generate_parameters with the circom
+ * reduction, what groth16/examples/sha256.rs calls circuit_specific_setup, before its fixed-base multiplications): R1CS
+ * and trapdoor -> the discrete logs of the five CRS vectors, LibsnarkReduction::instance_map_with_evaluation +
+ * CircomReduction::h_query_scalars, on the device.  A, B and C as CSR exactly as zk_r1cs_qap takes them (row_ptr u32
+ * [num_constraints + 1], col u32 wire indices, val Montgomery Fr; a matrix without nonzeros may pass NULL col / val).
+ * trapdoor (HOST): alpha, beta, gamma, delta, tau, five Montgomery Fr.  With u_i the Lagrange coefficients of the size-m
+ * domain (m = 2^log_m) at tau, outputs are Montgomery Fr device vectors in natural order:
+ *   a_query_d   [nv]      a_j = sum_i u_i A[i][j], plus u_{nc + j} for j < ni
+ *   b_query_d   [nv]      b_j = sum_i u_i B[i][j]
+ *   gamma_abc_d [ni]      (beta a_j + alpha b_j + c_j) / gamma for j < ni       (c_j = sum_i u_i C[i][j])
+ *   l_query_d   [nv - ni] (beta a_j + alpha b_j + c_j) / delta for j >= ni
+ *   h_query_d   [m]       the odd entries of ifft_2m([tau^j / delta]_{j < 2m - 1} || 0)
+ * `tail_zeros` zero elements are written behind each of a_query, b_query, l_query and h_query (so that l-chunked views
+ * handed to zk_pss_det_pack read zeros past the end); gamma_abc has no tail.  Any output pointer may be NULL: that vector
+ * is not written.  Ordered on `stream`; the call returns after the kernels that validate the wire indices have run.
+ * Errors: 2^log_m < nc + ni, ni == 0, ni > nv or a 2m domain beyond the field's two-adicity -> ZK_ERR_BAD_INPUT; a wire
+ * index >= nv -> ZK_ERR_GENERIC (as zk_r1cs_qap); a degenerate trapdoor -> ZK_ERR_BAD_INPUT naming the element: gamma = 0,
+ * delta = 0, tau = 0 or tau^(2m) = 1 (tau inside the size-2m domain), checked on the host before any launch.  arkworks
+ * would return an indicator vector for tau in the domain; no honest setup keeps such a tau, and refusing it keeps every
+ * denominator of the call nonzero.  The context stays usable after every error.  Device engine only. */
+int zk_groth16_setup_scalars(zk_ctx* ctx, const void* a_row_ptr_d, const void* a_col_d, const void* a_val_d,
+                             const void* b_row_ptr_d, const void* b_col_d, const void* b_val_d, const void* c_row_ptr_d,
+                             const void* c_col_d, const void* c_val_d, size_t num_variables, size_t num_constraints,
+                             size_t num_instance, int log_m, const void* trapdoor, size_t tail_zeros, void* a_query_d,
+                             void* b_query_d, void* l_query_d, void* h_query_d, void* gamma_abc_d, void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

@@ -28,6 +28,7 @@ pub mod dpp;
 pub mod error;
 pub mod net;
 pub mod pss;
+pub mod setup;
 
 use core::any::TypeId;
 use core::ffi::c_void;

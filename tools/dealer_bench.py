@@ -2,6 +2,7 @@
 before the parties start, and calls its slowest step (`groth16/src/proving_key.rs:47-123`, `.github/workflows/ci.yml:54-67`).
 
 usage: python tools/dealer_bench.py [--quick] [--reps R]      -> ONE JSON line (`bench.py --workload dealer` prints the same)
+       python tools/dealer_bench.py setup_scalars [--reps R]  -> ONE JSON line with the `setup_scalars` entry alone
 
 Keys (per entry: wall per call with a sync on both sides, units / s, the base-field products one unit costs as the
 kernel executes them, and `frac_issue_bound` = products / s over the multiplier's issue bound -- 153.6 G/s for 8 limbs,
@@ -19,6 +20,10 @@ kernel executes them, and `frac_issue_bound` = products / s over the multiplier'
                     slots set) -- all in this process, every path writing into buffers allocated before the clock starts
   witness_deal      ms per witness of the SHA-256 circuit: the former composition (zk_r1cs_qap, zk_bitrev, zk_pss_pack, the
                     witness downloaded, sliced and padded in Python and uploaded again) against zk_groth16_deal_witness
+  setup_scalars     (its own mode) the circuit-specific setup of the SHA-256 circuit in the exponent: groth16.SetupScalars on
+                    the host plus the upload of its five vectors (one run: it takes seconds) against groth16.DeviceSetup
+                    (zk_groth16_setup_scalars, wall clock around a stream sync), the upload of the C matrix it needs, and the
+                    longest column of A, B and C (a host count: what the long-column path of the kernels is there for)
 """
 import json
 import os
@@ -156,6 +161,41 @@ def witness_deal_entry(pp, reps):
             "deal_witness": ms3(timed_spread(pp, lambda: zg.Witness(pp, pp.curve, r1, w_d, 5, dev_r1cs=dev), reps))}
 
 
+def setup_scalars_entry(pp, reps):
+    from zksaas_amd import circom
+    from zksaas_amd import sha256_circuit as sc
+    p = pp.fr.p
+    r1, _ = sc.build(1, 2, p)
+    td = [pow(7, 11 + i, p) for i in range(5)]
+    t0 = time.perf_counter()
+    host = zg.SetupScalars(pp.curve, r1, *td)
+    t1 = time.perf_counter()
+    keep = [pp.upload_fr(v) for v in (host.a_query, host.b_query, host.l_query, host.h_query, host.gamma_abc)]
+    pp.sync()
+    t2 = time.perf_counter()
+    del keep
+    dev = circom.DeviceR1cs(pp, r1)
+    t3 = time.perf_counter()
+    dev.upload_c(r1)
+    pp.sync()
+    t4 = time.perf_counter()
+    got = zg.DeviceSetup(pp, dev, *td).to_host()
+    same = all(getattr(got, k) == getattr(host, k) for k in ("a_query", "b_query", "l_query", "h_query", "gamma_abc"))
+    longest = {}
+    for name, rows in (("a", r1.a), ("b", r1.b), ("c", r1.c)):
+        cnt = {}
+        for row in rows:
+            for _, wire in row:
+                cnt[wire] = cnt.get(wire, 0) + 1
+        top = sorted(cnt.values(), reverse=True)
+        longest[name] = {"nonzeros": sum(top), "longest_columns": top[:4],
+                         "columns_above_heavy_min": sum(1 for v in top if v > zg.SETUP_HEAVY_MIN)}
+    return {"circuit": "sha256", "log_m": dev.log_m, "num_variables": r1.num_variables, "num_constraints": r1.num_constraints,
+            "host_setup_scalars_s": round(t1 - t0, 3), "host_upload_fr_s": round(t2 - t1, 3),
+            "upload_c_matrix_s": round(t4 - t3, 3), "device_setup": ms3(timed_spread(pp, lambda: zg.DeviceSetup(pp, dev, *td), reps)),
+            "device_equals_host": same, "heavy_min": zg.SETUP_HEAVY_MIN, "columns": longest}
+
+
 def entry(dt, units, unit_name, products_per_unit, limbs, **extra):
     e = {"ms": round(dt * 1e3, 4), unit_name + "_per_s": round(units / dt, 1),
          "products_per_" + unit_name: round(products_per_unit, 1),
@@ -268,6 +308,11 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     quick = "--quick" in argv
     reps = int(argv[argv.index("--reps") + 1]) if "--reps" in argv else 5
+    if "setup_scalars" in argv:
+        res = {"workload": "dealer: circuit-specific setup in the exponent (SHA-256 circuit, BN254)",
+               "setup_scalars": setup_scalars_entry(zk.PackedSharingParams("bn254", 2), reps)}
+        print(json.dumps(res), flush=True)
+        return res
     res = {"workload": "dealer (SURVEY.md 8 f1 / f2): CRS share packing, fixed-base multiplication, table build, mask sampling",
            "curves": [run("bn254", quick, reps), run("bls12_381", quick, reps)]}
     print(json.dumps(res), flush=True)

@@ -29,6 +29,7 @@ SYMBOLS = [
     "zk_groth16_prove_host",
     "zk_multi_pairing", "zk_fq12_selftest", "zk_groth16_vk_prepare", "zk_groth16_vk_free", "zk_groth16_verify",
     "zk_base_mul_few", "zk_groth16_deal_masks", "zk_groth16_deal_witness", "zk_groth16_verify_all",
+    "zk_groth16_setup_scalars",
 ]
 
 _lib = None
@@ -212,5 +213,7 @@ def load():
     lib.zk_groth16_deal_masks.argtypes = [vp, i32, i32, vp, vp, u64, vp, vp]
     lib.zk_groth16_deal_witness.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, i32, u64, vp, vp, vp, vp, vp,
                                             C.POINTER(sz), C.POINTER(sz), vp]
+    lib.zk_groth16_setup_scalars.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, i32, vp, sz, vp, vp, vp, vp, vp,
+                                             vp]
     _lib = lib
     return lib

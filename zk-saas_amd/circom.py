@@ -157,8 +157,8 @@ def wtns_to_limbs(src, nl):
 
 
 class DeviceR1cs:
-    """CSR copies of the A and B matrices on the device (C is not needed: the circom reduction sets c = a * b,
-    qap.rs:66-70) and the QAP evaluation kernel."""
+    """CSR copies of the A and B matrices on the device (the prover does not need C: the circom reduction sets c = a * b,
+    qap.rs:66-70) and the QAP evaluation kernel.  The setup does read C: upload_c() / from_csr(..., c_csr) add it."""
 
     def __init__(self, pp, r1cs):
         self.pp = pp
@@ -167,36 +167,48 @@ class DeviceR1cs:
         self.num_variables = r1cs.num_variables
         nc, ni = r1cs.num_constraints, r1cs.num_instance_variables
         self.log_m = max(0, (nc + ni - 1).bit_length())
-        self._mats = []
-        for rows in (r1cs.a, r1cs.b):
-            ptr = np.zeros(nc + 1, dtype=np.uint32)
-            cols, vals = [], []
-            for i, lc in enumerate(rows):
-                for coeff, wire in lc:
-                    cols.append(wire)
-                    vals.append(coeff)
-                ptr[i + 1] = len(cols)
-            cols_d = pp.upload_u32(np.asarray(cols, dtype=np.uint32))
-            ptr_d = pp.upload_u32(ptr)
-            vals_d = pp.upload_fr(vals) if vals else pp.alloc_fr(1)
-            self._mats.append((ptr_d, cols_d, vals_d))
+        self.c_mat = None
+        self._mats = [self._upload_rows(rows) for rows in (r1cs.a, r1cs.b)]
+
+    def _upload_rows(self, rows):
+        pp = self.pp
+        ptr = np.zeros(self.num_constraints + 1, dtype=np.uint32)
+        cols, vals = [], []
+        for i, lc in enumerate(rows):
+            for coeff, wire in lc:
+                cols.append(wire)
+                vals.append(coeff)
+            ptr[i + 1] = len(cols)
+        cols_d = pp.upload_u32(np.asarray(cols, dtype=np.uint32))
+        ptr_d = pp.upload_u32(ptr)
+        vals_d = pp.upload_fr(vals) if vals else pp.alloc_fr(1)
+        return ptr_d, cols_d, vals_d
+
+    def upload_c(self, r1cs):
+        """The third CSR, which zk_groth16_setup_scalars reads (groth16.DeviceSetup); returns self."""
+        if r1cs.num_constraints != self.num_constraints:
+            raise ValueError("C has another number of rows")
+        self.c_mat = self._upload_rows(r1cs.c)
+        return self
 
     @classmethod
-    def from_csr(cls, pp, num_constraints, num_instance_variables, num_variables, a_csr, b_csr):
-        """a_csr / b_csr = (row_ptr uint32 [nc+1], cols uint32, vals uint64 [nnz][limbs] in Montgomery form):
+    def from_csr(cls, pp, num_constraints, num_instance_variables, num_variables, a_csr, b_csr, c_csr=None):
+        """a_csr / b_csr (/ c_csr) = (row_ptr uint32 [nc+1], cols uint32, vals uint64 [nnz][limbs] in Montgomery form):
         for matrices that are produced as arrays (synthetic circuits at scale) rather than Python lists."""
         self = cls.__new__(cls)
         self.pp = pp
         self.num_constraints, self.num_instance_variables = num_constraints, num_instance_variables
         self.num_variables = num_variables
         self.log_m = max(0, (num_constraints + num_instance_variables - 1).bit_length())
-        self._mats = []
-        for ptr, cols, vals in (a_csr, b_csr):
+        def up(csr):
+            ptr, cols, vals = csr
             if len(ptr) != num_constraints + 1 or int(ptr[-1]) != len(cols):
                 raise ValueError("inconsistent CSR arrays")
-            self._mats.append((pp.upload_u32(ptr), pp.upload_u32(cols),
-                               DeviceBuffer.from_numpy(pp, np.ascontiguousarray(vals, dtype=np.uint64))
-                               if len(cols) else pp.alloc_fr(1)))
+            return (pp.upload_u32(ptr), pp.upload_u32(cols),
+                    DeviceBuffer.from_numpy(pp, np.ascontiguousarray(vals, dtype=np.uint64)) if len(cols) else pp.alloc_fr(1))
+
+        self._mats = [up(a_csr), up(b_csr)]
+        self.c_mat = None if c_csr is None else up(c_csr)
         return self
 
     def qap(self, w_d, stream=None):

@@ -799,6 +799,17 @@ int zk_groth16_deal_witness(zk_ctx* ctx, const void* a_row_ptr_d, const void* a_
                                  num_constraints, num_instance, log_m, seed, qap_a_d, qap_b_d, qap_c_d, a_share_d,
                                  ax_share_d, len_a, len_w, S(stream));
 }
+int zk_groth16_setup_scalars(zk_ctx* ctx, const void* a_row_ptr_d, const void* a_col_d, const void* a_val_d,
+                             const void* b_row_ptr_d, const void* b_col_d, const void* b_val_d, const void* c_row_ptr_d,
+                             const void* c_col_d, const void* c_val_d, size_t num_variables, size_t num_constraints,
+                             size_t num_instance, int log_m, const void* trapdoor, size_t tail_zeros, void* a_query_d,
+                             void* b_query_d, void* l_query_d, void* h_query_d, void* gamma_abc_d, void* stream) {
+  CTX_OR_FAIL();
+  const void* const mats[9] = {a_row_ptr_d, a_col_d, a_val_d, b_row_ptr_d, b_col_d, b_val_d, c_row_ptr_d, c_col_d, c_val_d};
+  void* const out[5] = {a_query_d, b_query_d, l_query_d, h_query_d, gamma_abc_d};
+  return e->groth16_setup_scalars(mats, num_variables, num_constraints, num_instance, log_m, trapdoor, tail_zeros, out,
+                                  S(stream));
+}
 int zk_circom_h(zk_ctx* ctx, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
                 const zk_groth16_masks* masks, uint64_t seed, void* h_d, void* stream) {
   CTX_OR_FAIL();

@@ -10,6 +10,7 @@
 #include "engine.hpp"
 #include "groth16.hpp"
 #include "qap.hpp"
+#include "setup.hpp"
 #include "msm.hpp"
 #include "hostpool.hpp"
 #include "points.hpp"
@@ -381,6 +382,7 @@ class Engine : public IEngine {
 #include "engine_points.inc.hpp"     // MSM entry points, group-element PSS / deg_red, front end, wire formats, options
 #include "engine_groth16.inc.hpp"    // circom_h / libsnark_h, prover, batch prover
 #include "engine_dist.inc.hpp"       // zk_dist_*: per-rank collective forms
+#include "engine_setup.inc.hpp"      // zk_groth16_setup_scalars: R1CS and trapdoor -> CRS scalars
 
   int ensure_streams() {
     std::lock_guard<std::mutex> lk(mu_);

@@ -5,11 +5,13 @@ What runs where:
   * host (Python ints, one-off per circuit): R1CS -> QAP evaluation vectors (groth16/src/qap.rs:42-89) and the
     discrete logs of the CRS for a seeded trapdoor (ark-groth16 generate_parameters with CircomReduction, in
     the exponent);
+    (zk_groth16_setup_scalars does the second on the device: DeviceSetup, Crs.from_device_setup);
   * GPU: CRS points and PackedProvingKeyShare (zk_pss_det_pack on the discrete logs + zk_base_mul, because
     det_pack is linear: groth16/src/proving_key.rs:47-123), QAP::pss / pack_from_witness dealing
     (zk_bitrev + zk_pss_pack), and the whole prover (zk_groth16_prove).
 """
 import ctypes as C
+import types
 
 import numpy as np
 
@@ -151,6 +153,49 @@ class SetupScalars:
         self.h_query = [co[i] * n2inv % p for i in range(1, 2 * m, 2)]
 
 
+# A column of A, B or C with more nonzeros than this is summed by workgroups in zk_groth16_setup_scalars, a shorter one by
+# one lane (csrc/setup_impl.hpp SETUP_HEAVY_MIN; tests/test_native_setup.py keeps the two equal).
+SETUP_HEAVY_MIN = 64
+
+
+class DeviceSetup:
+    """SetupScalars on the device (zk_groth16_setup_scalars): the discrete logs of the CRS for a trapdoor as DeviceBuffers
+    a_query [nv], b_query [nv], l_query [nv - ni], h_query [m] and gamma_abc [ni], each but the last followed by
+    `tail_zeros` (default pp.l) zero elements, so that l-chunked views read zeros past the end.  dev_r1cs is a
+    circom.DeviceR1cs that holds the C matrix (upload_c / from_csr(..., c_csr))."""
+
+    def __init__(self, pp, dev_r1cs, alpha, beta, gamma, delta, tau, stream=None, tail_zeros=None):
+        if dev_r1cs.c_mat is None:
+            raise ValueError("the setup reads the C matrix: DeviceR1cs.upload_c(r1cs) or from_csr(..., c_csr)")
+        self.pp, self.curve, self.p = pp, pp.curve, fields.FR[pp.curve]
+        self.alpha, self.beta, self.gamma, self.delta, self.tau = alpha, beta, gamma, delta, tau
+        self.log_m, self.m = dev_r1cs.log_m, 1 << dev_r1cs.log_m
+        self.num_variables, self.num_constraints = dev_r1cs.num_variables, dev_r1cs.num_constraints
+        self.num_instance_variables = dev_r1cs.num_instance_variables
+        nv, ni = self.num_variables, self.num_instance_variables
+        self.tail_zeros = tail = pp.l if tail_zeros is None else int(tail_zeros)
+        self.a_query, self.b_query = pp.alloc_fr(nv + tail), pp.alloc_fr(nv + tail)
+        self.l_query = pp.alloc_fr(max(1, nv - ni + tail))
+        self.h_query = pp.alloc_fr(self.m + tail)
+        self.gamma_abc = pp.alloc_fr(ni)
+        td = np.ascontiguousarray(pp.fr.encode([alpha, beta, gamma, delta, tau]))
+        mats = [b.ptr for mat in (dev_r1cs._mats[0], dev_r1cs._mats[1], dev_r1cs.c_mat) for b in mat]
+        pp._check(pp.lib.zk_groth16_setup_scalars(pp.h, *mats, nv, self.num_constraints, ni, self.log_m, td.ctypes.data, tail,
+                                                  self.a_query.ptr, self.b_query.ptr, self.l_query.ptr, self.h_query.ptr,
+                                                  self.gamma_abc.ptr, stream))
+
+    def to_host(self):
+        """The five vectors as lists of ints, under SetupScalars' attribute names (tests and small tools)."""
+        pp, nv, ni = self.pp, self.num_variables, self.num_instance_variables
+        out = types.SimpleNamespace(**{k: getattr(self, k) for k in ("curve", "p", "alpha", "beta", "gamma", "delta", "tau",
+                                                                     "log_m", "m")})
+        out.a_query, out.b_query = pp.download_fr(self.a_query, nv), pp.download_fr(self.b_query, nv)
+        out.l_query = pp.download_fr(self.l_query, nv - ni)
+        out.h_query = pp.download_fr(self.h_query, self.m)
+        out.gamma_abc = pp.download_fr(self.gamma_abc, ni)
+        return out
+
+
 def _affine_codec(pp, vals, g2):
     """flat coordinate ints -> uint64 rows"""
     per = 4 if g2 else 2
@@ -208,6 +253,46 @@ class Crs:
                              "b_g2_query": q(setup.b_query, ZK_G2), "l_query": q(setup.l_query, ZK_G1),
                              "h_query": q(setup.h_query, ZK_G1)}
         self._make_ct()
+
+    @classmethod
+    def from_device_setup(cls, pp, dsetup, keep_unpacked=False):
+        """What Crs(pp, setup) builds, from a DeviceSetup: the query vectors go from its device buffers straight into det_pack and
+        base_points (a_query and b_query from element 1, l_query and h_query from 0; a short last chunk reads the zero
+        tail), a_query[0] and b_query[0] are one-element views.  No vector crosses the host."""
+        l, frb = pp.l, pp.fr.nbytes
+        nv, ni = dsetup.num_variables, dsetup.num_instance_variables
+        if dsetup.tail_zeros < l - 1:
+            raise ValueError("the DeviceSetup was made with fewer than l - 1 tail zeros")
+
+        def packed(buf, first, count, group):
+            nch = (count + l - 1) // l
+            sh = pp.det_pack(buf.view(first * frb, nch * l * frb), nch)
+            return base_points(pp, group, sh, pp.n * nch), nch
+
+        self = cls.__new__(cls)
+        self.pp, self.setup = pp, dsetup
+        self.s, self.len_a = packed(dsetup.a_query, 1, nv - 1, ZK_G1)
+        self.h, _ = packed(dsetup.b_query, 1, nv - 1, ZK_G1)
+        self.v, _ = packed(dsetup.b_query, 1, nv - 1, ZK_G2)
+        self.w, self.len_w = packed(dsetup.l_query, 0, nv - ni, ZK_G1)
+        self.u, self.len_u = packed(dsetup.h_query, 0, dsetup.m, ZK_G1)
+        nl = pp.fq.nl
+        a0, b0 = dsetup.a_query.view(0, frb), dsetup.b_query.view(0, frb)
+        one = lambda grp, sc, cnt: base_points(pp, grp, sc, cnt).to_numpy().reshape(cnt, -1)
+        self.s1 = np.ascontiguousarray(np.concatenate([
+            one(ZK_G1, a0, 1), one(ZK_G1, b0, 1),
+            one(ZK_G1, pp.upload_fr([dsetup.delta, dsetup.alpha, dsetup.beta]), 3)]).reshape(5, 2 * nl))
+        self.s2 = np.ascontiguousarray(np.concatenate([
+            one(ZK_G2, b0, 1), one(ZK_G2, pp.upload_fr([dsetup.delta, dsetup.beta]), 2)]).reshape(3, 4 * nl))
+        self.unpacked = None
+        if keep_unpacked:
+            self.unpacked = {"a_query": base_points(pp, ZK_G1, dsetup.a_query, nv),
+                             "b_g1_query": base_points(pp, ZK_G1, dsetup.b_query, nv),
+                             "b_g2_query": base_points(pp, ZK_G2, dsetup.b_query, nv),
+                             "l_query": base_points(pp, ZK_G1, dsetup.l_query, nv - ni),
+                             "h_query": base_points(pp, ZK_G1, dsetup.h_query, dsetup.m)}
+        self._make_ct()
+        return self
 
     def precompute(self, pp=None):
         """Fixed-base tables for the five query vectors (zk_msm_precompute): for a service that proves many witnesses
@@ -309,11 +394,17 @@ class ProofMasks:
 
 def verifying_key(pp, setup):
     """ark_groth16::VerifyingKey of a trapdoor setup as affine coordinate ints (verifier side, not the hot path):
-    dict(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1)."""
+    dict(alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1).  `setup`: a SetupScalars, or a DeviceSetup, whose gamma_abc is
+    read from its device buffer."""
     nl = pp.fq.nl
-    g1 = base_points(pp, ZK_G1, pp.upload_fr([setup.alpha] + list(setup.gamma_abc)), 1 + len(setup.gamma_abc))
+    if isinstance(setup, DeviceSetup):
+        ni = setup.num_instance_variables
+        pts = [base_points(pp, ZK_G1, pp.upload_fr([setup.alpha]), 1), base_points(pp, ZK_G1, setup.gamma_abc, ni)]
+        a1 = pp.fq.decode(np.concatenate([b.to_numpy() for b in pts]).reshape(-1, nl))
+    else:
+        g1 = base_points(pp, ZK_G1, pp.upload_fr([setup.alpha] + list(setup.gamma_abc)), 1 + len(setup.gamma_abc))
+        a1 = pp.fq.decode(g1.to_numpy().reshape(-1, nl))
     g2 = base_points(pp, ZK_G2, pp.upload_fr([setup.beta, setup.gamma, setup.delta]), 3)
-    a1 = pp.fq.decode(g1.to_numpy().reshape(-1, nl))
     a2 = pp.fq.decode(g2.to_numpy().reshape(-1, nl))
     p1 = [(a1[2 * i], a1[2 * i + 1]) for i in range(len(a1) // 2)]
     p2 = [((a2[4 * i], a2[4 * i + 1]), (a2[4 * i + 2], a2[4 * i + 3])) for i in range(3)]
