@@ -359,8 +359,9 @@ int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d
  * wire, ser_net.rs:111-120) <-> affine Montgomery points on the device: len x (|Fq| bytes for G1, 2 |Fq| for G2).
  * BN254 / BLS12-377: ark-ec's default flags (little-endian x, bit 7 / 6 of the last byte = y is the larger root /
  * infinity); BLS12-381: the zcash encoding ark-bls12-381 uses (big-endian, c1 || c0, flags in the first byte).
- * Decompression validates like arkworks (x below the modulus, on the curve, consistent flags) and returns
- * ZK_ERR_GENERIC naming the first bad index.  Square roots: the (q + 1) / 4 power for q = 3 mod 4 (BN254, BLS12-381),
+ * Decompression tests what arkworks tests before its subgroup test: x below the modulus, a y on the curve, consistent
+ * flags.  It does NOT test membership in the order-r subgroup, which deserialize_compressed (Validate::Yes) also does:
+ * zk_points_decompress_checked below is the call with that test.  It returns ZK_ERR_GENERIC naming the first bad index.  Square roots: the (q + 1) / 4 power for q = 3 mod 4 (BN254, BLS12-381),
  * Tonelli-Shanks for BLS12-377 (q - 1 = 2^46 t). */
 int zk_points_decompress(zk_ctx* ctx, int group, const void* bytes_d, size_t len, void* out_affine_d, void* stream);
 int zk_points_compress(zk_ctx* ctx, int group, const void* affine_d, size_t len, void* bytes_out_d, void* stream);
@@ -606,7 +607,8 @@ int zk_d_msm_parties(zk_ctx* ctx, int group, const void* bases_d, const void* sc
  * zk_multi_pairing = ark-ec Pairing::multi_pairing: out[i] = final_exp(prod_j miller(P[i][j], Q[i][j])), i < count, j < k.
  * p_affine_d [count][k] G1 affine, q_affine_d [count][k] G2 affine, gt_out_d [count][12] Fq (Montgomery), coefficient
  * order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... = arkworks' Fp12 in memory = snarkjs' [2][3][2] nesting.  An identity in
- * either slot of a pair contributes 1.  Points are taken as given (no curve or subgroup check).  The BN254 final
+ * either slot of a pair contributes 1.  Points are taken as given (no curve or subgroup check; zk_points_subgroup_check
+ * tests a vector of points, and off the subgroups the pairing is not bilinear).  The BN254 final
  * exponentiation raises to the exponent of the Fuentes-Castaneda chain that arkworks and snarkjs use, so the values are
  * theirs; BLS12-381 uses the exact (q^12 - 1) / r.  Returns when the result is in gt_out_d. */
 int zk_multi_pairing(zk_ctx* ctx, const void* p_affine_d, const void* q_affine_d, size_t k, size_t count, void* gt_out_d,
@@ -623,7 +625,8 @@ int zk_fq12_selftest(zk_ctx* ctx, int op, const void* a_d, const void* b_d, size
  * ZK_ERR_BAD_INPUT ("malformed verifying key").  Per proof: acc = abc[0] + sum_i x_i abc[i + 1];
  * ok[i] = (final_exp(miller(A, B) miller(acc, -gamma) miller(C, -delta)) == e(alpha, beta)).  A point of a proof that is
  * not on its curve (or a coordinate that is not below q) gives ok[i] = 0, not an error.  As in verify_proof there is NO
- * G2 subgroup check (nor a G1 one): a caller that needs it decompresses with validation first.  Every step runs on the
+ * G2 subgroup check (nor a G1 one): a caller whose proofs come from outside calls zk_groth16_verify_bytes on their wire
+ * bytes, or zk_points_subgroup_check on the points, instead.  Every step runs on the
  * device; the call returns with ok filled, and its wait honours the option wait_deadline_ms. */
 typedef struct zk_vk zk_vk;
 int zk_groth16_vk_prepare(zk_ctx* ctx, const void* alpha_g1, const void* beta_g2, const void* gamma_g2,
@@ -648,13 +651,45 @@ int zk_groth16_verify(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affine, c
  * zk_groth16_verify is 1", except with probability at most 2^-128 over the seed (a batch with a bad proof is accepted
  * only when the randomizers hit one residue mod r).  As in zk_groth16_verify there is NO subgroup check: outside the
  * subgroups (possible for G2 on both curves and for G1 on BLS12-381) bilinearity does not hold and the two calls may
- * disagree; a caller that needs the check decompresses with validation first.  After a 0, zk_groth16_verify on the same
+ * disagree; a caller whose proofs come from outside calls zk_groth16_verify_all_bytes, which makes the check, instead.
+ * After a 0, zk_groth16_verify on the same
  * arrays says which proofs failed.  WHEN TO USE WHICH (measured on one MI355X): the batch call is the
  * faster one from 4096 proofs on BN254 and from 16384 on BLS12-381 (2.8x / 3.2x at 65536); below 4096 it is 3-8 ms slower
  * than zk_groth16_verify, which also names the bad proof.
  * Every step runs on the device; the call returns with the verdict on the host, and its wait honours wait_deadline_ms. */
 int zk_groth16_verify_all(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affine, const void* public_inputs,
                           size_t n_inputs, size_t count, const uint8_t* seed, int* all_ok, void* gt_out, void* stream);
+
+/* ---- subgroup membership, and verification from wire bytes (BN254 and BLS12-381; BLS12-377: ZK_ERR_BAD_INPUT) ----------
+ * zk_points_subgroup_check = ark-ec's is_in_correct_subgroup_assuming_on_curve after the curve test, on a device vector of
+ * affine Montgomery points [len]: ok_d[i] (device, one byte) = 1 iff both coordinates are below q and the point is the
+ * identity (0, 0) or lies on its curve with [r]P = O.  A point off its curve gives 0 and is never an error; len = 0 launches
+ * nothing.  The tests are those of ark-bn254 / ark-bls12-381 0.4: BN254 G1 has cofactor 1 (the curve equation decides);
+ * BN254 G2 psi(P) = [6x^2]P in the form of eprint 2022/352 4.3 that multiplies by x only; BLS12-381 G2 psi(P) = [x]P;
+ * BLS12-381 G1 phi(P) = -[x^2]P.  Fixed chains of 63 / 64 doublings: no loop bound depends on the point.
+ * Returns when ok_d is written. */
+int zk_points_subgroup_check(zk_ctx* ctx, int group, const void* affine_d, size_t len, uint8_t* ok_d, void* stream);
+/* CanonicalDeserialize::deserialize_compressed with validation (Validate::Yes), per element: decodes exactly as
+ * zk_points_decompress does (both encodings, the same flag rules) and tests the subgroup.  A bad element does not fail
+ * the call: ok_d[i] = 0 and (0, 0) is written for an encoding that does not decode; ok_d[i] = 0 and the decoded point is
+ * kept for a point outside the order-r subgroup; ok_d[i] = 1 otherwise. */
+int zk_points_decompress_checked(zk_ctx* ctx, int group, const void* bytes_d, size_t len, void* out_affine_d, uint8_t* ok_d,
+                                 void* stream);
+/* Groth16::verify_proof after Proof::deserialize_compressed (with validation) and Fr::deserialize_compressed of the
+ * public inputs, all on the device: what a verifier that takes proofs from strangers calls.
+ * proof_bytes (host) = [count][4 |Fq| bytes], exactly what zk_groth16_reconstruct writes as proof_bytes (128 bytes on
+ * BN254, 192 on BLS12-381 in the zcash form); input_bytes (host) = [count][n_inputs][32], little-endian canonical Fr,
+ * WITHOUT the leading 1.  ok[i] = 1 iff A, B and C decode, lie in their order-r subgroups, every input is below r and the
+ * pairing equation of zk_groth16_verify holds.  A defect of any kind gives ok[i] = 0 for that proof only, never an error;
+ * the argument errors are those of zk_groth16_verify.  The bytes are copied up once; two launches decode them into the
+ * arrays zk_groth16_verify stages, whose verdict kernels then run unchanged. */
+int zk_groth16_verify_bytes(zk_ctx* ctx, const zk_vk* vk, const void* proof_bytes, const void* input_bytes, size_t n_inputs,
+                            size_t count, uint8_t* ok, void* stream);
+/* The one randomized verdict of zk_groth16_verify_all from the same bytes: seed, all_ok and gt_out as there.  *all_ok = 0
+ * as soon as any proof fails decoding, the subgroup test or the input range; with every point in its subgroup the
+ * guarantee of zk_groth16_verify_all holds without its limit. */
+int zk_groth16_verify_all_bytes(zk_ctx* ctx, const zk_vk* vk, const void* proof_bytes, const void* input_bytes,
+                                size_t n_inputs, size_t count, const uint8_t* seed, int* all_ok, void* gt_out, void* stream);
 
 #ifdef __cplusplus
 }

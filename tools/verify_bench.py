@@ -1,7 +1,11 @@
 """The verifier timed on one GPU: us per proof of zk_groth16_verify and of zk_groth16_verify_all (one verdict for the batch)
 and us per pairing of zk_multi_pairing (k = 1) at count = 1, 16, 256, 4096, 16384 and 65536 on BN254 and BLS12-381.
 usage: python tools/verify_bench.py [--counts 1,16,...] [--curves bn254,bls12_381] [--reps 7] [--out FILE] [--cpu-oracle]
-                                    [--alternate]
+                                    [--alternate] [--bytes] [--subgroup]
+--bytes alternates zk_groth16_verify (points as given, no subgroup test) with zk_groth16_verify_bytes (decode, subgroup test
+and pairing check from the wire bytes) on the same proofs, rep by rep, and prints per count what the checked call adds and how
+much of that the new kernels' own slot times account for: the rest is host time or a stall.  --subgroup times
+zk_points_subgroup_check per group: points per second.
 --alternate times only the two verifier calls, interleaved rep by rep in one process (per-proof, batch, per-proof, ...) on
 arrays encoded once outside the timed region, so that both see the same clocks and the same neighbours: the yardstick for
 "from which count does the batch call win".  Call a count faster only where the two min-max ranges do not overlap.
@@ -51,7 +55,7 @@ def slots(pp):
     out = {}
     for slot in range(pp.lib.zk_profile_slots()):
         name = pp.lib.zk_profile_name(slot).decode()
-        if not name.startswith("pairing_"):
+        if not name.startswith(("pairing_", "points_subgroup", "points_decompress_checked", "verify_")):
             continue
         ms, units, calls = C.c_double(), C.c_double(), C.c_long()
         pp._check(pp.lib.zk_profile_read(pp.h, slot, C.byref(ms), C.byref(units), C.byref(calls)))
@@ -152,6 +156,84 @@ def run_alternate(curve, counts, reps):
     return rows
 
 
+NEW_KERNELS = ("verify_stage_points_kernel", "verify_stage_inputs_kernel", "verify_valid_and_kernel")
+
+
+def run_bytes(curve, counts, reps):
+    """zk_groth16_verify on the affine points and zk_groth16_verify_bytes on the wire bytes of the same proofs, one warm-up
+    each, then `reps` rounds of (unchecked, bytes); the kernel slots are read in a profiled round of their own"""
+    pp = zk.PackedSharingParams(curve, 2)
+    P = zk.fields.FR[curve]
+    r1, w = small_r1cs(P)
+    setup = zg.SetupScalars(curve, r1, 11, 12, 13, 14, 15)
+    aff, raw = zg.reconstruct(pp, zg.prove(pp, zg.Crs(pp, setup), zg.Witness(pp, curve, r1, w, seed=5), 21, 22, seed=9))
+    pvk = zg.PreparedVk(pp, zg.verifying_key(pp, setup))
+    rows = []
+    for count in counts:
+        proofs = np.ascontiguousarray(np.tile(np.asarray(aff, dtype=np.uint64).reshape(1, -1), (count, 1)))
+        xs = np.ascontiguousarray(np.tile(pp.fr.encode([w[1]]).reshape(1, -1), (count, 1)))
+        pb = np.ascontiguousarray(np.tile(np.frombuffer(raw, dtype=np.uint8), count))
+        xb = np.ascontiguousarray(np.tile(np.frombuffer(int(w[1]).to_bytes(32, "little"), dtype=np.uint8), count))
+        ok = np.zeros(count, dtype=np.uint8)
+
+        def plain():
+            pp._check(pp.lib.zk_groth16_verify(pp.h, pvk.h, proofs.ctypes.data, xs.ctypes.data, 1, count, ok.ctypes.data, None))
+            assert ok.all(), "a valid proof was rejected"
+
+        def checked():
+            pp._check(pp.lib.zk_groth16_verify_bytes(pp.h, pvk.h, pb.ctypes.data, xb.ctypes.data, 1, count, ok.ctypes.data, None))
+            assert ok.all(), "a valid proof was rejected"
+
+        calls = (("zk_groth16_verify", plain), ("zk_groth16_verify_bytes", checked))
+        plain()
+        checked()
+        t = {name: [] for name, _ in calls}
+        for _ in range(reps):
+            for name, fn in calls:
+                t0 = time.perf_counter()
+                fn()
+                t[name].append(time.perf_counter() - t0)
+        ks = {}
+        for name, fn in calls:
+            pp._check(pp.lib.zk_profile_enable(pp.h, 1))
+            fn()
+            ks[name] = slots(pp)
+            pp._check(pp.lib.zk_profile_enable(pp.h, 0))
+            rows.append(row(curve, name + " (alternating)", count, t[name], ks[name]))
+        a, b = statistics.median(t["zk_groth16_verify"]), statistics.median(t["zk_groth16_verify_bytes"])
+        new_ms = sum(ks["zk_groth16_verify_bytes"].get(k, 0.0) for k in NEW_KERNELS) / 1e3
+        acc = {"curve": curve, "count": count, "extra_ms": round((b - a) * 1e3, 3), "new_kernels_ms": round(new_ms, 3),
+               "unaccounted_ms": round((b - a) * 1e3 - new_ms, 3),
+               "unaccounted_share_of_the_call": round(((b - a) * 1e3 - new_ms) / (b * 1e3), 4)}
+        print(json.dumps(acc), flush=True)
+        rows.append(acc)
+    return rows
+
+
+def run_subgroup(curve, counts, reps):
+    """zk_points_subgroup_check on `count` random multiples of the generator, per group: points per second"""
+    pp = zk.PackedSharingParams(curve, 2)
+    rows = []
+    for count in counts:
+        sc = pp.upload_fr([3 + 5 * i for i in range(count)])
+        for group, name in ((ZK_G1, "G1"), (ZK_G2, "G2")):
+            pts = zg.base_points(pp, group, sc, count)
+            okd = zk.DeviceBuffer(pp, count)
+
+            def check():
+                pp._check(pp.lib.zk_points_subgroup_check(pp.h, group, pts.ptr, count, okd.ptr, None))
+
+            ts, k = timed(pp, check, reps)
+            assert okd.to_numpy(dtype=np.uint8)[:count].all(), "a subgroup point was rejected"
+            r = row(curve, "zk_points_subgroup_check " + name, count, ts, k)
+            r["points_per_s"] = round(count / statistics.median(ts))
+            rows.append(r)
+            pts.free()
+            okd.free()
+        sc.free()
+    return rows
+
+
 def row(curve, call, count, ts, kernels):
     med = statistics.median(ts)
     r = {"curve": curve, "call": call, "count": count, "reps": len(ts), "median_ms": round(med * 1e3, 3),
@@ -183,9 +265,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--cpu-oracle", action="store_true")
     ap.add_argument("--alternate", action="store_true")
+    ap.add_argument("--bytes", action="store_true")
+    ap.add_argument("--subgroup", action="store_true")
     a = ap.parse_args()
-    out = {"tool": "tools/verify_bench.py" + (" --alternate" if a.alternate else ""), "reps": a.reps, "rows": []}
+    mode = " --alternate" if a.alternate else " --bytes" if a.bytes else " --subgroup" if a.subgroup else ""
+    out = {"tool": "tools/verify_bench.py" + mode, "reps": a.reps, "rows": []}
     for curve in a.curves.split(","):
+        if a.bytes or a.subgroup:
+            out["rows"] += (run_bytes if a.bytes else run_subgroup)(curve, [int(c) for c in a.counts.split(",")], a.reps)
+            continue
         if a.alternate:
             out["rows"] += run_alternate(curve, [int(c) for c in a.counts.split(",")], a.reps)
             continue

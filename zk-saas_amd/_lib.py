@@ -30,6 +30,7 @@ SYMBOLS = [
     "zk_multi_pairing", "zk_fq12_selftest", "zk_groth16_vk_prepare", "zk_groth16_vk_free", "zk_groth16_verify",
     "zk_base_mul_few", "zk_groth16_deal_masks", "zk_groth16_deal_witness", "zk_groth16_verify_all",
     "zk_groth16_setup_scalars",
+    "zk_points_subgroup_check", "zk_points_decompress_checked", "zk_groth16_verify_bytes", "zk_groth16_verify_all_bytes",
 ]
 
 _lib = None
@@ -215,5 +216,9 @@ def load():
                                             C.POINTER(sz), C.POINTER(sz), vp]
     lib.zk_groth16_setup_scalars.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, i32, vp, sz, vp, vp, vp, vp, vp,
                                              vp]
+    lib.zk_points_subgroup_check.argtypes = [vp, i32, vp, sz, vp, vp]
+    lib.zk_points_decompress_checked.argtypes = [vp, i32, vp, sz, vp, vp, vp]
+    lib.zk_groth16_verify_bytes.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]
+    lib.zk_groth16_verify_all_bytes.argtypes = [vp, vp, vp, vp, sz, sz, vp, C.POINTER(i32), vp, vp]
     _lib = lib
     return lib

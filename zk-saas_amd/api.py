@@ -458,3 +458,24 @@ def fq12_selftest(pp, op, a_d, b_d, length, out=None, stream=None):
     pp._check(pp.lib.zk_fq12_selftest(pp.h, FQ12_OPS[op] if isinstance(op, str) else int(op), _ptr(a_d), _ptr(b_d), length,
                                       out.ptr, stream))
     return out
+
+
+def points_subgroup_check(pp, group, affine_d, length, out=None, stream=None):
+    """zk_points_subgroup_check (ark-ec is_in_correct_subgroup_assuming_on_curve after the curve test): one byte per affine
+    Montgomery point of the device vector [length] -- 1 when both coordinates are below q and the point is the identity
+    (0, 0) or lies in the order-r subgroup, 0 otherwise (also for a point off its curve).  Returns a uint8 array."""
+    out = out or DeviceBuffer(pp, max(1, length))
+    pp._check(pp.lib.zk_points_subgroup_check(pp.h, group, _ptr(affine_d), length, out.ptr, stream))
+    return out.to_numpy(dtype=np.uint8)[:length].copy()
+
+
+def points_decompress_checked(pp, group, bytes_d, length, out=None, stream=None):
+    """zk_points_decompress_checked (CanonicalDeserialize::deserialize_compressed with validation, per element): decodes as
+    zk_points_decompress does and tests the subgroup.  Returns (points, ok): the device vector of affine Montgomery points
+    and a uint8 array -- ok[i] = 0 with (0, 0) written for an invalid encoding, ok[i] = 0 with the decoded point kept for a
+    point outside the subgroup.  A bad element never fails the call."""
+    size = pp.fq.nbytes * (4 if group == ZK_G2 else 2)
+    out = out or DeviceBuffer(pp, max(1, length) * size)
+    ok = DeviceBuffer(pp, max(1, length))
+    pp._check(pp.lib.zk_points_decompress_checked(pp.h, group, _ptr(bytes_d), length, out.ptr, ok.ptr, stream))
+    return out, ok.to_numpy(dtype=np.uint8)[:length].copy()

@@ -741,7 +741,10 @@ static const char* const kSlotNames[zk::PROF_NSLOTS] = {"ntt_pass_kernel", "king
                                                          "pairing_final_exp_kernel", "pairing_rlc_scale_kernel",
                                                          "pairing_rlc_dot_kernel", "pairing_rlc_sum_kernel",
                                                          "pairing_rlc_gamma_kernel", "pairing_rlc_finish_kernel",
-                                                         "pairing_gt_fold_kernel"};
+                                                         "pairing_gt_fold_kernel", "points_subgroup_check_kernel<G1>",
+                                                         "points_subgroup_check_kernel<G2>",
+                                                         "points_decompress_checked_kernel", "verify_stage_points_kernel",
+                                                         "verify_stage_inputs_kernel", "verify_valid_and_kernel"};
 int zk_profile_enable(zk_ctx* ctx, int on) {
   CTX_OR_FAIL();
   e->prof.reset();
@@ -864,6 +867,25 @@ int zk_groth16_verify_all(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affin
                           size_t n_inputs, size_t count, const uint8_t* seed, int* all_ok, void* gt_out, void* stream) {
   PAIRING_OR_FAIL();
   return pr->verify_all(e, vk, proofs_affine, public_inputs, n_inputs, count, seed, all_ok, gt_out, S(stream));
+}
+int zk_points_subgroup_check(zk_ctx* ctx, int group, const void* affine_d, size_t len, uint8_t* ok_d, void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->points_subgroup_check(e, group, affine_d, len, ok_d, S(stream));
+}
+int zk_points_decompress_checked(zk_ctx* ctx, int group, const void* bytes_d, size_t len, void* out_affine_d, uint8_t* ok_d,
+                                 void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->points_decompress_checked(e, group, bytes_d, len, out_affine_d, ok_d, S(stream));
+}
+int zk_groth16_verify_bytes(zk_ctx* ctx, const zk_vk* vk, const void* proof_bytes, const void* input_bytes, size_t n_inputs,
+                            size_t count, uint8_t* ok, void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->verify_bytes(e, vk, proof_bytes, input_bytes, n_inputs, count, ok, S(stream));
+}
+int zk_groth16_verify_all_bytes(zk_ctx* ctx, const zk_vk* vk, const void* proof_bytes, const void* input_bytes, size_t n_inputs,
+                                size_t count, const uint8_t* seed, int* all_ok, void* gt_out, void* stream) {
+  PAIRING_OR_FAIL();
+  return pr->verify_all_bytes(e, vk, proof_bytes, input_bytes, n_inputs, count, seed, all_ok, gt_out, S(stream));
 }
 
 }  // extern "C"

@@ -39,7 +39,10 @@ enum ProfSlot { PROF_NTT_PASS = 0, PROF_KING, PROF_MSM_ACC_G1, PROF_MSM_ACC_G2, 
                 // the verifier (pairing.hpp): Miller loops + group product, then the final exponentiation; units = pairs / groups
                 PROF_MILLER, PROF_FINAL_EXP,
                 // zk_groth16_verify_all (pairing_rlc.hpp): units = proofs, Fr sums, points summed, table rows, Miller values
-                PROF_RLC_SCALE, PROF_RLC_DOT, PROF_RLC_SUM, PROF_RLC_GAMMA, PROF_RLC_FINISH, PROF_GT_FOLD, PROF_NSLOTS };
+                PROF_RLC_SCALE, PROF_RLC_DOT, PROF_RLC_SUM, PROF_RLC_GAMMA, PROF_RLC_FINISH, PROF_GT_FOLD,
+                // subgroup membership and the bytes verifiers' staging (subgroup_impl.hpp): units = points; points; proofs
+                PROF_SUBGROUP_G1, PROF_SUBGROUP_G2, PROF_DECOMPRESS_CHECKED, PROF_STAGE_POINTS, PROF_STAGE_INPUTS,
+                PROF_STAGE_VALID, PROF_NSLOTS };
 
 struct Profiler {
   bool on = false;

@@ -47,6 +47,14 @@ class IPairing {
                      uint8_t* ok, hipStream_t st) = 0;
   virtual int verify_all(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count,
                          const uint8_t* seed, int* all_ok, void* gt_out, hipStream_t st) = 0;
+  // subgroup membership and the verifiers that start from wire bytes (subgroup.hpp, subgroup_impl.hpp)
+  virtual int points_subgroup_check(IEngine* e, int group, const void* affine_d, size_t len, uint8_t* ok_d, hipStream_t st) = 0;
+  virtual int points_decompress_checked(IEngine* e, int group, const void* bytes_d, size_t len, void* out_affine_d, uint8_t* ok_d,
+                                        hipStream_t st) = 0;
+  virtual int verify_bytes(IEngine* e, const zk_vk* vk, const void* proof_bytes, const void* input_bytes, size_t n_inputs,
+                           size_t count, uint8_t* ok, hipStream_t st) = 0;
+  virtual int verify_all_bytes(IEngine* e, const zk_vk* vk, const void* proof_bytes, const void* input_bytes, size_t n_inputs,
+                               size_t count, const uint8_t* seed, int* all_ok, void* gt_out, hipStream_t st) = 0;
 };
 
 IPairing* pairing_bn254();

@@ -284,6 +284,7 @@ __global__ __launch_bounds__(64) void pairing_verify_prep_kernel(
 
 }  // namespace zk
 #include "pairing_rlc.hpp"
+#include "subgroup_impl.hpp"
 namespace zk {
 
 #define ZK_PAIR_HIP(expr)                                \
@@ -309,6 +310,8 @@ class PairingImpl : public IPairing {
     // zk_groth16_verify_all: points (r_i C_i, the levels of the two sums), Fr (r_i, s and s_t), bytes (validity and its
     // levels, the folded byte, the verdict), Fq12 (the group products, the value after the final exponentiation)
     DevBuf rlc_pts, rlc_fr, rlc_bytes, rlc_gt;
+    // the bytes verifiers: the wire bytes (proofs, then inputs) and the staged verdicts (three per proof, then one per proof)
+    DevBuf wire, stage_ok;
     uint8_t host_ok = 0;              // where the verdict and the value land: not the caller's memory, which a call whose
     F2 host_gt[6];                    // wait deadline passed has already given back
   };
@@ -432,42 +435,64 @@ class PairingImpl : public IPairing {
   int verify(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count, uint8_t* ok,
              hipStream_t st) override {
     if (int rc = e->check_wedged()) return rc;
-    if (!vk || vk->curve != CURVE || vk->device != e->device)
-      return e->fail(ZK_ERR_BAD_INPUT, "zk_groth16_verify: the verifying key was prepared for another context");
-    if (n_inputs + 1 != vk->n_abc) return e->fail(ZK_ERR_BAD_INPUT, "malformed verifying key");
+    if (int rc = verify_args(e, vk, n_inputs, "zk_groth16_verify")) return rc;
     if (!count) return ZK_OK;
     if (!proofs || !ok || (n_inputs && !inputs)) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
     if (count > ((size_t)1 << 30)) return e->fail(ZK_ERR_BAD_INPUT, "zk_groth16_verify: count too large");
-    using Proof = ProofAffine<Fq, F2>;
-    static_assert(sizeof(Proof) == 8 * sizeof(Fq), "A | B | C is eight Fq");
     Workspace& ws = workspace(e->device);
     std::lock_guard<std::mutex> g(ws.mu);
-    DevBuf &pr = ws.proofs, &in = ws.inputs, &P = ws.P, &Q = ws.Q, &mill = ws.mill, &val = ws.valid, &okd = ws.ok;
-    ZK_PAIR_HIP(pr.ensure(count * sizeof(Proof)));
-    ZK_PAIR_HIP(in.ensure(count * n_inputs * sizeof(Fr) + 1));
-    ZK_PAIR_HIP(P.ensure(3 * count * sizeof(Affine<Fq>)));
-    ZK_PAIR_HIP(Q.ensure(3 * count * sizeof(Affine<F2>)));
-    ZK_PAIR_HIP(mill.ensure(3 * count * 6 * sizeof(F2)));
-    ZK_PAIR_HIP(val.ensure(count));
-    ZK_PAIR_HIP(okd.ensure(count));
-    ZK_PAIR_HIP(hipMemcpyAsync(pr.p, proofs, count * sizeof(Proof), hipMemcpyHostToDevice, st));
-    if (n_inputs) ZK_PAIR_HIP(hipMemcpyAsync(in.p, inputs, count * n_inputs * sizeof(Fr), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((pairing_verify_prep_kernel<PP, FrP>), dim3((unsigned)count), dim3(64), 0, st,
-                       (const Proof*)pr.p, (const Fr*)in.p, n_inputs, (const Affine<Fq>*)vk->abc_d,
-                       (const XYZZ<Fq>*)vk->abc_table_d,
-                       (const Affine<F2>*)vk->neg_gamma_d, (const Affine<F2>*)vk->neg_delta_d, B1, count, (Affine<Fq>*)P.p,
-                       (Affine<F2>*)Q.p, (uint8_t*)val.p);
-    int rc = launch(e, P.p, Q.p, 3, count, (F2*)mill.p, nullptr, (const F2*)vk->alpha_beta_d, (const uint8_t*)val.p,
-                    (uint8_t*)okd.p, st);
-    if (!rc) {
-      hipError_t h = hipMemcpyAsync(ok, okd.p, count, hipMemcpyDeviceToHost, st);
-      if (h != hipSuccess) rc = e->hip_fail(h, "zk_groth16_verify: copy of the verdicts");
-    }
-    const int wrc = wait(e, st, "zk_groth16_verify");      // also on an error path: the workspace is handed on after it
-    return rc ? rc : wrc;
+    if (int rc = verify_ensure(e, ws, n_inputs, count)) return rc;
+    ZK_PAIR_HIP(hipMemcpyAsync(ws.proofs.p, proofs, count * sizeof(Proof), hipMemcpyHostToDevice, st));
+    if (n_inputs) ZK_PAIR_HIP(hipMemcpyAsync(ws.inputs.p, inputs, count * n_inputs * sizeof(Fr), hipMemcpyHostToDevice, st));
+    return verify_run(e, vk, ws, n_inputs, count, nullptr, ok, st, "zk_groth16_verify");
   }
 
  private:
+  using Proof = ProofAffine<Fq, F2>;
+  static_assert(sizeof(Proof) == 8 * sizeof(Fq), "A | B | C is eight Fq");
+  static constexpr bool ZCASH = CURVE == ZK_BLS12_381;          // the point encoding of the curve's arkworks crate
+  static constexpr size_t PROOF_BYTES = 4 * PointCodec<Fq>::SIZE, INPUT_BYTES = 32;
+
+  int verify_args(IEngine* e, const zk_vk* vk, size_t n_inputs, const char* what) {
+    if (!vk || vk->curve != CURVE || vk->device != e->device)
+      return e->fail(ZK_ERR_BAD_INPUT, std::string(what) + ": the verifying key was prepared for another context");
+    if (n_inputs + 1 != vk->n_abc) return e->fail(ZK_ERR_BAD_INPUT, "malformed verifying key");
+    return ZK_OK;
+  }
+  int verify_ensure(IEngine* e, Workspace& ws, size_t n_inputs, size_t count) {
+    ZK_PAIR_HIP(ws.proofs.ensure(count * sizeof(Proof)));
+    ZK_PAIR_HIP(ws.inputs.ensure(count * n_inputs * sizeof(Fr) + 1));
+    ZK_PAIR_HIP(ws.P.ensure(3 * count * sizeof(Affine<Fq>)));
+    ZK_PAIR_HIP(ws.Q.ensure(3 * count * sizeof(Affine<F2>)));
+    ZK_PAIR_HIP(ws.mill.ensure(3 * count * 6 * sizeof(F2)));
+    ZK_PAIR_HIP(ws.valid.ensure(count));
+    ZK_PAIR_HIP(ws.ok.ensure(count));
+    return ZK_OK;
+  }
+  // The verdict stages of zk_groth16_verify over the proofs and inputs staged in the workspace (held by the caller).  valid0
+  // (device, one byte per proof; null from the host-pointer entry point) joins the validity bytes the prep kernel writes.
+  int verify_run(IEngine* e, const zk_vk* vk, Workspace& ws, size_t n_inputs, size_t count, const uint8_t* valid0, uint8_t* ok,
+                 hipStream_t st, const char* what) {
+    hipLaunchKernelGGL((pairing_verify_prep_kernel<PP, FrP>), dim3((unsigned)count), dim3(64), 0, st,
+                       (const Proof*)ws.proofs.p, (const Fr*)ws.inputs.p, n_inputs, (const Affine<Fq>*)vk->abc_d,
+                       (const XYZZ<Fq>*)vk->abc_table_d,
+                       (const Affine<F2>*)vk->neg_gamma_d, (const Affine<F2>*)vk->neg_delta_d, B1, count, (Affine<Fq>*)ws.P.p,
+                       (Affine<F2>*)ws.Q.p, (uint8_t*)ws.valid.p);
+    if (valid0) valid_and(e, (uint8_t*)ws.valid.p, valid0, count, st);
+    int rc = launch(e, ws.P.p, ws.Q.p, 3, count, (F2*)ws.mill.p, nullptr, (const F2*)vk->alpha_beta_d, (const uint8_t*)ws.valid.p,
+                    (uint8_t*)ws.ok.p, st);
+    if (!rc) {
+      hipError_t h = hipMemcpyAsync(ok, ws.ok.p, count, hipMemcpyDeviceToHost, st);
+      if (h != hipSuccess) rc = e->hip_fail(h, (std::string(what) + ": copy of the verdicts").c_str());
+    }
+    const int wrc = wait(e, st, what);      // also on an error path: the workspace is handed on after it
+    return rc ? rc : wrc;
+  }
+  static void valid_and(IEngine* e, uint8_t* valid, const uint8_t* valid0, size_t count, hipStream_t st) {
+    ProfScope ps(e->prof, PROF_STAGE_VALID, st, (double)count);
+    hipLaunchKernelGGL(verify_valid_and_kernel<PP>, dim3((unsigned)div256(count)), dim3(256), 0, st, valid, valid0, count);
+  }
+
   static size_t div256(size_t n) { return (n + 255) / 256; }
   // the sum of in[0 .. n) (and the AND of vin[0 .. n)) by pairing_rlc_sum_kernel, 256 to 1 per launch and at least once;
   // a / b (va / vb) take the levels in turn: a holds div256(n) entries, b div256(div256(n))
@@ -486,14 +511,15 @@ class PairingImpl : public IPairing {
     return in;
   }
 
- public:
-  int verify_all(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count,
-                 const uint8_t* seed, int* all_ok, void* gt_out, hipStream_t st) override {
-    if (int rc = e->check_wedged()) return rc;
-    if (!vk || vk->curve != CURVE || vk->device != e->device)
-      return e->fail(ZK_ERR_BAD_INPUT, "zk_groth16_verify_all: the verifying key was prepared for another context");
-    if (n_inputs + 1 != vk->n_abc) return e->fail(ZK_ERR_BAD_INPUT, "malformed verifying key");
-    if (!all_ok) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+ private:
+  // what both batch entry points do before they stage: the argument errors, the empty batch, the randomizer key
+  // (returns 1 when the call is already answered)
+  int verify_all_begin(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count,
+                       const uint8_t* seed, int* all_ok, void* gt_out, const char* what, RlcKey* key, int* rc_out) {
+    *rc_out = ZK_OK;
+    if (int rc = e->check_wedged()) return *rc_out = rc, 1;
+    if (int rc = verify_args(e, vk, n_inputs, what)) return *rc_out = rc, 1;
+    if (!all_ok) return *rc_out = e->fail(ZK_ERR_BAD_INPUT, "null pointer"), 1;
     if (!count) {
       *all_ok = 1;
       if (gt_out) {
@@ -501,57 +527,73 @@ class PairingImpl : public IPairing {
         for (int i = 0; i < 6; i++) one[i] = i ? F2::zero() : F2::one();
         memcpy(gt_out, one, sizeof(one));
       }
-      return ZK_OK;
+      return 1;
     }
-    if (!proofs || (n_inputs && !inputs)) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
-    if (count > ((size_t)1 << 30)) return e->fail(ZK_ERR_BAD_INPUT, "zk_groth16_verify_all: count too large");
+    if (!proofs || (n_inputs && !inputs)) return *rc_out = e->fail(ZK_ERR_BAD_INPUT, "null pointer"), 1;
+    if (count > ((size_t)1 << 30)) return *rc_out = e->fail(ZK_ERR_BAD_INPUT, std::string(what) + ": count too large"), 1;
     uint8_t drawn[32];
     if (!seed) {
       FILE* f = fopen("/dev/urandom", "rb");
       const size_t got = f ? fread(drawn, 1, sizeof(drawn), f) : 0;
       if (f) fclose(f);
-      if (got != sizeof(drawn)) return e->fail(ZK_ERR_GENERIC, "cannot read /dev/urandom for the batch check's randomizers");
+      if (got != sizeof(drawn))
+        return *rc_out = e->fail(ZK_ERR_GENERIC, "cannot read /dev/urandom for the batch check's randomizers"), 1;
       seed = drawn;
     }
-    const RlcKey key = rlc_key(seed);
-    using Proof = ProofAffine<Fq, F2>;
-    using Pt = XYZZ<Fq>;
-    const size_t n_abc = vk->n_abc, npairs = count + 3;
-    const GtFoldPlan plan = gt_fold_plan(npairs);
+    *key = rlc_key(seed);
+    return 0;
+  }
+  struct RlcSizes {
+    size_t n_abc, npairs, c1, c2, gblk, g1, g2;
+    GtFoldPlan plan;
+  };
+  static RlcSizes rlc_sizes(const zk_vk* vk, size_t count) {
+    RlcSizes z;
+    z.n_abc = vk->n_abc, z.npairs = count + 3;
+    z.plan = gt_fold_plan(z.npairs);
     // r_i C_i | the two levels of their sum | the gamma kernel's partial sums (+ s alpha) | the two levels of theirs
-    const size_t c1 = div256(count), c2 = div256(c1), gblk = (n_abc + RLC_GAMMA_ROWS - 1) / RLC_GAMMA_ROWS, g1 = div256(gblk),
-                 g2 = div256(g1);
-    Workspace& ws = workspace(e->device);
-    std::lock_guard<std::mutex> g(ws.mu);
+    z.c1 = div256(count), z.c2 = div256(z.c1), z.gblk = (z.n_abc + RLC_GAMMA_ROWS - 1) / RLC_GAMMA_ROWS, z.g1 = div256(z.gblk),
+    z.g2 = div256(z.g1);
+    return z;
+  }
+  int verify_all_ensure(IEngine* e, Workspace& ws, const RlcSizes& z, size_t n_inputs, size_t count) {
+    using Pt = XYZZ<Fq>;
     ZK_PAIR_HIP(ws.proofs.ensure(count * sizeof(Proof)));
     ZK_PAIR_HIP(ws.inputs.ensure(count * n_inputs * sizeof(Fr) + 1));
-    ZK_PAIR_HIP(ws.P.ensure(npairs * sizeof(Affine<Fq>)));
-    ZK_PAIR_HIP(ws.Q.ensure(npairs * sizeof(Affine<F2>)));
-    ZK_PAIR_HIP(ws.mill.ensure(npairs * 6 * sizeof(F2)));
-    ZK_PAIR_HIP(ws.rlc_pts.ensure((count + c1 + c2 + gblk + 1 + g1 + g2) * sizeof(Pt)));
-    ZK_PAIR_HIP(ws.rlc_fr.ensure((count + n_abc) * sizeof(Fr)));
-    ZK_PAIR_HIP(ws.rlc_bytes.ensure(count + c1 + c2 + 2));
-    ZK_PAIR_HIP(ws.rlc_gt.ensure((plan.G + 1) * 6 * sizeof(F2)));
+    ZK_PAIR_HIP(ws.P.ensure(z.npairs * sizeof(Affine<Fq>)));
+    ZK_PAIR_HIP(ws.Q.ensure(z.npairs * sizeof(Affine<F2>)));
+    ZK_PAIR_HIP(ws.mill.ensure(z.npairs * 6 * sizeof(F2)));
+    ZK_PAIR_HIP(ws.rlc_pts.ensure((count + z.c1 + z.c2 + z.gblk + 1 + z.g1 + z.g2) * sizeof(Pt)));
+    ZK_PAIR_HIP(ws.rlc_fr.ensure((count + z.n_abc) * sizeof(Fr)));
+    ZK_PAIR_HIP(ws.rlc_bytes.ensure(count + z.c1 + z.c2 + 2));
+    ZK_PAIR_HIP(ws.rlc_gt.ensure((z.plan.G + 1) * 6 * sizeof(F2)));
+    return ZK_OK;
+  }
+  // The verdict stages of zk_groth16_verify_all over the proofs and inputs staged in the workspace (held by the caller); rc is
+  // what the staging left (nothing is launched after an error, the wait is made all the same).  valid0 (device, one byte per
+  // proof; null from the host-pointer entry point) joins the validity bytes before the tree sum folds them.
+  int verify_all_run(IEngine* e, const zk_vk* vk, Workspace& ws, const RlcSizes& z, const RlcKey& key, size_t n_inputs, size_t count,
+                     const uint8_t* valid0, int rc, int* all_ok, void* gt_out, hipStream_t st, const char* what) {
+    using Pt = XYZZ<Fq>;
+    const size_t n_abc = z.n_abc, npairs = z.npairs, c1 = z.c1, c2 = z.c2, gblk = z.gblk, g1 = z.g1;
+    const GtFoldPlan& plan = z.plan;
     Pt *cx = (Pt*)ws.rlc_pts.p, *ca = cx + count, *cb = ca + c1, *gpart = cb + c2, *ga = gpart + gblk + 1, *gb = ga + g1;
     Fr *rfr = (Fr*)ws.rlc_fr.p, *sdot = rfr + count;
     uint8_t *valid = (uint8_t*)ws.rlc_bytes.p, *va = valid + count, *vb = va + c1, *all_valid = vb + c2, *okd = all_valid + 1;
     F2 *gfold = (F2*)ws.rlc_gt.p, *gt_d = gfold + plan.G * 6;
     Affine<Fq>* P = (Affine<Fq>*)ws.P.p;
     Affine<F2>* Q = (Affine<F2>*)ws.Q.p;
-    int rc = ZK_OK;
-    auto step = [&](hipError_t h, const char* what) {
-      if (!rc && h != hipSuccess) rc = e->hip_fail(h, what);
+    const std::string w(what);
+    auto step = [&](hipError_t h, const char* part) {
+      if (!rc && h != hipSuccess) rc = e->hip_fail(h, (w + part).c_str());
     };
-    step(hipMemcpyAsync(ws.proofs.p, proofs, count * sizeof(Proof), hipMemcpyHostToDevice, st), "zk_groth16_verify_all: copy of the proofs");
-    if (n_inputs)
-      step(hipMemcpyAsync(ws.inputs.p, inputs, count * n_inputs * sizeof(Fr), hipMemcpyHostToDevice, st),
-           "zk_groth16_verify_all: copy of the public inputs");
     if (!rc) {
       {
         ProfScope ps(e->prof, PROF_RLC_SCALE, st, (double)count);
         hipLaunchKernelGGL((pairing_rlc_scale_kernel<PP, FrP>), dim3((unsigned)div256(2 * count)), dim3(256), 0, st,
                            (const Proof*)ws.proofs.p, key, B1, count, P, Q, cx, rfr, valid);
       }
+      if (valid0) valid_and(e, valid, valid0, count, st);
       {
         ProfScope ps(e->prof, PROF_RLC_DOT, st, (double)n_abc);
         hipLaunchKernelGGL(pairing_rlc_dot_kernel<FrP>, dim3((unsigned)n_abc), dim3(256), 0, st, (const Fr*)rfr,
@@ -586,15 +628,142 @@ class PairingImpl : public IPairing {
         hipLaunchKernelGGL(pairing_final_exp_kernel<PP>, dim3(1), dim3(256), 0, st, (const F2*)gfold, plan.G, (size_t)1, digits(),
                            gt_d, (const F2*)vk->one_d, (const uint8_t*)all_valid, okd);
       }
-      step(hipGetLastError(), "zk_groth16_verify_all: launch");
-      step(hipMemcpyAsync(&ws.host_ok, okd, 1, hipMemcpyDeviceToHost, st), "zk_groth16_verify_all: copy of the verdict");
-      if (gt_out) step(hipMemcpyAsync(ws.host_gt, gt_d, sizeof(ws.host_gt), hipMemcpyDeviceToHost, st), "zk_groth16_verify_all: copy of the value");
+      step(hipGetLastError(), ": launch");
+      step(hipMemcpyAsync(&ws.host_ok, okd, 1, hipMemcpyDeviceToHost, st), ": copy of the verdict");
+      if (gt_out) step(hipMemcpyAsync(ws.host_gt, gt_d, sizeof(ws.host_gt), hipMemcpyDeviceToHost, st), ": copy of the value");
     }
-    const int wrc = wait(e, st, "zk_groth16_verify_all");      // also on an error path: the workspace is handed on after it
+    const int wrc = wait(e, st, what);      // also on an error path: the workspace is handed on after it
     if (rc || wrc) return rc ? rc : wrc;
     *all_ok = ws.host_ok != 0;
     if (gt_out) memcpy(gt_out, ws.host_gt, sizeof(ws.host_gt));
     return ZK_OK;
+  }
+
+  // Staging of the bytes verifiers: the wire bytes go up in one buffer (proofs, then inputs), two launches leave the
+  // ProofAffine array, the Montgomery inputs and one validity byte per proof in the workspace.  Returns the validity bytes.
+  int stage_ensure(IEngine* e, Workspace& ws, size_t n_inputs, size_t count) {
+    ZK_PAIR_HIP(ws.wire.ensure(count * (PROOF_BYTES + n_inputs * INPUT_BYTES)));
+    ZK_PAIR_HIP(ws.stage_ok.ensure(4 * count));
+    return ZK_OK;
+  }
+  const uint8_t* stage(IEngine* e, Workspace& ws, const void* proof_bytes, const void* input_bytes, size_t n_inputs, size_t count,
+                       hipStream_t st, const char* what, int* rc) {
+    uint8_t *wire = (uint8_t*)ws.wire.p, *wire_in = wire + count * PROOF_BYTES;
+    uint8_t *pok = (uint8_t*)ws.stage_ok.p, *valid0 = pok + 3 * count;
+    const std::string w(what);
+    auto step = [&](hipError_t h, const char* part) {
+      if (!*rc && h != hipSuccess) *rc = e->hip_fail(h, (w + part).c_str());
+    };
+    step(hipMemcpyAsync(wire, proof_bytes, count * PROOF_BYTES, hipMemcpyHostToDevice, st), ": copy of the proof bytes");
+    if (n_inputs)
+      step(hipMemcpyAsync(wire_in, input_bytes, count * n_inputs * INPUT_BYTES, hipMemcpyHostToDevice, st), ": copy of the input bytes");
+    if (*rc) return valid0;
+    const size_t nb = (count + 63) / 64 * 64;
+    {
+      ProfScope ps(e->prof, PROF_STAGE_POINTS, st, (double)count);
+      hipLaunchKernelGGL(verify_stage_points_kernel<PP>, dim3((unsigned)((nb + 2 * count + 63) / 64)), dim3(64), 0, st,
+                         (const uint8_t*)wire, count, nb, B1, ZCASH ? 1 : 0, (Proof*)ws.proofs.p, pok);
+    }
+    {
+      ProfScope ps(e->prof, PROF_STAGE_INPUTS, st, (double)count);
+      hipLaunchKernelGGL(verify_stage_inputs_kernel<FrP>, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, (const uint8_t*)wire_in,
+                         n_inputs, count, (const uint8_t*)pok, (Fr*)ws.inputs.p, valid0);
+    }
+    return valid0;
+  }
+
+ public:
+  int verify_all(IEngine* e, const zk_vk* vk, const void* proofs, const void* inputs, size_t n_inputs, size_t count,
+                 const uint8_t* seed, int* all_ok, void* gt_out, hipStream_t st) override {
+    const char* what = "zk_groth16_verify_all";
+    RlcKey key;
+    int rc = ZK_OK;
+    if (verify_all_begin(e, vk, proofs, inputs, n_inputs, count, seed, all_ok, gt_out, what, &key, &rc)) return rc;
+    const RlcSizes z = rlc_sizes(vk, count);
+    Workspace& ws = workspace(e->device);
+    std::lock_guard<std::mutex> g(ws.mu);
+    if (int erc = verify_all_ensure(e, ws, z, n_inputs, count)) return erc;
+    auto step = [&](hipError_t h, const char* part) {
+      if (!rc && h != hipSuccess) rc = e->hip_fail(h, part);
+    };
+    step(hipMemcpyAsync(ws.proofs.p, proofs, count * sizeof(Proof), hipMemcpyHostToDevice, st), "zk_groth16_verify_all: copy of the proofs");
+    if (n_inputs)
+      step(hipMemcpyAsync(ws.inputs.p, inputs, count * n_inputs * sizeof(Fr), hipMemcpyHostToDevice, st),
+           "zk_groth16_verify_all: copy of the public inputs");
+    return verify_all_run(e, vk, ws, z, key, n_inputs, count, nullptr, rc, all_ok, gt_out, st, what);
+  }
+
+  // ---- subgroup membership, checked decompression, the verifiers from wire bytes
+  int points_subgroup_check(IEngine* e, int group, const void* affine_d, size_t len, uint8_t* ok_d, hipStream_t st) override {
+    if (int rc = e->check_wedged()) return rc;
+    if (group != ZK_G1 && group != ZK_G2) return e->fail(ZK_ERR_BAD_INPUT, "zk_points_subgroup_check: group is ZK_G1 or ZK_G2");
+    if (!len) return ZK_OK;
+    if (!affine_d || !ok_d) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (len > ((size_t)1 << 36)) return e->fail(ZK_ERR_BAD_INPUT, "zk_points_subgroup_check: len too large");
+    const dim3 grid((unsigned)((len + 63) / 64));
+    {
+      ProfScope ps(e->prof, group == ZK_G2 ? PROF_SUBGROUP_G2 : PROF_SUBGROUP_G1, st, (double)len);
+      if (group == ZK_G2)
+        hipLaunchKernelGGL((points_subgroup_check_kernel<PP, true>), grid, dim3(64), 0, st, (const Affine<F2>*)affine_d, len, B1, ok_d);
+      else
+        hipLaunchKernelGGL((points_subgroup_check_kernel<PP, false>), grid, dim3(64), 0, st, (const Affine<Fq>*)affine_d, len, B1, ok_d);
+    }
+    ZK_PAIR_HIP(hipGetLastError());
+    return wait(e, st, "zk_points_subgroup_check");
+  }
+  int points_decompress_checked(IEngine* e, int group, const void* bytes_d, size_t len, void* out_affine_d, uint8_t* ok_d,
+                                hipStream_t st) override {
+    if (int rc = e->check_wedged()) return rc;
+    if (group != ZK_G1 && group != ZK_G2) return e->fail(ZK_ERR_BAD_INPUT, "zk_points_decompress_checked: group is ZK_G1 or ZK_G2");
+    if (!len) return ZK_OK;
+    if (!bytes_d || !out_affine_d || !ok_d) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (len > ((size_t)1 << 36)) return e->fail(ZK_ERR_BAD_INPUT, "zk_points_decompress_checked: len too large");
+    const dim3 grid((unsigned)((len + 63) / 64));
+    {
+      ProfScope ps(e->prof, PROF_DECOMPRESS_CHECKED, st, (double)len);
+      if (group == ZK_G2)
+        hipLaunchKernelGGL((points_decompress_checked_kernel<PP, true>), grid, dim3(64), 0, st, (const uint8_t*)bytes_d, len, B1,
+                           ZCASH ? 1 : 0, (Affine<F2>*)out_affine_d, ok_d);
+      else
+        hipLaunchKernelGGL((points_decompress_checked_kernel<PP, false>), grid, dim3(64), 0, st, (const uint8_t*)bytes_d, len, B1,
+                           ZCASH ? 1 : 0, (Affine<Fq>*)out_affine_d, ok_d);
+    }
+    ZK_PAIR_HIP(hipGetLastError());
+    return wait(e, st, "zk_points_decompress_checked");
+  }
+  int verify_bytes(IEngine* e, const zk_vk* vk, const void* proof_bytes, const void* input_bytes, size_t n_inputs, size_t count,
+                   uint8_t* ok, hipStream_t st) override {
+    const char* what = "zk_groth16_verify_bytes";
+    if (int rc = e->check_wedged()) return rc;
+    if (int rc = verify_args(e, vk, n_inputs, what)) return rc;
+    if (!count) return ZK_OK;
+    if (!proof_bytes || !ok || (n_inputs && !input_bytes)) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (count > ((size_t)1 << 30)) return e->fail(ZK_ERR_BAD_INPUT, "zk_groth16_verify_bytes: count too large");
+    Workspace& ws = workspace(e->device);
+    std::lock_guard<std::mutex> g(ws.mu);
+    if (int rc = verify_ensure(e, ws, n_inputs, count)) return rc;
+    if (int rc = stage_ensure(e, ws, n_inputs, count)) return rc;
+    int rc = ZK_OK;
+    const uint8_t* valid0 = stage(e, ws, proof_bytes, input_bytes, n_inputs, count, st, what, &rc);
+    if (rc) {
+      (void)wait(e, st, what);      // the workspace is handed on after it
+      return rc;
+    }
+    return verify_run(e, vk, ws, n_inputs, count, valid0, ok, st, what);
+  }
+  int verify_all_bytes(IEngine* e, const zk_vk* vk, const void* proof_bytes, const void* input_bytes, size_t n_inputs, size_t count,
+                       const uint8_t* seed, int* all_ok, void* gt_out, hipStream_t st) override {
+    const char* what = "zk_groth16_verify_all_bytes";
+    RlcKey key;
+    int rc = ZK_OK;
+    if (verify_all_begin(e, vk, proof_bytes, input_bytes, n_inputs, count, seed, all_ok, gt_out, what, &key, &rc)) return rc;
+    const RlcSizes z = rlc_sizes(vk, count);
+    Workspace& ws = workspace(e->device);
+    std::lock_guard<std::mutex> g(ws.mu);
+    if (int erc = verify_all_ensure(e, ws, z, n_inputs, count)) return erc;
+    if (int erc = stage_ensure(e, ws, n_inputs, count)) return erc;
+    const uint8_t* valid0 = stage(e, ws, proof_bytes, input_bytes, n_inputs, count, st, what, &rc);
+    return verify_all_run(e, vk, ws, z, key, n_inputs, count, valid0, rc, all_ok, gt_out, st, what);
   }
 };
 

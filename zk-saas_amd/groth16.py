@@ -442,7 +442,8 @@ class PreparedVk:
 def verify(pp, pvk, proofs, public_inputs, stream=None):
     """zk_groth16_verify (ark_groth16 Groth16::verify_proof, sha256.rs:400-415) on the device.  proofs: a list of
     reconstruct()'s `affine` arrays (or one [count][8 nl] array); public_inputs: per proof the list of Fr ints without
-    the leading 1.  Returns list[bool]; a proof with a point off its curve is False.  No subgroup check is made."""
+    the leading 1.  Returns list[bool]; a proof with a point off its curve is False.  No subgroup check is made: points that
+    arrive from outside go through verify_bytes() or api.points_subgroup_check() first."""
     nl = pp.fq.nl
     pr = np.ascontiguousarray(np.asarray(proofs, dtype=np.uint64).reshape(-1, 8 * nl))
     count = pr.shape[0]
@@ -484,6 +485,49 @@ def verify_all(pp, pvk, proofs, public_inputs, seed=None, stream=None, want_gt=F
     gt = np.zeros(12 * nl, dtype=np.uint64)
     pp._check(pp.lib.zk_groth16_verify_all(pp.h, pvk.h, pr.ctypes.data if count else None, xs.ctypes.data if xs.size else None,
                                            n_inputs, count, sd, C.byref(ok), gt.ctypes.data if want_gt else None, stream))
+    return (bool(ok.value), pp.fq.decode(gt.reshape(12, nl))) if want_gt else bool(ok.value)
+
+
+def _wire_batch(pp, pvk, proof_bytes, input_bytes):
+    """(proofs [count][4 |Fq|] uint8, inputs uint8, n_inputs, count) of a bytes verifier call.  proof_bytes: one bytes object
+    per proof (Proof::serialize_compressed) or their concatenation; input_bytes: per proof its public inputs as one bytes object
+    of 32-byte little-endian Fr values (without the leading 1), or the concatenation over the batch."""
+    size = 4 * pp.fq.nbytes
+    pb = b"".join(bytes(b) for b in proof_bytes) if isinstance(proof_bytes, (list, tuple)) else bytes(proof_bytes)
+    ib = b"".join(bytes(b) for b in input_bytes) if isinstance(input_bytes, (list, tuple)) else bytes(input_bytes)
+    if len(pb) % size:
+        raise ValueError("a proof is %d bytes" % size)
+    count, n_inputs = len(pb) // size, pvk.n_abc - 1
+    if len(ib) != count * n_inputs * 32:
+        raise ValueError("every proof takes %d public inputs of 32 bytes" % n_inputs)
+    return np.frombuffer(pb, dtype=np.uint8), np.frombuffer(ib, dtype=np.uint8), n_inputs, count
+
+
+def verify_bytes(pp, pvk, proof_bytes, input_bytes, stream=None):
+    """zk_groth16_verify_bytes (Groth16::verify_proof after Proof::deserialize_compressed with validation): decode, subgroup
+    test and pairing check on the device from the wire bytes (see _wire_batch for the two arguments).  Returns list[bool];
+    a proof with a point that does not decode or lies outside its subgroup, or with an input not below r, is False."""
+    pb, ib, n_inputs, count = _wire_batch(pp, pvk, proof_bytes, input_bytes)
+    ok = np.zeros(max(1, count), dtype=np.uint8)
+    pp._check(pp.lib.zk_groth16_verify_bytes(pp.h, pvk.h, pb.ctypes.data if count else None, ib.ctypes.data if ib.size else None,
+                                             n_inputs, count, ok.ctypes.data, stream))
+    return [bool(v) for v in ok[:count]]
+
+
+def verify_all_bytes(pp, pvk, proof_bytes, input_bytes, seed=None, stream=None, want_gt=False):
+    """zk_groth16_verify_all_bytes: the one randomized verdict of verify_all() from the wire bytes; False as soon as any
+    proof fails decoding, the subgroup test or the input range.  seed and want_gt as in verify_all()."""
+    pb, ib, n_inputs, count = _wire_batch(pp, pvk, proof_bytes, input_bytes)
+    sd = None
+    if seed is not None:
+        sd = bytes(seed)
+        if len(sd) != 32:
+            raise ValueError("the seed is 32 bytes")
+    nl = pp.fq.nl
+    ok = C.c_int(0)
+    gt = np.zeros(12 * nl, dtype=np.uint64)
+    pp._check(pp.lib.zk_groth16_verify_all_bytes(pp.h, pvk.h, pb.ctypes.data if count else None, ib.ctypes.data if ib.size else None,
+                                                 n_inputs, count, sd, C.byref(ok), gt.ctypes.data if want_gt else None, stream))
     return (bool(ok.value), pp.fq.decode(gt.reshape(12, nl))) if want_gt else bool(ok.value)
 
 

@@ -282,6 +282,21 @@ def points_from_bytes(pp, group, data, stream=None):
     return out, count
 
 
+def points_from_bytes_checked(pp, group, data, stream=None):
+    """points_from_bytes with a verdict per element instead of an exception (zk_points_decompress_checked: arkworks'
+    deserialize_compressed with validation, subgroup test included).  Returns (device vector, count, ok): ok[i] = 0 where
+    element i does not decode ((0, 0) is written) or lies outside the order-r subgroup (the decoded point is kept)."""
+    g2 = group == api.ZK_G2
+    size = pp.fq.nbytes * (2 if g2 else 1)
+    host = np.frombuffer(bytes(data), dtype=np.uint8)
+    if host.size % size:
+        raise ValueError("byte length is not a multiple of the compressed point size")
+    count = host.size // size
+    raw = api.DeviceBuffer.from_numpy(pp, host)
+    out, ok = api.points_decompress_checked(pp, group, raw, count, stream=stream)
+    return out, count, ok
+
+
 def points_to_bytes(pp, group, pts_d, count, stream=None):
     g2 = group == api.ZK_G2
     size = pp.fq.nbytes * (2 if g2 else 1)
