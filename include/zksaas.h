@@ -353,6 +353,31 @@ int zk_groth16_setup_scalars(zk_ctx* ctx, const void* a_row_ptr_d, const void* a
                              const void* c_col_d, const void* c_val_d, size_t num_variables, size_t num_constraints,
                              size_t num_instance, int log_m, const void* trapdoor, size_t tail_zeros, void* a_query_d,
                              void* b_query_d, void* l_query_d, void* h_query_d, void* gamma_abc_d, void* stream);
+/* zk_pss_unpack_robust: the error-correcting unpack.  The n = 4l shares of a chunk are a Reed-Solomon word over the share
+ * domain H_n; for a polynomial of degree < `dimension` (2l for packed shares, 4l - 1 for their products) the word has
+ * redundancy that zk_pss_unpack / zk_pss_unpack2 do not use.  secret-sharing/src/gao.rs:47-84 decode_to_message per chunk, with the early return and the failure checks
+ * its todo lines ask for.  A verdict per chunk: the call returns ZK_OK whatever the shares are.
+ * With cap = (n - dimension) / 2:
+ *   status 0  clean: the interpolant of the n shares has degree < dimension; it is the message h
+ *   status 1  corrected: a polynomial h of degree < dimension (it is unique) differs from the shares in 1 .. cap positions;
+ *             bit p of errpos is set exactly for those parties
+ *   status 2  failed: no such polynomial; message and secrets are written as zeros, errpos as 0
+ * For status 0 and 1 the secrets are h(g w_2l^i), i < l: zk_pss_unpack's result on a clean word of degree < 2l,
+ * zk_pss_unpack2's on a clean product word.  More than cap wrong shares either fail or -- with probability about
+ * n^cap / r -- land within cap of another codeword, which is a legitimate status 1.
+ * Only all n parties: shares_d is [n][nchunks] in party order.  Erasures together with errors (a dropout and a bad share
+ * in one chunk) are NOT supported; a dropout alone is zk_pss_unpack2's party list.
+ * Errors: dimension outside 1 .. n - 1, or NULL shares_d / status_d with nchunks > 0 -> ZK_ERR_BAD_INPUT (the context stays
+ * usable); nchunks == 0 is ZK_OK.  No host synchronisation inside the call: everything is ordered on `stream`, working
+ * memory comes from the stream's workspace as in zk_groth16_setup_scalars.  Device engine only. */
+int zk_pss_unpack_robust(zk_ctx* ctx, const void* shares_d /* [n][nchunks] */, size_t nchunks, int dimension,
+                         void* secrets_d   /* [nchunks*l], order 0, or NULL */,
+                         void* message_d   /* [dimension][nchunks] coefficients of h, or NULL */,
+                         uint8_t* status_d /* [nchunks] */,
+                         uint32_t* errpos_d /* [nchunks], or NULL */,
+                         uint64_t* summary_d /* [3 + n]: clean, corrected, failed, then per party the number of
+                                                chunks in which its share was corrected; or NULL */,
+                         void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

@@ -65,6 +65,64 @@ pub fn unpack_missing_shares_vec<F: PrimeField + 'static>(ctx: &Context, shares:
     out.to_vec(nchunks * ctx.l)
 }
 
+/// Verdict of [`unpack_robust_vec`] for one chunk.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Verdict {
+    /// the interpolant of the `n` shares already has degree `< dimension`
+    Clean,
+    /// up to `(n - dimension) / 2` shares were wrong and have been corrected; `errpos` names the parties
+    Corrected,
+    /// no polynomial of degree `< dimension` lies that close: secrets and message read as zero
+    Failed,
+}
+
+/// What [`unpack_robust_vec`] returns: `decode_to_message`'s message and the secrets of every chunk, with a verdict
+/// in place of its panic.
+pub struct RobustUnpack<F> {
+    /// `[m]` in `pack_vec` order (zeros for a failed chunk)
+    pub secrets: Vec<F>,
+    /// coefficient `j` of chunk `c`'s message polynomial at `[j][c]`, `j < dimension`
+    pub message: Vec<Vec<F>>,
+    pub verdicts: Vec<Verdict>,
+    /// bit `p` set: party `p`'s share of the chunk was corrected
+    pub errpos: Vec<u32>,
+    /// chunks clean, corrected, failed
+    pub counts: [u64; 3],
+    /// per party, the number of chunks in which its share was corrected
+    pub corrected_per_party: Vec<u64>,
+}
+
+/// The role of `decode_to_message` (`secret-sharing/src/gao.rs:47-84`) for every chunk of a vector at once, with the
+/// early return for a codeword and the checks for a failed decoding its todo lines ask for: `shares` are all `n`
+/// parties' vectors, `dimension` is `2l` for packed shares and `4l - 1` for their products.  Bad shares never make
+/// the call fail; they show in the verdicts.  Erasures together with errors are not supported.
+pub fn unpack_robust_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], dimension: usize)
+                                                  -> Result<RobustUnpack<F>, MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, ctx.n)?;
+    let fsz = core::mem::size_of::<F>();
+    let sh = DeviceBuf::from_slice(ctx, &flat)?;
+    let sec = DeviceBuf::alloc(ctx, nchunks * ctx.l * fsz)?;
+    let msg = DeviceBuf::alloc(ctx, nchunks * dimension * fsz)?;
+    let st = DeviceBuf::alloc(ctx, nchunks)?;
+    let ep = DeviceBuf::alloc(ctx, nchunks * 4)?;
+    let sm = DeviceBuf::alloc(ctx, (3 + ctx.n) * 8)?;
+    check(ctx, unsafe {
+        sys::zk_pss_unpack_robust(ctx.raw(), sh.ptr(), nchunks, dimension as i32, sec.ptr(), msg.ptr(), st.ptr() as *mut u8,
+                                  ep.ptr() as *mut u32, sm.ptr() as *mut u64, ptr::null_mut())
+    })?;
+    let status: Vec<u8> = st.to_vec(nchunks)?;
+    let summary: Vec<u64> = if nchunks == 0 { vec![0; 3 + ctx.n] } else { sm.to_vec(3 + ctx.n)? };
+    let message: Vec<F> = msg.to_vec(nchunks * dimension)?;
+    Ok(RobustUnpack {
+        secrets: sec.to_vec(nchunks * ctx.l)?,
+        message: message.chunks(nchunks.max(1)).map(|c| c.to_vec()).collect(),
+        verdicts: status.iter().map(|s| match s { 0 => Verdict::Clean, 1 => Verdict::Corrected, _ => Verdict::Failed }).collect(),
+        errpos: ep.to_vec(nchunks)?,
+        counts: [summary[0], summary[1], summary[2]],
+        corrected_per_party: summary[3..].to_vec(),
+    })
+}
+
 fn flatten<F: PrimeField>(_ctx: &Context, shares: &[Vec<F>], want: usize) -> Result<(Vec<F>, usize), MpcNetError> {
     if shares.len() != want || shares.is_empty() {
         return Err(MpcNetError::BadInput { err: "unpack: one share vector per listed party expected" });

@@ -174,10 +174,49 @@ class PackedSharingParams(Context):
         self._check(self.lib.zk_pss_unpack2(self.h, _ptr(shares_d), arr, np_, nchunks, _ptr(out), stream))
         return out
 
+    def unpack_robust(self, shares_d, nchunks, dimension=None, want_message=False, stream=None):
+        """zk_pss_unpack_robust: the error-correcting unpack of all n parties' shares [n][nchunks] (gao.rs decode_to_message
+        per chunk, with a verdict instead of a panic).  dimension: 2l (packed shares, the default) up to 4l - 1 (their
+        products).  Returns a RobustUnpack; nothing is synchronised until its numbers are read."""
+        k = 2 * self.l if dimension is None else int(dimension)
+        r = RobustUnpack(self, nchunks, k)
+        r.secrets = self.alloc_fr(self.l * nchunks)
+        r.status = DeviceBuffer(self, nchunks)
+        r.errpos = DeviceBuffer(self, 4 * nchunks)
+        r.summary_d = DeviceBuffer(self, 8 * (3 + self.n))
+        r.message = self.alloc_fr(k * nchunks) if want_message and k > 0 else None
+        self._check(self.lib.zk_pss_unpack_robust(self.h, _ptr(shares_d), nchunks, k, _ptr(r.secrets), _ptr(r.message),
+                                                  _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
+
     def lagrange_unpack(self, shares_d, nchunks, parties, out=None, stream=None):
         return self.unpack2(shares_d, nchunks, parties, out, stream)
 
     unpack_missing_shares = unpack2
+
+
+class RobustUnpack:
+    """Result of PackedSharingParams.unpack_robust.  Device buffers: secrets [nchunks * l] (order 0), status [nchunks] bytes
+    (0 clean, 1 corrected, 2 failed), errpos [nchunks] u32 (bit p: party p's share was corrected), summary_d [3 + n] u64,
+    message [dimension][nchunks] or None.  `summary` downloads summary_d: [clean, corrected, failed] + per party the number
+    of chunks in which its share was corrected."""
+    CLEAN, CORRECTED, FAILED = 0, 1, 2
+
+    def __init__(self, ctx, nchunks, dimension):
+        self.ctx, self.nchunks, self.dimension = ctx, nchunks, dimension
+        self.secrets = self.status = self.errpos = self.summary_d = self.message = None
+
+    @property
+    def summary(self):
+        if not self.nchunks:            # the call writes nothing for an empty vector
+            return [0] * (3 + self.ctx.n)
+        return [int(v) for v in self.summary_d.to_numpy(np.uint64)]
+
+    def status_host(self):
+        return self.status.to_numpy(np.uint8) if self.nchunks else np.zeros(0, np.uint8)
+
+    def errpos_host(self):
+        return self.errpos.to_numpy(np.uint32) if self.nchunks else np.zeros(0, np.uint32)
 
 
 class FftMask:

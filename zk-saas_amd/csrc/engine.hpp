@@ -390,6 +390,9 @@ class IEngine {
   // mats: A, B, C as {row_ptr, col, val}; out: a_query, b_query, l_query, h_query, gamma_abc (any may be null)
   virtual int groth16_setup_scalars(const void* const mats[9], size_t nvars, size_t nc, size_t ni, int log_m,
                                     const void* trapdoor, size_t tail_zeros, void* const out[5], hipStream_t st) = 0;
+  // shares [n][nchunks] of all n parties -> a verdict per chunk (gao.hpp); any of secrets, message, errpos, summary may be null
+  virtual int pss_unpack_robust(const void* shares, size_t nchunks, int dimension, void* secrets, void* message,
+                                uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,

@@ -11,6 +11,7 @@
 #include "groth16.hpp"
 #include "qap.hpp"
 #include "setup.hpp"
+#include "gao.hpp"
 #include "msm.hpp"
 #include "hostpool.hpp"
 #include "points.hpp"
@@ -383,6 +384,7 @@ class Engine : public IEngine {
 #include "engine_groth16.inc.hpp"    // circom_h / libsnark_h, prover, batch prover
 #include "engine_dist.inc.hpp"       // zk_dist_*: per-rank collective forms
 #include "engine_setup.inc.hpp"      // zk_groth16_setup_scalars: R1CS and trapdoor -> CRS scalars
+#include "engine_gao.inc.hpp"        // zk_pss_unpack_robust: the error-correcting unpack
 
   int ensure_streams() {
     std::lock_guard<std::mutex> lk(mu_);

@@ -975,6 +975,9 @@ struct Fp {
       r[i] = (int32_t)((((hi << 32) | lo) >> sh) & 0x3fffffffu);
     }
   }
+  // PLAIN: the integer x^-1 mod p of the limbs, without the two products with R^2 -- for a caller that multiplies inline
+  // (gao.hpp: the out-of-line product passes its operands through scratch memory)
+  template <bool PLAIN = false>
   ZK_HD Fp inverse_safegcd() const {
     constexpr int32_t M30 = 0x3fffffff;
     int32_t f[K30], g[K30], d[K30], e[K30], m[K30];
@@ -1086,7 +1089,8 @@ struct Fp {
       if (i + 2 < K30) acc |= (uint64_t)(uint32_t)d[i + 2] << (60 - sh);
       y.v[w] = (uint32_t)acc;
     }
-    return mul_ni(mul_ni(y, r2()), r2());
+    if constexpr (PLAIN) return y;
+    else return mul_ni(mul_ni(y, r2()), r2());
   }
   // The inversion of code that inverts per lane or per point (affine normalisation, ec.hpp xyzz_to_affine): batched
   // divsteps -- about 35 (8 limbs) / 25 (12 limbs) product equivalents of issue against the Fermat ladder's 380 / 570.

@@ -1,0 +1,325 @@
+// Error-correcting unpack (zk_pss_unpack_robust): bounded-distance decoding of the Reed-Solomon word the n = 4l shares of one
+// chunk form, after secret-sharing/src/gao.rs:11-84 (partial_xgcd, decode_to_message) with the early return and the failure
+// checks its todo lines ask for.  For a received word y on the share domain H_n and a dimension k, cap = (n - k) / 2:
+//   status 0  the interpolant R = IFFT(y) has degree < k                                  -> h = R
+//   status 1  a polynomial h of degree < k agrees with y in all but 1 .. cap positions    -> h, the positions in errpos
+//   status 2  neither                                                                     -> zeros
+// Two parts, both host + device code (tests/native/gao_host_test.cpp runs the text the kernels compile):
+//   gao_load / gao_ifft / gao_is_clean / gao_clean_secrets   one lane (two at l = 8), one chunk: the syndrome test and the
+//                                                 clean unpack (stage 1)
+//   gao_chunk                                     n lanes, one chunk: Gao's decoder (stage 2), written against a lane group
+// The lane group G gives the decoder its cross-lane operations -- broadcast from a lane, shift by d lanes, ballot, any -- with
+// a value of type G::V<T> holding one T per lane: GaoDevGroup (gao_impl.hpp) maps them to the wave's cross-lane builtins and
+// V<T> = T, GaoHostGroup below is a loop over an array of n lanes.  Lane p holds coefficient p of a polynomial.
+#pragma once
+#include <type_traits>
+
+#include "field.hpp"
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+
+namespace zk {
+
+constexpr int GAO_MAX_N = 32;
+
+// Constants of one packing factor.  A kernel takes them by value and reads them at compile-time indices only.
+template <class F>
+struct GaoConsts {
+  F ninv;                  // 1 / n
+  F tw[GAO_MAX_N / 2];     // w_n^-j, j < n / 2: the twiddles of the inverse transform over H_n
+  F wpow2[5], wipow2[5];   // w_n^(2^b), w_n^-(2^b)
+  F spow2[3];              // w_2l^(2^b)
+  F g;                     // the coset generator
+  F sec[8];                // g w_2l^i, i < l: where the secrets sit (pss.rs:44-52)
+};
+
+template <class P>
+inline GaoConsts<Fp<P>> gao_make_consts(int l) {
+  using F = Fp<P>;
+  const int n = 4 * l;
+  auto root = [](int size) {
+    F r = F::from_limbs(P::TWO_ADIC_ROOT);
+    for (int i = 0; ((size_t)size << i) < ((size_t)1 << P::TWO_ADICITY); i++) r = r.sqr();
+    return r;
+  };
+  GaoConsts<F> c;
+  const F z = F::zero();
+  c.ninv = F::from_u64((uint64_t)n).inverse();
+  const F w = root(n), wi = w.inverse(), w2l = l == 1 ? (z - F::one()) : root(2 * l);
+  F cur = F::one();
+  for (int j = 0; j < GAO_MAX_N / 2; j++) c.tw[j] = j < n / 2 ? cur : z, cur = cur * wi;
+  F a = w, b = wi, s = w2l;
+  for (int i = 0; i < 5; i++) c.wpow2[i] = a, c.wipow2[i] = b, a = a.sqr(), b = b.sqr();
+  for (int i = 0; i < 3; i++) c.spow2[i] = s, s = s.sqr();
+  c.g = F::from_limbs(P::GENERATOR);
+  cur = c.g;
+  for (int i = 0; i < 8; i++) c.sec[i] = i < l ? cur : z, cur = cur * w2l;
+  return c;
+}
+
+// base^e for e < 2^NB from the squarings pow2[b] = base^(2^b)
+template <class F, int NB>
+ZK_HD F gao_lane_pow(const F* pow2, int e) {
+  F r = F::one();
+#pragma unroll
+  for (int b = 0; b < NB; b++)
+    if ((e >> b) & 1) r = r * pow2[b];
+  return r;
+}
+
+// ---------------------------------------------------------------- stage 1: one lane (or two), one chunk
+// A chunk is worked on by SP = 1 or 2 lanes.  With SP = 2 (l = 8: 32 coefficients of 8 limbs do not fit one lane's registers)
+// lane q takes the first decimation-in-frequency stage at the load -- y_i + y_{i+n/2}, or (y_i - y_{i+n/2}) w^-i -- and then
+// holds the M = n / 2 coefficients of index 2 j' + q.  In general a lane holds coefficient SP j' + q at x[gao_bitrev(j', M)].
+constexpr int gao_split(int l) { return l >= 8 ? 2 : 1; }
+constexpr int gao_bitrev(int i, int n) {
+  int r = 0;
+  for (int b = 1; b < n; b <<= 1) r = (r << 1) | ((i & b) ? 1 : 0);
+  return r;
+}
+constexpr int gao_log2(int n) { return n <= 1 ? 0 : 1 + gao_log2(n / 2); }
+// fn(integral_constant<int, I>) for I = B .. E - 1: the loops of the one-lane form, unrolled by the language and not by a
+// pragma -- with products inline the bodies are large, the unroller left the outer loops rolled and the array of loaded
+// elements, then indexed at run time, went to scratch memory
+template <int B, int E, class Fn>
+ZK_HD void gao_static_for(Fn&& fn) {
+  if constexpr (B < E) {
+    fn(std::integral_constant<int, B>{});
+    gao_static_for<B + 1, E>(fn);
+  }
+}
+// x[i], i < M, from the shares ld(p), p < SP M, for lane q of the split
+template <int M, int SP, class F, class Ld>
+ZK_HD void gao_load(const GaoConsts<F>& c, int q, Ld ld, F* x) {
+  gao_static_for<0, M>([&](auto i_) {
+    constexpr int i = decltype(i_)::value;
+    if constexpr (SP == 1) {
+      x[i] = ld(i);
+    } else {
+      const F u = ld(i), v = ld(i + M);
+      if constexpr (i == 0) x[i] = q ? u - v : u + v;
+      else x[i] = q ? (u - v) * c.tw[i] : u + v;
+    }
+  });
+}
+// In place: x[gao_bitrev(j', M)] = n R_{SP j' + q}, R = IFFT_{H_n}(y).  Radix 2, decimation in frequency, every index a
+// compile-time constant: (M / 2) (log2 M - 1) - (M / 2 - 1) products -- 1, 5, 17 for M = 4, 8, 16.
+template <int M, int SP, class F>
+ZK_HD void gao_ifft(const GaoConsts<F>& c, F* x) {
+  gao_static_for<0, gao_log2(M)>([&](auto s_) {
+    gao_static_for<0, M / 2>([&](auto t_) {
+      constexpr int s = decltype(s_)::value, t = decltype(t_)::value;
+      constexpr int len = M >> s, h = len / 2, i = t % h, lo = (t / h) * len + i;
+      const F u = x[lo], v = x[lo + h];
+      x[lo] = u + v;
+      if constexpr (i == 0) x[lo + h] = u - v;
+      else x[lo + h] = (u - v) * c.tw[(i << s) * SP];
+    });
+  });
+}
+// this lane's coefficients of index >= k all zero
+template <int M, int SP, class F>
+ZK_HD bool gao_is_clean(const F* x, int k, int q) {
+  bool clean = true;
+  gao_static_for<0, M>([&](auto j_) {
+    constexpr int j = decltype(j_)::value;
+    if (SP * j + q >= k && !x[gao_bitrev(j, M)].is_zero()) clean = false;
+  });
+  return clean;
+}
+// put(j, R_j) for this lane's j < k: the message of a clean word
+template <int M, int SP, class F, class Put>
+ZK_HD void gao_clean_message(const GaoConsts<F>& c, const F* x, int k, int q, Put put) {
+  gao_static_for<0, M>([&](auto j_) {
+    constexpr int j = decltype(j_)::value;
+    if (SP * j + q < k) put(SP * j + q, x[gao_bitrev(j, M)] * c.ninv);
+  });
+}
+// put(i, this lane's part of R(g w_2l^i)), i < l, for R of degree < k: Horner over the coefficients the transform left (in
+// X^SP, lane 1 of a split then multiplies by X), then the 1 / n; the parts of the SP lanes add up to the secret.
+// Every multiply is inline (an out-of-line one passes its operands through scratch memory, and the values that live across a
+// call no longer fit the registers a callee preserves).  For l >= 4 the secrets are a loop that is not unrolled, so the
+// products of one evaluation are in the code once: the coefficient indices stay compile-time constants, the loop index only
+// moves the point on by one product and selects where put() stores.
+template <int M, int SP, class F, class Put>
+ZK_HD void gao_clean_secrets(const GaoConsts<F>& c, const F* x, int k, int q, Put put) {
+  constexpr int L = M * SP / 4;
+  if constexpr (L <= 2) {
+    static_assert(SP == 1, "no split at small l");
+    F sec[L];
+    gao_static_for<0, L>([&](auto i_) { sec[decltype(i_)::value] = F::zero(); });
+    gao_static_for<0, M>([&](auto r_) {
+      constexpr int j = M - 1 - decltype(r_)::value;
+      if (j < k) gao_static_for<0, L>([&](auto i_) {
+        constexpr int i = decltype(i_)::value;
+        sec[i] = sec[i] * c.sec[i] + x[gao_bitrev(j, M)];
+      });
+    });
+    gao_static_for<0, L>([&](auto i_) { put(decltype(i_)::value, sec[decltype(i_)::value] * c.ninv); });
+  } else {
+    F pt1 = c.g;              // g w_2l^i, walked: a run-time index into the constants would copy them to scratch memory
+#pragma unroll 1
+    for (int i = 0; i < L; i++) {
+      if (i) pt1 = pt1 * c.spow2[0];
+      const F pt = SP == 1 ? pt1 : pt1.sqr();
+      F acc = F::zero();
+      gao_static_for<0, M>([&](auto r_) {
+        constexpr int j = M - 1 - decltype(r_)::value;
+        if (SP * j + q < k) acc = acc * pt + x[gao_bitrev(j, M)];
+      });
+      if (SP == 2 && q) acc = acc * pt1;
+      put(i, acc * c.ninv);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- the host lane group
+struct GaoHostGroup {
+  template <class T>
+  struct V {
+    T a[GAO_MAX_N];
+  };
+  int n;
+  template <class T>
+  const T& at(const V<T>& v, int p) const { return v.a[p]; }
+  template <class T, class Fn>
+  V<T> make(Fn fn) const {
+    V<T> o{};
+    for (int p = 0; p < n; p++) o.a[p] = fn(p);
+    return o;
+  }
+  template <class T>
+  T bcast(const V<T>& v, int src) const { return v.a[src]; }
+  template <class T>
+  V<T> shift(const V<T>& v, int d) const {
+    V<T> o{};
+    for (int p = 0; p < n; p++) o.a[p] = p >= d ? v.a[p - d] : T::zero();
+    return o;
+  }
+  template <class Fn>
+  uint32_t ballot(Fn pred) const {
+    uint32_t m = 0;
+    for (int p = 0; p < n; p++)
+      if (pred(p)) m |= 1u << p;
+    return m;
+  }
+  bool wave_any(bool b) const { return b; }
+};
+
+// ---------------------------------------------------------------- stage 2: n lanes, one chunk
+// index of the highest set bit, -1 for 0: the degree of a polynomial from the ballot of its nonzero coefficients
+ZK_HD int gao_top_bit(uint32_t m) { return m ? 31 - __builtin_clz(m) : -1; }
+ZK_HD int gao_popcount(uint32_t m) { return __builtin_popcount(m); }
+
+template <class F, class G>
+struct GaoResult {
+  int status;                          // 1 or 2 (a clean word never reaches the decoder)
+  uint32_t errpos;
+  typename G::template V<F> h;         // lane j: coefficient j of the message, zero for j >= k and on failure
+  typename G::template V<F> sec;       // lane i < l: secret i
+};
+
+// One chunk, all n lanes of the group together.  y: lane p holds share p; xp, xinv: w_n^p and w_n^-p; sp: g w_2l^p (read in
+// lanes p < l).  A group that is not `live` takes every cross-lane step with the others and changes nothing.
+//
+// partial_xgcd runs as elementary row operations on [A; SA] (the row being reduced) and [B; SB] (the divisor):
+//   [A; SA] <- lc(B) [A; SA] - lc(A) X^d [B; SB],  d = deg A - deg B,
+// and a swap once deg A < deg B: one reference loop iteration is the run of steps between two swaps.  A row is the reference's
+// row times a nonzero scalar, which h = r / s does not see, so the only inversion is the one of the final exact division.
+// z = X^n - 1 has n + 1 coefficients: the first step is taken in closed form, lc(R) z - X^(n - deg R) R, whose X^n terms cancel.
+// Every loop has a static bound and runs while any group of the wave is active, so no cross-lane read sits in divergent code
+// and no share vector makes the decoder spin.
+template <class F, class G>
+ZK_HD GaoResult<F, G> gao_chunk(const G& g, const GaoConsts<F>& c, int n, int k, bool live,
+                                const typename G::template V<F>& y, const typename G::template V<F>& xp,
+                                const typename G::template V<F>& xinv, const typename G::template V<F>& sp) {
+  using VF = typename G::template V<F>;
+  const int stop = (n + k) / 2, cap = (n - k) / 2;
+  auto deg = [&](const VF& v) { return gao_top_bit(g.ballot([&](int p) { return !g.at(v, p).is_zero(); })); };
+  const F zero = F::zero(), one = F::one();
+  // ---- R = IFFT(y): lane p evaluates (1 / n) sum_q y_q (w^-p)^q by Horner
+  VF B = g.template make<F>([&](int) { return zero; });
+  for (int q = n - 1; q >= 0; q--) {
+    const F yq = g.bcast(y, q);
+    B = g.template make<F>([&](int p) { return g.at(B, p) * g.at(xinv, p) + yq; });
+  }
+  B = g.template make<F>([&](int p) { return g.at(B, p) * c.ninv; });
+  VF SB = g.template make<F>([&](int p) { return p == 0 ? one : zero; });
+  // ---- partial_xgcd(z, R): stop at the first remainder of degree < (n + k) / 2
+  int degB = deg(B);
+  bool active = live && degB >= stop;
+  VF A, SA;
+  {
+    const int d = active ? n - degB : 0;
+    const F lc = g.bcast(B, degB < 0 ? 0 : degB);
+    const VF sh = g.shift(B, d);
+    A = g.template make<F>([&](int p) { return p == 0 ? zero - g.at(sh, p) - lc : zero - g.at(sh, p); });
+    SA = g.template make<F>([&](int p) { return p == d ? zero - one : zero; });
+  }
+  for (int it = 0; it < 2 * n + 2; it++) {
+    if (!g.wave_any(active)) break;
+    int degA = deg(A);
+    degB = deg(B);
+    const bool sw = active && degA < degB;
+    {
+      const VF tA = A, tS = SA;
+      A = g.template make<F>([&](int p) { return sw ? g.at(B, p) : g.at(tA, p); });
+      B = g.template make<F>([&](int p) { return sw ? g.at(tA, p) : g.at(B, p); });
+      SA = g.template make<F>([&](int p) { return sw ? g.at(SB, p) : g.at(tS, p); });
+      SB = g.template make<F>([&](int p) { return sw ? g.at(tS, p) : g.at(SB, p); });
+    }
+    if (sw) {
+      const int t = degA;
+      degA = degB, degB = t;
+    }
+    if (active && degB < stop) active = false;
+    const int d = active ? degA - degB : 0;
+    const F a = g.bcast(B, degB < 0 ? 0 : degB), b = g.bcast(A, degA < 0 ? 0 : degA);
+    const VF shB = g.shift(B, d), shS = g.shift(SB, d);
+    const bool on = active;
+    A = g.template make<F>([&](int p) { return on ? a * g.at(A, p) - b * g.at(shB, p) : g.at(A, p); });
+    SA = g.template make<F>([&](int p) { return on ? a * g.at(SA, p) - b * g.at(shS, p) : g.at(SA, p); });
+  }
+  // a group still active here has met the static bound, which no input reaches: it fails
+  bool ok = live && !active;
+  // ---- h = r / s, exactly, with deg h < k (decode_to_message's divide_with_q_and_r and its assert)
+  const int dr = deg(B), ds = deg(SB), qd = dr - ds;
+  if (qd >= k || ds < 0) ok = false;
+  const F inv = g.bcast(SB, ds < 0 ? 0 : ds).template inverse_safegcd<true>() * F::r2() * F::r2();
+  VF rem = B, h = g.template make<F>([&](int) { return zero; });
+  for (int j = k - 1; j >= 0; j--) {
+    const bool on = ok && j <= qd;
+    const F q = g.bcast(rem, on ? ds + j : 0) * inv;
+    const VF sh = g.shift(SB, j);
+    rem = g.template make<F>([&](int p) { return on ? g.at(rem, p) - q * g.at(sh, p) : g.at(rem, p); });
+    h = g.template make<F>([&](int p) { return on && p == j ? q : g.at(h, p); });
+  }
+  if (g.ballot([&](int p) { return !g.at(rem, p).is_zero(); })) ok = false;
+  // ---- re-encode: lane p compares h(w^p) with its own share; lanes i < l evaluate the secrets
+  VF ev = g.template make<F>([&](int) { return zero; }), sv = ev;
+  for (int j = k - 1; j >= 0; j--) {
+    const F hj = g.bcast(h, j);
+    ev = g.template make<F>([&](int p) { return g.at(ev, p) * g.at(xp, p) + hj; });
+    sv = g.template make<F>([&](int p) { return g.at(sv, p) * g.at(sp, p) + hj; });
+  }
+  const uint32_t diff = g.ballot([&](int p) { return g.at(ev, p) != g.at(y, p); });
+  if (gao_popcount(diff) > cap) ok = false;
+  GaoResult<F, G> out;
+  out.status = ok ? 1 : 2;
+  out.errpos = ok ? diff : 0;
+  out.h = g.template make<F>([&](int p) { return ok ? g.at(h, p) : zero; });
+  out.sec = g.template make<F>([&](int p) { return ok ? g.at(sv, p) : zero; });
+  return out;
+}
+
+#if defined(__HIPCC__)
+class IEngine;
+struct DevBuf;
+// zk_pss_unpack_robust over the scalar field FrP (engine_gao.inc.hpp has the argument list); wk: working memory
+template <class FrP>
+int gao_unpack_robust_run(IEngine* e, DevBuf& wk, int l, const void* shares, size_t nchunks, int dimension, void* secrets,
+                          void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
+#endif
+
+}  // namespace zk

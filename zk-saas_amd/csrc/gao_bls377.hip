@@ -1,0 +1,8 @@
+// zk_pss_unpack_robust over the scalar field of this curve (gao_impl.hpp).
+#include "curves.hpp"
+#include "gao_impl.hpp"
+
+namespace zk {
+template int gao_unpack_robust_run<Bls377Fr>(IEngine*, DevBuf&, int, const void*, size_t, int, void*, void*, uint8_t*, uint32_t*,
+                                       uint64_t*, hipStream_t);
+}  // namespace zk
