@@ -138,6 +138,69 @@ def test_d_pp_c_matches_python_oracle(name, threads):
         cp.d_pp(ns, transpose(od.pack_vec(den, o, 28)), None, 29, threads)
 
 
+def _raw_residues(count, seed):
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 1 << 63, size=(count, 4), dtype=np.uint64)
+    a[:, 3] &= np.uint64((1 << 60) - 1)                  # below r on all three curves: Montgomery residues
+    return a
+
+
+def _deg_red_c(cp, x, ln, im, om, seed, threads):
+    out = x.copy()
+    lib().zkref_set_fast_king(1 if threads > 1 else 0, threads)
+    try:
+        cp.deg_red_arrays(out, ln, im, om, seed)
+    finally:
+        lib().zkref_set_fast_king(0, 1)
+    return out
+
+
+@pytest.mark.parametrize("l", [1, 4, 8])
+@pytest.mark.parametrize("name", ["bn254", "bls12_377", "bls12_381"])
+def test_d_pp_and_deg_red_c_match_python_oracle_at_every_packing_factor(name, l):
+    """What tests/test_gpu_degred_dpp.py takes as its reference at l = 1, 4, 8 (l = 2: the tests above).  zkref_d_pp and
+    zkref_deg_red == oracle/dist.py with sampled masks, with one mask only and with none, at 11 chunks; the threaded king
+    (matrices, spans over threads -- king_parallel splits from 1024 chunks up) == the serial FFT-form king at 1100 chunks
+    on the same raw residues."""
+    cp = CPss(name, l)
+    o = cp.opp
+    nch = 11
+    num, den = rand_vec(20, nch * l, o.p), rand_vec(21, nch * l, o.p)
+    ns, ds = transpose(od.pack_vec(num, o, 22)), transpose(od.pack_vec(den, o, 23))
+    masks = od.DegRedMask.sample(o, 1, nch, 24)
+    zero = [0] * nch
+    in_only = [od.DegRedMask(k.in_mask, zero) for k in masks]
+    out_only = [od.DegRedMask(zero, k.out_mask) for k in masks]
+    mul = [[x * x % o.p for x in v] for v in ns]
+    for mk in (masks, in_only, out_only):
+        assert cp.d_pp(ns, ds, mk, 25, 3) == od.d_pp(ns, ds, mk, o, seed=25)
+        assert cp.deg_red(mul, mk, 11) == od.deg_red(mul, mk, o, seed=11)
+    none = [od.DegRedMask.zero(nch)] * o.n
+    assert cp.d_pp(ns, ds, None, 25) == od.d_pp(ns, ds, none, o, seed=25)
+    assert cp.deg_red(mul, None, 11) == od.deg_red(mul, none, o, seed=11)
+    # None for one side is the zero mask of that side (what the GPU tests pass for an absent pointer)
+    a = cp.fr.enc([v for s in mul for v in s])
+    im = cp.fr.enc([v for k in masks for v in k.in_mask])
+    assert cp.fr.dec(_deg_red_c(cp, a, nch, im, None, 11, 1)) == [v for s in od.deg_red(mul, in_only, o, seed=11) for v in s]
+    ln = 1100
+    x, im, om = (_raw_residues(cp.n * ln, 30 + k) for k in range(3))
+    serial = _deg_red_c(cp, x, ln, im, om, 31, 1)
+    for threads in (3, 16):
+        assert np.array_equal(_deg_red_c(cp, x, ln, im, om, 31, threads), serial)
+    y = _raw_residues(cp.n * ln, 33)
+    serial = cp.d_pp_arrays(x, y, ln, im, om, 34, threads=1)
+    for threads in (3, 16):
+        assert np.array_equal(cp.d_pp_arrays(x, y, ln, im, om, 34, threads=threads), serial)
+
+
+def test_threaded_deg_red_equals_the_serial_one_at_65537_chunks():
+    """bn254, l = 2, the first size past the 2^16 boundary of the GPU's king kernels, sixteen threads"""
+    cp = CPss("bn254", 2)
+    ln = (1 << 16) + 1
+    x, im, om = (_raw_residues(cp.n * ln, 40 + k) for k in range(3))
+    assert np.array_equal(_deg_red_c(cp, x, ln, im, om, 41, 16), _deg_red_c(cp, x, ln, im, om, 41, 1))
+
+
 @pytest.mark.parametrize("count,threads", [(1, 1), (31, 1), (200, 1), (200, 4)])
 def test_msm_g1(count, threads):
     cp = CPss("bn254", 2)
