@@ -365,8 +365,8 @@ int zk_groth16_setup_scalars(zk_ctx* ctx, const void* a_row_ptr_d, const void* a
  * For status 0 and 1 the secrets are h(g w_2l^i), i < l: zk_pss_unpack's result on a clean word of degree < 2l,
  * zk_pss_unpack2's on a clean product word.  More than cap wrong shares either fail or -- with probability about
  * n^cap / r -- land within cap of another codeword, which is a legitimate status 1.
- * Only all n parties: shares_d is [n][nchunks] in party order.  Erasures together with errors (a dropout and a bad share
- * in one chunk) are NOT supported; a dropout alone is zk_pss_unpack2's party list.
+ * Only all n parties: shares_d is [n][nchunks] in party order.  With parties absent -- a dropout, or a party left out
+ * because it is known to lie -- the call is zk_pss_unpack_robust_parties below.
  * Errors: dimension outside 1 .. n - 1, or NULL shares_d / status_d with nchunks > 0 -> ZK_ERR_BAD_INPUT (the context stays
  * usable); nchunks == 0 is ZK_OK.  No host synchronisation inside the call: everything is ordered on `stream`, working
  * memory comes from the stream's workspace as in zk_groth16_setup_scalars.  Device engine only. */
@@ -378,6 +378,27 @@ int zk_pss_unpack_robust(zk_ctx* ctx, const void* shares_d /* [n][nchunks] */, s
                          uint64_t* summary_d /* [3 + n]: clean, corrected, failed, then per party the number of
                                                 chunks in which its share was corrected; or NULL */,
                          void* stream);
+/* zk_pss_unpack_robust_parties: the error-correcting unpack of the shares of a party list S: dropouts (erasures) and wrong
+ * shares (errors) in one chunk.  secret-sharing/src/gao.rs:11-84 over the points of S, with the party list of
+ * unpack_missing_shares / lagrange_unpack, secret-sharing/src/pss.rs:141-221.  shares_d is [nparties][nchunks], row i the
+ * shares of party parties[i]; parties (HOST) holds ascending ids below n, NULL stands for 0 .. nparties - 1.
+ * With k = dimension and cap = (nparties - k) / 2, rounded down:
+ *   status 0  the interpolant through the shares on { w_n^p : p in S } has degree < k; it is the message h
+ *   status 1  a polynomial h of degree < k (it is unique) differs from the listed shares in 1 .. cap places; bit p of
+ *             errpos is set exactly for those parties -- p is the party's id, not its place in the list -- and never
+ *             for an absent party
+ *   status 2  neither; message and secrets are written as zeros, errpos as 0
+ * secrets_d, message_d [dimension][nchunks], status_d, errpos_d and summary_d [3 + n] (per party id) are
+ * zk_pss_unpack_robust's, and with nparties == n every output equals that call's.  A party named in errpos once can be
+ * left out of the list afterwards: its chunks are clean again, at the cost of the clean path.
+ * Errors: a list that is not strictly ascending or holds an id >= n, nparties outside 1 .. n, dimension outside
+ * 1 .. n - 1, or NULL shares_d / status_d with nchunks > 0 -> ZK_ERR_BAD_INPUT; nparties <= dimension ->
+ * ZK_ERR_PROTOCOL (too few shares, as zk_pss_unpack2, pss.rs:183-186); the context stays usable.  nchunks == 0 is ZK_OK.
+ * No host synchronisation, working memory from the stream's workspace.  Device engine only. */
+int zk_pss_unpack_robust_parties(zk_ctx* ctx, const void* shares_d /* [nparties][nchunks] */,
+                                 const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */, int nparties,
+                                 size_t nchunks, int dimension, void* secrets_d, void* message_d, uint8_t* status_d,
+                                 uint32_t* errpos_d, uint64_t* summary_d, void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

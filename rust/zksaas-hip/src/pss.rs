@@ -65,12 +65,12 @@ pub fn unpack_missing_shares_vec<F: PrimeField + 'static>(ctx: &Context, shares:
     out.to_vec(nchunks * ctx.l)
 }
 
-/// Verdict of [`unpack_robust_vec`] for one chunk.
+/// Verdict of [`unpack_robust_vec`] / [`unpack_robust_parties_vec`] for one chunk.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum Verdict {
-    /// the interpolant of the `n` shares already has degree `< dimension`
+    /// the interpolant of the (listed) shares already has degree `< dimension`
     Clean,
-    /// up to `(n - dimension) / 2` shares were wrong and have been corrected; `errpos` names the parties
+    /// up to `(n - dimension) / 2` shares (`n`: the number of listed parties) were wrong and have been corrected; `errpos` names the parties
     Corrected,
     /// no polynomial of degree `< dimension` lies that close: secrets and message read as zero
     Failed,
@@ -95,10 +95,25 @@ pub struct RobustUnpack<F> {
 /// The role of `decode_to_message` (`secret-sharing/src/gao.rs:47-84`) for every chunk of a vector at once, with the
 /// early return for a codeword and the checks for a failed decoding its todo lines ask for: `shares` are all `n`
 /// parties' vectors, `dimension` is `2l` for packed shares and `4l - 1` for their products.  Bad shares never make
-/// the call fail; they show in the verdicts.  Erasures together with errors are not supported.
+/// the call fail; they show in the verdicts.  With parties absent the call is [`unpack_robust_parties_vec`].
 pub fn unpack_robust_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], dimension: usize)
                                                   -> Result<RobustUnpack<F>, MpcNetError> {
-    let (flat, nchunks) = flatten(ctx, shares, ctx.n)?;
+    robust_impl(ctx, shares, None, dimension)
+}
+
+/// [`unpack_robust_vec`] for the share vectors of the listed parties only (ascending ids, the list of
+/// `unpack_missing_shares`, `secret-sharing/src/pss.rs:141-221`): dropouts and wrong shares in one chunk.  Up to
+/// `(parties.len() - dimension) / 2` wrong shares among the listed are corrected per chunk; `errpos` and
+/// `corrected_per_party` stay indexed by party id and never name an absent party.  A party named once can be left out
+/// of the list afterwards.  `parties.len() <= dimension` is `MpcNetError::Protocol`, as for `unpack_missing_shares`.
+pub fn unpack_robust_parties_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], parties: &[u32],
+                                                          dimension: usize) -> Result<RobustUnpack<F>, MpcNetError> {
+    robust_impl(ctx, shares, Some(parties), dimension)
+}
+
+fn robust_impl<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], parties: Option<&[u32]>, dimension: usize)
+                                        -> Result<RobustUnpack<F>, MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, parties.map_or(ctx.n, |p| p.len()))?;
     let fsz = core::mem::size_of::<F>();
     let sh = DeviceBuf::from_slice(ctx, &flat)?;
     let sec = DeviceBuf::alloc(ctx, nchunks * ctx.l * fsz)?;
@@ -107,8 +122,13 @@ pub fn unpack_robust_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F
     let ep = DeviceBuf::alloc(ctx, nchunks * 4)?;
     let sm = DeviceBuf::alloc(ctx, (3 + ctx.n) * 8)?;
     check(ctx, unsafe {
-        sys::zk_pss_unpack_robust(ctx.raw(), sh.ptr(), nchunks, dimension as i32, sec.ptr(), msg.ptr(), st.ptr() as *mut u8,
-                                  ep.ptr() as *mut u32, sm.ptr() as *mut u64, ptr::null_mut())
+        match parties {
+            None => sys::zk_pss_unpack_robust(ctx.raw(), sh.ptr(), nchunks, dimension as i32, sec.ptr(), msg.ptr(),
+                                              st.ptr() as *mut u8, ep.ptr() as *mut u32, sm.ptr() as *mut u64, ptr::null_mut()),
+            Some(p) => sys::zk_pss_unpack_robust_parties(ctx.raw(), sh.ptr(), p.as_ptr(), p.len() as i32, nchunks,
+                                                         dimension as i32, sec.ptr(), msg.ptr(), st.ptr() as *mut u8,
+                                                         ep.ptr() as *mut u32, sm.ptr() as *mut u64, ptr::null_mut()),
+        }
     })?;
     let status: Vec<u8> = st.to_vec(nchunks)?;
     let summary: Vec<u64> = if nchunks == 0 { vec![0; 3 + ctx.n] } else { sm.to_vec(3 + ctx.n)? };

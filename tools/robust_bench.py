@@ -8,12 +8,20 @@ Legs, each over shares of `pack` of random secrets, dimension 2l:
   clean        no share touched                      (stage 1 alone does the work; stage 2 finds an empty list and leaves)
   dirty_1pct   every 100th chunk has one wrong share (party 0)
   dirty_all    every chunk has one wrong share, the same party (3): what one bad rank does to a vector
+Legs with a party list (zk_pss_unpack_robust_parties), at the same sizes:
+  absent1_clean        the last party absent, the rest clean: against zk_pss_unpack2 with the same list (the dropout path)
+  absent1_dirty_1pct   the last party absent, every 100th chunk with one wrong share (party 0) among the listed
+  liar_listed_absent   the dirty_all vector with the lying party (3) listed absent: against zk_pss_unpack_robust on the
+                       dirty_all vector itself, in turns (`ratio` = parties / dirty_all)
 A figure is the median over R windows of B back-to-back calls with one stream synchronise behind them (host clock / B); the
 two entry points take turns window by window.  `ratio` = robust / unpack.  `products_per_chunk` are the Fr products the code
 executes per chunk, counted from the source: l n for unpack; for the clean path the inverse transform, the k l Horner steps
 and the scalings (all SP lanes of a chunk); for a dirty chunk additionally n lanes times the products one lane of the decoder
-executes with one error (interpolation n, 2 Euclid steps of 4, the inversion's 2, k division steps of 2, 2 k re-encoding)."""
+executes with one error (interpolation n, 2 Euclid steps of 4, the inversion's 2, k division steps of 2, 2 k re-encoding).
+With rho parties absent the clean path multiplies the n - rho listed shares at the load (every lane of a split loads them all)
+and takes its Horner steps over k + rho coefficients; a dirty chunk's decoder runs at dimension k + rho and scales l secrets."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -62,6 +70,14 @@ def products(l, k):
     return {"unpack": l * n, "robust_clean": clean, "decoder_per_dirty_chunk": n * lane}
 
 
+def products_absent(l, k, rho):
+    n, sp = 4 * l, 2 if l >= 8 else 1
+    base, wide = products(l, k), products(l, k + rho)
+    return {"unpack2": l * (n - rho), "robust_clean": wide["robust_clean"] + sp * (n - rho),
+            "decoder_per_dirty_chunk": wide["decoder_per_dirty_chunk"] + (n - rho) + l,
+            "robust_clean_all_parties": base["robust_clean"]}
+
+
 def run_shape(l, log_chunks, reps, batch):
     pp = zk.PackedSharingParams("bn254", l)
     nch, n, k = 1 << log_chunks, 4 * l, 2 * l
@@ -106,7 +122,52 @@ def run_shape(l, log_chunks, reps, batch):
         assert np.array_equal(out_r.to_numpy(), want), leg          # corrected: the original secrets
         res[leg] = {"unpack_us": round(tu * 1e6, 2), "robust_us": round(tr * 1e6, 2), "ratio": round(tr / tu, 3),
                     "robust_us_per_2p14_chunks": round(tr * 1e6 * (1 << 14) / nch, 2), "summary_head": s[:3]}
+    # ---- the legs with a party list
+    out_p = pp.alloc_fr(l * nch)
+
+    def ids(parties):
+        return (C.c_uint32 * len(parties))(*parties)
+
+    def parties_call(buf, lst):
+        arr = ids(lst)
+        return lambda: pp._check(lib.zk_pss_unpack_robust_parties(pp.h, buf.ptr, arr, len(lst), nch, k, out_p.ptr, None,
+                                                                  status.ptr, errpos.ptr, summary.ptr, None))
+
+    # the lying party of dirty_all listed absent: its rows without row 3
+    wo3 = [q for q in range(n) if q != 3]
+    sh_wo3 = zk.DeviceBuffer(pp, (n - 1) * row)
+    for i, q in enumerate(wo3):
+        arr = get_row(q)
+        pp._check(lib.zk_memcpy_h2d(pp.h, sh_wo3.ptr + i * row, arr.ctypes.data, arr.nbytes, None))
+    t_all, t_abs = windows(pp, [robust, parties_call(sh_wo3, wo3)], reps, batch)
+    s = [int(v) for v in summary.to_numpy(np.uint64)]
+    assert s == [nch, 0, 0] + [0] * n, ("liar_listed_absent", s[:3])
+    assert np.array_equal(out_p.to_numpy(), want), "liar_listed_absent"
+    res["products_per_chunk_absent1"] = products_absent(l, k, 1)
+    res["liar_listed_absent"] = {"robust_dirty_all_us": round(t_all * 1e6, 2), "robust_parties_us": round(t_abs * 1e6, 2),
+                                 "ratio": round(t_abs / t_all, 4),
+                                 "robust_parties_us_per_2p14_chunks": round(t_abs * 1e6 * (1 << 14) / nch, 2),
+                                 "summary_head": s[:3]}
+    del sh_wo3
     set_row(3, keep3)
+    # the last party absent: the first n - 1 rows of the same buffer
+    head = list(range(n - 1))
+    head_ids = ids(head)
+
+    def unpack2_head():
+        pp._check(lib.zk_pss_unpack2(pp.h, shares.ptr, head_ids, n - 1, nch, out_u.ptr, None))
+
+    for leg in ("absent1_clean", "absent1_dirty_1pct"):
+        if leg == "absent1_dirty_1pct":
+            set_row(0, r0)
+        t2, tp = windows(pp, [unpack2_head, parties_call(shares, head)], reps, batch)
+        s = [int(v) for v in summary.to_numpy(np.uint64)]
+        ndirty = 0 if leg == "absent1_clean" else len(keep0[::100])
+        assert s[:3] == [nch - ndirty, ndirty, 0] and s[3 + n - 1] == 0, (leg, s)
+        assert np.array_equal(out_p.to_numpy(), want), leg
+        res[leg] = {"unpack2_us": round(t2 * 1e6, 2), "robust_parties_us": round(tp * 1e6, 2), "ratio": round(tp / t2, 3),
+                    "robust_parties_us_per_2p14_chunks": round(tp * 1e6 * (1 << 14) / nch, 2), "summary_head": s[:3]}
+    set_row(0, keep0)
     pp.close()
     return res
 

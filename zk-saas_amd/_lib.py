@@ -31,7 +31,7 @@ SYMBOLS = [
     "zk_base_mul_few", "zk_groth16_deal_masks", "zk_groth16_deal_witness", "zk_groth16_verify_all",
     "zk_groth16_setup_scalars",
     "zk_points_subgroup_check", "zk_points_decompress_checked", "zk_groth16_verify_bytes", "zk_groth16_verify_all_bytes",
-    "zk_pss_unpack_robust",
+    "zk_pss_unpack_robust", "zk_pss_unpack_robust_parties",
 ]
 
 _lib = None
@@ -218,6 +218,7 @@ def load():
     lib.zk_groth16_setup_scalars.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, i32, vp, sz, vp, vp, vp, vp, vp,
                                              vp]
     lib.zk_pss_unpack_robust.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp, vp, vp]
+    lib.zk_pss_unpack_robust_parties.argtypes = [vp, vp, C.POINTER(C.c_uint32), i32, sz, i32, vp, vp, vp, vp, vp, vp]
     lib.zk_points_subgroup_check.argtypes = [vp, i32, vp, sz, vp, vp]
     lib.zk_points_decompress_checked.argtypes = [vp, i32, vp, sz, vp, vp, vp]
     lib.zk_groth16_verify_bytes.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]

@@ -174,19 +174,28 @@ class PackedSharingParams(Context):
         self._check(self.lib.zk_pss_unpack2(self.h, _ptr(shares_d), arr, np_, nchunks, _ptr(out), stream))
         return out
 
-    def unpack_robust(self, shares_d, nchunks, dimension=None, want_message=False, stream=None):
+    def unpack_robust(self, shares_d, nchunks, dimension=None, want_message=False, stream=None, parties=None):
         """zk_pss_unpack_robust: the error-correcting unpack of all n parties' shares [n][nchunks] (gao.rs decode_to_message
         per chunk, with a verdict instead of a panic).  dimension: 2l (packed shares, the default) up to 4l - 1 (their
-        products).  Returns a RobustUnpack; nothing is synchronised until its numbers are read."""
+        products).  With `parties` (ascending ids) shares_d is [len(parties)][nchunks], the other parties are absent and the
+        call is zk_pss_unpack_robust_parties: wrong shares among the listed are corrected up to (len(parties) - dimension) // 2
+        per chunk, errpos and summary stay indexed by party id.  Returns a RobustUnpack; nothing is synchronised until its
+        numbers are read."""
         k = 2 * self.l if dimension is None else int(dimension)
-        r = RobustUnpack(self, nchunks, k)
+        r = RobustUnpack(self, nchunks, k, None if parties is None else list(parties))
         r.secrets = self.alloc_fr(self.l * nchunks)
         r.status = DeviceBuffer(self, nchunks)
         r.errpos = DeviceBuffer(self, 4 * nchunks)
         r.summary_d = DeviceBuffer(self, 8 * (3 + self.n))
         r.message = self.alloc_fr(k * nchunks) if want_message and k > 0 else None
-        self._check(self.lib.zk_pss_unpack_robust(self.h, _ptr(shares_d), nchunks, k, _ptr(r.secrets), _ptr(r.message),
-                                                  _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        if parties is None:
+            self._check(self.lib.zk_pss_unpack_robust(self.h, _ptr(shares_d), nchunks, k, _ptr(r.secrets), _ptr(r.message),
+                                                      _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        else:
+            arr = (C.c_uint32 * len(r.parties))(*r.parties)
+            self._check(self.lib.zk_pss_unpack_robust_parties(self.h, _ptr(shares_d), arr, len(r.parties), nchunks, k,
+                                                              _ptr(r.secrets), _ptr(r.message), _ptr(r.status),
+                                                              _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
     def lagrange_unpack(self, shares_d, nchunks, parties, out=None, stream=None):
@@ -199,11 +208,11 @@ class RobustUnpack:
     """Result of PackedSharingParams.unpack_robust.  Device buffers: secrets [nchunks * l] (order 0), status [nchunks] bytes
     (0 clean, 1 corrected, 2 failed), errpos [nchunks] u32 (bit p: party p's share was corrected), summary_d [3 + n] u64,
     message [dimension][nchunks] or None.  `summary` downloads summary_d: [clean, corrected, failed] + per party the number
-    of chunks in which its share was corrected."""
+    of chunks in which its share was corrected.  `parties`: the party list the call was given, None for all n."""
     CLEAN, CORRECTED, FAILED = 0, 1, 2
 
-    def __init__(self, ctx, nchunks, dimension):
-        self.ctx, self.nchunks, self.dimension = ctx, nchunks, dimension
+    def __init__(self, ctx, nchunks, dimension, parties=None):
+        self.ctx, self.nchunks, self.dimension, self.parties = ctx, nchunks, dimension, parties
         self.secrets = self.status = self.errpos = self.summary_d = self.message = None
 
     @property

@@ -818,6 +818,13 @@ int zk_pss_unpack_robust(zk_ctx* ctx, const void* shares_d, size_t nchunks, int 
   CTX_OR_FAIL();
   return e->pss_unpack_robust(shares_d, nchunks, dimension, secrets_d, message_d, status_d, errpos_d, summary_d, S(stream));
 }
+int zk_pss_unpack_robust_parties(zk_ctx* ctx, const void* shares_d, const uint32_t* parties, int nparties, size_t nchunks,
+                                 int dimension, void* secrets_d, void* message_d, uint8_t* status_d, uint32_t* errpos_d,
+                                 uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_unpack_robust_parties(shares_d, parties, nparties, nchunks, dimension, secrets_d, message_d, status_d,
+                                      errpos_d, summary_d, S(stream));
+}
 int zk_circom_h(zk_ctx* ctx, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
                 const zk_groth16_masks* masks, uint64_t seed, void* h_d, void* stream) {
   CTX_OR_FAIL();

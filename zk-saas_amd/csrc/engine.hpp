@@ -393,6 +393,10 @@ class IEngine {
   // shares [n][nchunks] of all n parties -> a verdict per chunk (gao.hpp); any of secrets, message, errpos, summary may be null
   virtual int pss_unpack_robust(const void* shares, size_t nchunks, int dimension, void* secrets, void* message,
                                 uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  // the same for the shares [nparties][nchunks] of a party list: errors among the listed, the others absent
+  virtual int pss_unpack_robust_parties(const void* shares, const uint32_t* parties, int nparties, size_t nchunks,
+                                        int dimension, void* secrets, void* message, uint8_t* status, uint32_t* errpos,
+                                        uint64_t* summary, hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,

@@ -11,6 +11,8 @@
 // The lane group G gives the decoder its cross-lane operations -- broadcast from a lane, shift by d lanes, ballot, any -- with
 // a value of type G::V<T> holding one T per lane: GaoDevGroup (gao_impl.hpp) maps them to the wave's cross-lane builtins and
 // V<T> = T, GaoHostGroup below is a loop over an array of n lanes.  Lane p holds coefficient p of a polynomial.
+// zk_pss_unpack_robust_parties -- the shares of a party list, the others absent -- runs the same two parts on a word made
+// full-length again: the section "absent parties" below (tests/native/gao_erasure_host_test.cpp runs that text).
 #pragma once
 #include <type_traits>
 
@@ -142,8 +144,10 @@ ZK_HD void gao_clean_message(const GaoConsts<F>& c, const F* x, int k, int q, Pu
 // call no longer fit the registers a callee preserves).  For l >= 4 the secrets are a loop that is not unrolled, so the
 // products of one evaluation are in the code once: the coefficient indices stay compile-time constants, the loop index only
 // moves the point on by one product and selects where put() stores.
-template <int M, int SP, class F, class Put>
-ZK_HD void gao_clean_secrets(const GaoConsts<F>& c, const F* x, int k, int q, Put put) {
+// The last product of a secret is by scale(i): 1 / n here, 1 / (n Lambda(g w_2l^i)) with absent parties (below).  For l >= 4
+// i is a run-time index: scale() must not read by-value constants there.
+template <int M, int SP, class F, class Scale, class Put>
+ZK_HD void gao_clean_secrets(const GaoConsts<F>& c, const F* x, int k, int q, Scale scale, Put put) {
   constexpr int L = M * SP / 4;
   if constexpr (L <= 2) {
     static_assert(SP == 1, "no split at small l");
@@ -156,7 +160,7 @@ ZK_HD void gao_clean_secrets(const GaoConsts<F>& c, const F* x, int k, int q, Pu
         sec[i] = sec[i] * c.sec[i] + x[gao_bitrev(j, M)];
       });
     });
-    gao_static_for<0, L>([&](auto i_) { put(decltype(i_)::value, sec[decltype(i_)::value] * c.ninv); });
+    gao_static_for<0, L>([&](auto i_) { put(decltype(i_)::value, sec[decltype(i_)::value] * scale(decltype(i_)::value)); });
   } else {
     F pt1 = c.g;              // g w_2l^i, walked: a run-time index into the constants would copy them to scratch memory
 #pragma unroll 1
@@ -169,9 +173,13 @@ ZK_HD void gao_clean_secrets(const GaoConsts<F>& c, const F* x, int k, int q, Pu
         if (SP * j + q < k) acc = acc * pt + x[gao_bitrev(j, M)];
       });
       if (SP == 2 && q) acc = acc * pt1;
-      put(i, acc * c.ninv);
+      put(i, acc * scale(i));
     }
   }
+}
+template <int M, int SP, class F, class Put>
+ZK_HD void gao_clean_secrets(const GaoConsts<F>& c, const F* x, int k, int q, Put put) {
+  gao_clean_secrets<M, SP>(c, x, k, q, [&](int) -> const F& { return c.ninv; }, put);
 }
 
 // ---------------------------------------------------------------- the host lane group
@@ -313,6 +321,117 @@ ZK_HD GaoResult<F, G> gao_chunk(const G& g, const GaoConsts<F>& c, int n, int k,
   return out;
 }
 
+// ---------------------------------------------------------------- absent parties (zk_pss_unpack_robust_parties)
+// With the parties of a set S listed, rho = n - |S| absent and Lambda(X) = prod_{e not in S} (X - w_n^e), the full-length word
+//   y~_p = y_p Lambda(w_n^p) for p in S,  0 otherwise
+// has IFFT(y~) = R_S Lambda exactly (R_S: the interpolant through S), and a polynomial h of degree < k within e places of y
+// on S is h Lambda of degree < k + rho within the same e places of y~.  So both stages run as above at dimension k + rho,
+// whose cap (n - k - rho) / 2 is (|S| - k) / 2, on shares multiplied as they are loaded; what comes out is h' = h Lambda:
+//   secrets  h'(g w_2l^i) / Lambda(g w_2l^i)      the points lie outside H_n, no denominator is zero
+//   message  h' / Lambda, an exact division       one lane: root by root (gao_deflate); a lane group: by the monic Lambda
+//   status 1 naming an absent party becomes status 2: by the distance of the (k + rho)-code no h exists then
+// Everything here depends on the party list only and is computed on the host per call.
+template <class F>
+struct GaoAbsentLoad {     // stage 1 takes this by value and reads it at compile-time indices only
+  F lam[GAO_MAX_N];        // Lambda(w_n^p) for a listed party p, zero for an absent one
+  int row[GAO_MAX_N];      // party p's row of shares_d, -1 for an absent one
+};
+template <class F>
+struct GaoAbsent {         // a small device table: what is read at a run-time index
+  GaoAbsentLoad<F> ld;
+  F lamc[GAO_MAX_N];       // the coefficients of Lambda (monic, degree rho), zero beyond
+  F root[GAO_MAX_N];       // w_n^e for the absent parties e, rho of them
+  F sscale[8];             // 1 / (n Lambda(g w_2l^i))
+  F slam[8];               // 1 / Lambda(g w_2l^i)
+  int k, rho;              // the caller's dimension; the decoder runs at k + rho
+  uint32_t listed;         // bit p: party p is listed
+};
+
+// parties: np ascending ids below n = 4l, np > k
+template <class P>
+inline GaoAbsent<Fp<P>> gao_make_absent(const GaoConsts<Fp<P>>& c, int l, const uint32_t* parties, int np, int k) {
+  using F = Fp<P>;
+  const int n = 4 * l;
+  GaoAbsent<F> a;
+  const F z = F::zero();
+  a.k = k, a.rho = n - np, a.listed = 0;
+  for (int i = 0; i < GAO_MAX_N; i++) a.ld.lam[i] = a.lamc[i] = a.root[i] = z, a.ld.row[i] = -1;
+  for (int i = 0; i < np; i++) a.ld.row[parties[i]] = i, a.listed |= 1u << parties[i];
+  a.lamc[0] = F::one();
+  int deg = 0;
+  for (int e = 0; e < n; e++)
+    if (!((a.listed >> e) & 1)) {
+      const F r = gao_lane_pow<F, 5>(c.wpow2, e);
+      a.root[deg++] = r;
+      for (int j = deg; j >= 0; j--) a.lamc[j] = (j ? a.lamc[j - 1] : z) - r * a.lamc[j];      // times (X - r)
+    }
+  auto lambda_at = [&](const F& x) {
+    F v = F::one();
+    for (int j = 0; j < a.rho; j++) v = v * (x - a.root[j]);
+    return v;
+  };
+  for (int p = 0; p < n; p++)
+    if ((a.listed >> p) & 1) a.ld.lam[p] = lambda_at(gao_lane_pow<F, 5>(c.wpow2, p));
+  for (int i = 0; i < 8; i++) {
+    a.slam[i] = i < l ? lambda_at(c.sec[i]).inverse() : z;
+    a.sscale[i] = a.slam[i] * c.ninv;
+  }
+  return a;
+}
+
+// x <- x / (X - r), exactly, for the coefficients a lane holds (stage 1's layout): b_{j-1} = a_j + r b_j from the top.
+// With SP = 2 a lane holds every second coefficient, b_i = a_{i+1} + r a_{i+2} + r^2 b_{i+2}: a_{i+1} is the other lane's,
+// one exchange per step -- xch(m, v) is the partner's v of step m (lane 0 sends its a_{2m+2}, lane 1 its a_{2m+1}).
+template <int M, int SP, class F, class Xch>
+ZK_HD void gao_deflate(F* x, const F& r, int q, Xch xch) {
+  if constexpr (SP == 1) {
+    F b = F::zero();
+    gao_static_for<0, M>([&](auto t_) {
+      constexpr int s = gao_bitrev(M - 1 - decltype(t_)::value, M);
+      const F a = x[s];
+      x[s] = b;
+      if constexpr (decltype(t_)::value == 0) b = a;
+      else b = a + r * b;
+    });
+  } else {
+    const F r2 = r.sqr();
+    F pa = F::zero(), pb = F::zero();
+    gao_static_for<0, M>([&](auto t_) {
+      constexpr int m = M - 1 - decltype(t_)::value, s = gao_bitrev(m, M);
+      const F a = x[s];
+      const F got = xch(m, q ? a : pa);
+      if constexpr (decltype(t_)::value == 0) x[s] = got;
+      else x[s] = got + r * pa + r2 * pb;
+      pa = a, pb = x[s];
+    });
+  }
+}
+
+// Stage 2's result for the word y~ (h' = h Lambda, errpos over all n places) -> the result for the listed shares.  slam: lane
+// i < l holds 1 / Lambda(g w_2l^i); lamc: lane j holds coefficient j of Lambda.  All lanes of the wave take every cross-lane
+// step; k division steps by the monic Lambda, and only when the message is wanted.
+template <class F, class G>
+ZK_HD void gao_absent_finish(const G& g, int k, int rho, uint32_t listed, bool want_message,
+                             const typename G::template V<F>& slam, const typename G::template V<F>& lamc,
+                             GaoResult<F, G>& r) {
+  using VF = typename G::template V<F>;
+  const F zero = F::zero();
+  const bool ok = r.status != 2 && !(r.errpos & ~listed);
+  r.status = ok ? r.status : 2;
+  r.errpos = ok ? r.errpos : 0;
+  r.sec = g.template make<F>([&](int p) { return ok ? g.at(r.sec, p) * g.at(slam, p) : zero; });
+  VF rem = g.template make<F>([&](int p) { return ok ? g.at(r.h, p) : zero; });
+  VF h = g.template make<F>([&](int) { return zero; });
+  if (want_message)
+    for (int j = k - 1; j >= 0; j--) {
+      const F q = g.bcast(rem, rho + j);
+      const VF sh = g.shift(lamc, j);
+      rem = g.template make<F>([&](int p) { return g.at(rem, p) - q * g.at(sh, p); });
+      h = g.template make<F>([&](int p) { return p == j ? q : g.at(h, p); });
+    }
+  r.h = h;
+}
+
 #if defined(__HIPCC__)
 class IEngine;
 struct DevBuf;
@@ -320,6 +439,11 @@ struct DevBuf;
 template <class FrP>
 int gao_unpack_robust_run(IEngine* e, DevBuf& wk, int l, const void* shares, size_t nchunks, int dimension, void* secrets,
                           void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
+// zk_pss_unpack_robust_parties: shares [nparties][nchunks] of the listed parties (NULL: 0 .. nparties - 1)
+template <class FrP>
+int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wk, int l, const void* shares, const uint32_t* parties, int nparties,
+                                  size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
+                                  uint32_t* errpos, uint64_t* summary, hipStream_t st);
 #endif
 
 }  // namespace zk

@@ -1,4 +1,5 @@
-// Kernels and host driver of zk_pss_unpack_robust (gao.hpp says what they compute).  Included by gao_<curve>.hip only.
+// Kernels and host drivers of zk_pss_unpack_robust and zk_pss_unpack_robust_parties (gao.hpp says what they compute).  Included
+// by gao_<curve>.hip only.  Each stage is one body with two kernels: the all-parties one, and the one for a party list (ER).
 //   stage 1  one lane per chunk (two at l = 8): the n shares are loaded once, transformed in registers, coefficients k .. n - 1 tested; a
 //            clean chunk gets its secrets (and message) and status 0, a dirty one is appended to a compact list
 //   stage 2  one group of n lanes per listed chunk: Gao's decoder (gao_chunk) over the wave's cross-lane builtins.  Launched
@@ -60,13 +61,18 @@ struct GaoWork {
 };
 
 // ---------------------------------------------------------------- stage 1
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
-                                                                size_t nchunks, int k, Fp<P>* __restrict__ secrets,
-                                                                Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
-                                                                uint32_t* __restrict__ errpos, GaoWork wk) {
+// ER: the form with absent parties (gao.hpp): the shares are rows of the listed parties, multiplied by Lambda(w^p) as they are
+// loaded -- ab by value, read at compile-time indices -- the word is tested and evaluated at dimension k + rho, a secret's last
+// product is by 1 / (n Lambda(g w_2l^i)) and the message is deflated by the rho roots of Lambda.  tab: the device table.
+template <class P, int L, bool ER>
+__device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const Fp<P>* __restrict__ shares, size_t nchunks,
+                                                int k, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
+                                                uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, const GaoWork& wk,
+                                                const GaoAbsentLoad<Fp<P>>* ab, int rho,
+                                                const GaoAbsent<Fp<P>>* __restrict__ tab) {
   using F = Fp<P>;
   constexpr int N = 4 * L, SP = gao_split(L), M = N / SP;
+  const int kd = ER ? k + rho : k;       // the dimension the word is tested and evaluated at
   __shared__ uint32_t wg_dirty, wg_base;
   if (threadIdx.x == 0) wg_dirty = 0;
   __syncthreads();
@@ -76,28 +82,51 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(const GaoConsts
   bool dirty = false;
   if (live) {
     F x[M];
-    gao_load<M, SP>(c, q, [&](int p) { return load_elem(shares + (size_t)p * nchunks + j); }, x);
+    if constexpr (ER)
+      gao_load<M, SP>(c, q, [&](int p) {
+        const int row = ab->row[p];
+        return row < 0 ? F::zero() : load_elem(shares + (size_t)row * nchunks + j) * ab->lam[p];
+      }, x);
+    else
+      gao_load<M, SP>(c, q, [&](int p) { return load_elem(shares + (size_t)p * nchunks + j); }, x);
     gao_ifft<M, SP>(c, x);
-    dirty = !gao_is_clean<M, SP>(x, k, q);
+    dirty = !gao_is_clean<M, SP>(x, kd, q);
     if (SP == 2) dirty = __shfl_xor((int)dirty, 1, 64) || dirty;
     if (!dirty) {
       if (q == 0) {
         status[j] = 0;
         if (errpos) errpos[j] = 0;
       }
-      if (message)
-        gao_clean_message<M, SP>(c, x, k, q, [&](int i, const F& v) { store_elem(message + (size_t)i * nchunks + j, v); });
-      if (secrets)
-        gao_clean_secrets<M, SP>(c, x, k, q, [&](int i, const F& v) {
-          F sum = v;
-          if (SP == 2) {           // the two lanes of the chunk are both here: add their parts
-            F o;
+      auto put_message = [&](int i, const F& v) { store_elem(message + (size_t)i * nchunks + j, v); };
+      auto put_secret = [&](int i, const F& v) {
+        F sum = v;
+        if (SP == 2) {           // the two lanes of the chunk are both here: add their parts
+          F o;
 #pragma unroll
-            for (int w = 0; w < F::N; w++) o.v[w] = (uint32_t)__shfl_xor((int)v.v[w], 1, 64);
-            sum = v + o;
+          for (int w = 0; w < F::N; w++) o.v[w] = (uint32_t)__shfl_xor((int)v.v[w], 1, 64);
+          sum = v + o;
+        }
+        if (q == 0) store_elem(secrets + j * L + i, sum);
+      };
+      if constexpr (!ER) {
+        if (message) gao_clean_message<M, SP>(c, x, k, q, put_message);
+        if (secrets) gao_clean_secrets<M, SP>(c, x, k, q, put_secret);
+      } else {
+        if (secrets) gao_clean_secrets<M, SP>(c, x, kd, q, [&](int i) { return tab->sscale[i]; }, put_secret);
+        if (message) {             // x = n h Lambda -> n h, root by root (the secrets above needed h Lambda)
+#pragma unroll 1
+          for (int e = 0; e < rho; e++) {
+            const F r = tab->root[e];
+            gao_deflate<M, SP>(x, r, q, [&](int, const F& v) {
+              F o;
+#pragma unroll
+              for (int w = 0; w < F::N; w++) o.v[w] = (uint32_t)__shfl_xor((int)v.v[w], 1, 64);
+              return o;
+            });
           }
-          if (q == 0) store_elem(secrets + j * L + i, sum);
-        });
+          gao_clean_message<M, SP>(c, x, k, q, put_message);
+        }
+      }
     }
   }
   if (q) dirty = false;                  // one entry per chunk
@@ -117,14 +146,31 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(const GaoConsts
   __syncthreads();
   if (dirty) wk.list[wg_base + wave_off + rank] = (uint32_t)j;
 }
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
+                                                                size_t nchunks, int k, Fp<P>* __restrict__ secrets,
+                                                                Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
+                                                                uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage1_body<P, L, false>(c, shares, nchunks, k, secrets, message, status, errpos, wk, nullptr, 0, nullptr);
+}
+// k: the caller's dimension
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
+    const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab, const GaoAbsent<Fp<P>>* __restrict__ tab,
+    const Fp<P>* __restrict__ shares, size_t nchunks, int k, int rho, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
+    uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage1_body<P, L, true>(c, shares, nchunks, k, secrets, message, status, errpos, wk, &ab, rho, tab);
+}
 
 // ---------------------------------------------------------------- stage 2
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_stage2_kernel(const GaoConsts<Fp<P>> c, int n, int l,
-                                                                const Fp<P>* __restrict__ shares, size_t nchunks, int k,
-                                                                Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
-                                                                uint8_t* __restrict__ status, uint32_t* __restrict__ errpos,
-                                                                GaoWork wk) {
+// ER: lane p reads its row and Lambda(w^p) from the device table (a run-time index: not from kernel arguments), the decoder
+// runs at dimension k + rho and gao_absent_finish maps its result back to the listed shares
+template <class P, bool ER>
+__device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n, int l, const Fp<P>* __restrict__ shares,
+                                                size_t nchunks, int k, Fp<P>* __restrict__ secrets,
+                                                Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
+                                                uint32_t* __restrict__ errpos, const GaoWork& wk,
+                                                const GaoAbsent<Fp<P>>* __restrict__ tab) {
   using F = Fp<P>;
   const uint32_t cnt = *wk.count;
   const uint32_t gpb = GAO_THREADS / n, stride = gridDim.x * gpb;
@@ -134,13 +180,23 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage2_kernel(const GaoConsts
   // this lane's points: w^p, w^-p and (lanes < l) g w_2l^p
   const F xp = gao_lane_pow<F, 5>(c.wpow2, p), xinv = gao_lane_pow<F, 5>(c.wipow2, p);
   const F sp = c.g * gao_lane_pow<F, 3>(c.spow2, p & 7);
+  int kd = k, rho = 0, row = p;
+  uint32_t listed = 0;
+  F lam, slam, lamc;
+  if constexpr (ER) {
+    rho = tab->rho, kd = k + rho, listed = tab->listed, row = tab->ld.row[p];
+    lam = tab->ld.lam[p], slam = tab->slam[p & 7], lamc = tab->lamc[p];
+  }
   uint32_t n_fixed = 0, n_status1 = 0, n_status2 = 0;       // this lane's part of the summary, added once at the end
   for (uint32_t first = blockIdx.x * gpb; first < cnt; first += stride) {       // (uniform over the workgroup)
     const uint32_t gi = first + threadIdx.x / n;
     const bool live = gi < cnt;
     const size_t j = live ? wk.list[gi] : 0;
-    const F y = live ? load_elem(shares + (size_t)p * nchunks + j) : F::zero();
-    const GaoResult<F, GaoDevGroup> r = gao_chunk<F, GaoDevGroup>(g, c, n, k, live, y, xp, xinv, sp);
+    F y;
+    if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * nchunks + j) * lam : F::zero();
+    else y = live ? load_elem(shares + (size_t)p * nchunks + j) : F::zero();
+    GaoResult<F, GaoDevGroup> r = gao_chunk<F, GaoDevGroup>(g, c, n, kd, live, y, xp, xinv, sp);
+    if constexpr (ER) gao_absent_finish<F, GaoDevGroup>(g, k, rho, listed, message != nullptr, slam, lamc, r);
     if (!live) continue;
     if (message && p < k) store_elem(message + (size_t)p * nchunks + j, r.h);
     if (secrets && p < l) store_elem(secrets + j * l + p, r.sec);
@@ -155,6 +211,30 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage2_kernel(const GaoConsts
   if (n_status1) atomicAdd(wk.summary + 1, (unsigned long long)n_status1);
   if (n_status2) atomicAdd(wk.summary + 2, (unsigned long long)n_status2);
   if (n_fixed) atomicAdd(wk.summary + 3 + p, (unsigned long long)n_fixed);
+}
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_stage2_kernel(const GaoConsts<Fp<P>> c, int n, int l,
+                                                                const Fp<P>* __restrict__ shares, size_t nchunks, int k,
+                                                                Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
+                                                                uint8_t* __restrict__ status, uint32_t* __restrict__ errpos,
+                                                                GaoWork wk) {
+  gao_stage2_body<P, false>(c, n, l, shares, nchunks, k, secrets, message, status, errpos, wk, nullptr);
+}
+// k: the caller's dimension
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_stage2_parties_kernel(
+    const GaoConsts<Fp<P>> c, const GaoAbsent<Fp<P>>* __restrict__ tab, int n, int l, const Fp<P>* __restrict__ shares,
+    size_t nchunks, int k, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
+    uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage2_body<P, true>(c, n, l, shares, nchunks, k, secrets, message, status, errpos, wk, tab);
+}
+// the table of a call, from the launch's arguments to working memory: one word per lane
+template <class F>
+__global__ __launch_bounds__(GAO_THREADS) void gao_absent_table_kernel(const GaoAbsent<F> a, GaoAbsent<F>* __restrict__ out) {
+  static_assert(sizeof(GaoAbsent<F>) % 4 == 0, "words");
+  const uint32_t* src = (const uint32_t*)&a;
+  uint32_t* dst = (uint32_t*)out;
+  for (uint32_t i = threadIdx.x; i < sizeof(GaoAbsent<F>) / 4; i += blockDim.x) dst[i] = src[i];
 }
 
 // ---------------------------------------------------------------- host driver
@@ -198,6 +278,62 @@ int gao_unpack_robust_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, 
   const size_t gpb = GAO_THREADS / n;
   const dim3 grid2((unsigned)std::min<size_t>((nchunks + gpb - 1) / gpb, GAO_STAGE2_GRID));
   gao_stage2_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, nchunks, dimension, sec, msg, status, errpos, wk);
+  GAO_HIP(hipGetLastError());
+  return ZK_OK;
+}
+// With all n parties listed this is the call above; otherwise the kernels' forms for absent parties, with the table of the
+// party list (gao_make_absent, host) put into working memory by a launch of its own ahead of them.
+template <class FrP>
+int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, const uint32_t* parties, int np,
+                                  size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
+                                  uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+  using Fr = Fp<FrP>;
+  const int n = 4 * l;
+  if (l != 1 && l != 2 && l != 4 && l != 8) return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
+  if (np <= 0 || np > n) return e->fail(ZK_ERR_BAD_INPUT, "bad party count");
+  uint32_t ids[GAO_MAX_N];
+  for (int i = 0; i < np; i++) {
+    ids[i] = parties ? parties[i] : (uint32_t)i;
+    if (ids[i] >= (uint32_t)n || (i > 0 && ids[i] <= ids[i - 1]))
+      return e->fail(ZK_ERR_BAD_INPUT, "party ids must be ascending and < n");
+  }
+  if (dimension < 1 || dimension > n - 1) return e->fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
+  if (np <= dimension) return e->fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
+  if (np == n)
+    return gao_unpack_robust_run<FrP>(e, wkbuf, l, shares, nchunks, dimension, secrets, message, status, errpos, summary, st);
+  if (nchunks == 0) return ZK_OK;
+  if (!shares || !status) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
+  if (nchunks >= ((size_t)1 << 32)) return e->fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
+  using Tab = GaoAbsent<Fr>;
+  constexpr size_t head = 320, tab_bytes = (sizeof(Tab) + 31) / 32 * 32;      // count, summary words, then the table
+  static_assert(sizeof(Tab) + 64 <= 4096, "the table travels as a kernel argument");
+  GAO_HIP(wkbuf.ensure(head + tab_bytes + nchunks * 4));
+  GaoWork wk;
+  wk.count = (uint32_t*)wkbuf.p;
+  wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkbuf.p + 32);
+  wk.list = (uint32_t*)((char*)wkbuf.p + head + tab_bytes);
+  Tab* tab = (Tab*)((char*)wkbuf.p + head);
+  GAO_HIP(hipMemsetAsync(wkbuf.p, 0, head, st));
+  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)(3 + n) * 8, st));
+  const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
+  const Tab a = gao_make_absent<FrP>(c, l, ids, np, dimension);
+  const dim3 blk(GAO_THREADS);
+  gao_absent_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(a, tab);
+  const size_t per_wg = GAO_THREADS / gao_split(l);
+  const dim3 grid1((unsigned)((nchunks + per_wg - 1) / per_wg));
+  const Fr* sh = (const Fr*)shares;
+  Fr* sec = (Fr*)secrets;
+  Fr* msg = (Fr*)message;
+  const int k = dimension, rho = a.rho;
+  switch (l) {
+    case 1: gao_stage1_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
+    case 2: gao_stage1_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
+    case 4: gao_stage1_parties_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
+    default: gao_stage1_parties_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
+  }
+  const size_t gpb = GAO_THREADS / n;
+  const dim3 grid2((unsigned)std::min<size_t>((nchunks + gpb - 1) / gpb, GAO_STAGE2_GRID));
+  gao_stage2_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, n, l, sh, nchunks, k, sec, msg, status, errpos, wk);
   GAO_HIP(hipGetLastError());
   return ZK_OK;
 }
