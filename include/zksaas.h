@@ -399,6 +399,45 @@ int zk_pss_unpack_robust_parties(zk_ctx* ctx, const void* shares_d /* [nparties]
                                  const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */, int nparties,
                                  size_t nchunks, int dimension, void* secrets_d, void* message_d, uint8_t* status_d,
                                  uint32_t* errpos_d, uint64_t* summary_d, void* stream);
+/* zk_pss_repair: the verdicts of zk_pss_unpack_robust, written back into the shares -- a corrected SHARE MATRIX, which the
+ * king steps below (and any other consumer of shares) then read unchanged.  secret-sharing/src/gao.rs:47-84 per chunk, as
+ * zk_pss_unpack_robust; the value written is the re-encoding of the decoded message, h(w_n^p).
+ * status_d, errpos_d and summary_d are exactly zk_pss_unpack_robust's on the same input, with the same encoding and the same
+ * error returns; summary_d is overwritten by the call.  shares_d changes only as follows: in a status-1 chunk the element of
+ * every party named in errpos is overwritten with h(w_n^p).  Every other element keeps its bytes: clean chunks, failed
+ * chunks, and the right shares of a corrected chunk.  A second call on the result reports the former status-1 chunks clean.
+ * All n parties only.  No host synchronisation, working memory from the stream's workspace.  Device engine only. */
+int zk_pss_repair(zk_ctx* ctx, void* shares_d /* [n][nchunks], in place */, size_t nchunks, int dimension,
+                  uint8_t* status_d /* [nchunks] */, uint32_t* errpos_d /* [nchunks], or NULL */,
+                  uint64_t* summary_d /* [3 + n], or NULL */, void* stream);
+/* Checked king rounds: each takes the unchecked call's arguments followed by status_d [chunks], errpos_d (or NULL) and
+ * summary_d [3 + n] (or NULL), runs zk_pss_repair on the word the king receives and then the unchecked king on the repaired
+ * matrix.  On honest input the output is bit for bit the unchecked call's under the same seed; on a repaired word it is the
+ * honest output.  A failed chunk (status 2) is NOT an error return: its shares go to the king as received, and the caller
+ * reads summary_d[2].  All n parties on this device; the unchecked calls are unchanged.  Device engine only.
+ *
+ * zk_fft2_king_checked: the king of d_fft / d_ifft (dist-primitives/src/dfft/mod.rs:264-304) on in_d [n][m/l], which is
+ * repaired IN PLACE at dimension 2l (gao.rs: up to l wrong shares per chunk are corrected).  status_d is [m/l], indexed by
+ * input chunk, which is column k of in_d.  nparties != n -> ZK_ERR_BAD_INPUT: the party list is the unchecked call's.
+ * in_d == out_d -> ZK_ERR_BAD_INPUT as for zk_fft2_king: the king's workgroups exchange chunks, it never runs in place. */
+int zk_fft2_king_checked(zk_ctx* ctx, void* in_d, const uint32_t* parties, int nparties, int log2_m, int inverse,
+                         const void* g, int scale_size_inv, int rearrange, uint64_t seed, void* out_d,
+                         const void* out_mask_d, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
+/* zk_d_fft_checked / zk_d_ifft_checked: zk_d_fft / zk_d_ifft with the king's word checked.  The word is what the
+ * reference's king receives, fft1(x) + in_mask, for d_ifft fft1(x) / m + in_mask (dfft/mod.rs:159, :254-258, the king
+ * :264-304); dimension 2l, so a party whose whole vector is wrong -- and up to l of them -- is named and corrected.
+ * shares_d is left untouched when out_d is given, as in the unchecked calls; status_d is [m/l]. */
+int zk_d_fft_checked(zk_ctx* ctx, void* shares_d, const void* in_mask_d, const void* out_mask_d, int rearrange, int log2_m,
+                     uint64_t seed, void* out_d, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
+int zk_d_ifft_checked(zk_ctx* ctx, void* shares_d, const void* in_mask_d, const void* out_mask_d, int rearrange, int log2_m,
+                      const void* g, uint64_t seed, void* out_d, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d,
+                      void* stream);
+/* zk_deg_red_checked: zk_deg_red with the king's word x + in_mask checked (dist-primitives/src/utils/deg_red.rs:99-115).
+ * The word has degree up to 4l - 2, so the dimension is 4l - 1 and cap = (n - 4l + 1) / 2 = 0 (gao.rs): this is DETECTION
+ * ONLY.  A chunk's status is 0 or 2, errpos is always 0, and nothing is ever rewritten: the output equals zk_deg_red's on the
+ * same input.  status_d is [len]. */
+int zk_deg_red_checked(zk_ctx* ctx, void* x_d, const void* in_mask_d, const void* out_mask_d, size_t len, uint64_t seed,
+                       uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

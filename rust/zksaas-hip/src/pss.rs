@@ -143,6 +143,157 @@ fn robust_impl<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], partie
     })
 }
 
+/// The verdicts of [`repair_vec`] and of the checked king rounds: [`RobustUnpack`] without secrets and message.
+pub struct Verdicts {
+    pub verdicts: Vec<Verdict>,
+    /// bit `p` set: party `p`'s share of the chunk was wrong and has been replaced
+    pub errpos: Vec<u32>,
+    /// chunks clean, corrected, failed
+    pub counts: [u64; 3],
+    /// per party, the number of chunks in which its share was corrected
+    pub corrected_per_party: Vec<u64>,
+}
+
+struct VerdictBufs {
+    st: DeviceBuf,
+    ep: DeviceBuf,
+    sm: DeviceBuf,
+    nchunks: usize,
+}
+impl VerdictBufs {
+    fn alloc(ctx: &Context, nchunks: usize) -> Result<Self, MpcNetError> {
+        Ok(VerdictBufs { st: DeviceBuf::alloc(ctx, nchunks)?, ep: DeviceBuf::alloc(ctx, nchunks * 4)?,
+                         sm: DeviceBuf::alloc(ctx, (3 + ctx.n) * 8)?, nchunks })
+    }
+    fn read(&self, ctx: &Context) -> Result<Verdicts, MpcNetError> {
+        let status: Vec<u8> = self.st.to_vec(self.nchunks)?;
+        let summary: Vec<u64> = if self.nchunks == 0 { vec![0; 3 + ctx.n] } else { self.sm.to_vec(3 + ctx.n)? };
+        Ok(Verdicts {
+            verdicts: status.iter().map(|s| match s { 0 => Verdict::Clean, 1 => Verdict::Corrected, _ => Verdict::Failed }).collect(),
+            errpos: self.ep.to_vec(self.nchunks)?,
+            counts: [summary[0], summary[1], summary[2]],
+            corrected_per_party: summary[3..].to_vec(),
+        })
+    }
+}
+
+fn rows<F: PrimeField>(buf: &DeviceBuf, n: usize, len: usize) -> Result<Vec<Vec<F>>, MpcNetError> {
+    let flat: Vec<F> = buf.to_vec(n * len)?;
+    Ok(flat.chunks(len.max(1)).map(|c| c.to_vec()).collect())
+}
+
+/// `zk_pss_repair`: the verdicts of [`unpack_robust_vec`] written back into the shares -- `decode_to_message`
+/// (`secret-sharing/src/gao.rs:47-84`) per chunk, then the share of every party named in `errpos` replaced by the
+/// decoded polynomial's value.  Every other share is returned as it came: clean chunks, failed chunks, the right shares
+/// of a corrected chunk.  All `n` parties.
+pub fn repair_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], dimension: usize)
+                                           -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, ctx.n)?;
+    let sh = DeviceBuf::from_slice(ctx, &flat)?;
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    check(ctx, unsafe {
+        sys::zk_pss_repair(ctx.raw(), sh.ptr(), nchunks, dimension as i32, v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32,
+                           v.sm.ptr() as *mut u64, ptr::null_mut())
+    })?;
+    Ok((rows(&sh, ctx.n, nchunks)?, v.read(ctx)?))
+}
+
+/// The king of `d_fft` / `d_ifft` (`dist-primitives/src/dfft/mod.rs:264-304`) on all `n` parties' vectors after
+/// `fft1_in_place`, with the received word repaired first (`zk_fft2_king_checked`; dimension `2l`: up to `l` wrong
+/// shares per chunk).  Returns the parties' output shares, the repaired input and the verdicts per input chunk.  A failed
+/// chunk is no error: its shares reach the king as received, `counts[2]` says how many.
+#[allow(clippy::too_many_arguments)]
+pub fn fft2_king_checked_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], log2_m: u32, inverse: bool, g: F,
+                                                      scale_size_inv: bool, rearrange: bool, out_mask: Option<&[F]>)
+                                                      -> Result<(Vec<Vec<F>>, Vec<Vec<F>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, ctx.n)?;
+    let sh = DeviceBuf::from_slice(ctx, &flat)?;
+    let out = DeviceBuf::alloc(ctx, flat.len() * core::mem::size_of::<F>())?;
+    let om = match out_mask { Some(m) => Some(DeviceBuf::from_slice(ctx, m)?), None => None };
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    let gl = [g];
+    check(ctx, unsafe {
+        sys::zk_fft2_king_checked(ctx.raw(), sh.ptr(), ptr::null(), ctx.n as i32, log2_m as i32, inverse as i32, fr_ptr(&gl),
+                                  scale_size_inv as i32, rearrange as i32, 0, out.ptr(),
+                                  om.as_ref().map_or(ptr::null(), |b| b.ptr() as *const core::ffi::c_void),
+                                  v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64, ptr::null_mut())
+    })?;
+    Ok((rows(&out, ctx.n, nchunks)?, rows(&sh, ctx.n, nchunks)?, v.read(ctx)?))
+}
+
+/// `d_fft` (`dfft/mod.rs:99-134`) for all `n` parties on this device with the king's word `fft1(x) + in_mask` repaired
+/// first (`zk_d_fft_checked`): a party whose whole vector is wrong -- and up to `l` of them -- is named in the verdicts
+/// and the output is the honest one.  `in_mask` / `out_mask`: all parties' masks `[n][m/l]` flattened, or `None`.
+pub fn d_fft_checked_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], in_mask: Option<&[F]>,
+                                                  out_mask: Option<&[F]>, rearrange: bool, log2_m: u32)
+                                                  -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    transform_checked(ctx, shares, in_mask, out_mask, rearrange, log2_m, None)
+}
+
+/// `d_ifft` (`dfft/mod.rs:137-175`) in the same way (`zk_d_ifft_checked`): the word is `fft1(x) / m + in_mask` (`:159`).
+pub fn d_ifft_checked_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], in_mask: Option<&[F]>,
+                                                   out_mask: Option<&[F]>, rearrange: bool, log2_m: u32, g: F)
+                                                   -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    transform_checked(ctx, shares, in_mask, out_mask, rearrange, log2_m, Some(g))
+}
+
+fn transform_checked<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], in_mask: Option<&[F]>,
+                                              out_mask: Option<&[F]>, rearrange: bool, log2_m: u32, g: Option<F>)
+                                              -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, ctx.n)?;
+    let sh = DeviceBuf::from_slice(ctx, &flat)?;
+    let up = |m: Option<&[F]>| -> Result<Option<DeviceBuf>, MpcNetError> {
+        match m {
+            Some(m) if m.len() != flat.len() => Err(MpcNetError::BadInput { err: "FftMask length differs from the share vectors" }),
+            Some(m) => Ok(Some(DeviceBuf::from_slice(ctx, m)?)),
+            None => Ok(None),
+        }
+    };
+    let (im, om) = (up(in_mask)?, up(out_mask)?);
+    let p = |b: &Option<DeviceBuf>| b.as_ref().map_or(ptr::null(), |b| b.ptr() as *const core::ffi::c_void);
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    check(ctx, unsafe {
+        match g {
+            None => sys::zk_d_fft_checked(ctx.raw(), sh.ptr(), p(&im), p(&om), rearrange as i32, log2_m as i32, 0,
+                                          ptr::null_mut(), v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32,
+                                          v.sm.ptr() as *mut u64, ptr::null_mut()),
+            Some(g) => {
+                let gl = [g];
+                sys::zk_d_ifft_checked(ctx.raw(), sh.ptr(), p(&im), p(&om), rearrange as i32, log2_m as i32, fr_ptr(&gl), 0,
+                                       ptr::null_mut(), v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32,
+                                       v.sm.ptr() as *mut u64, ptr::null_mut())
+            }
+        }
+    })?;
+    Ok((rows(&sh, ctx.n, nchunks)?, v.read(ctx)?))
+}
+
+/// `deg_red` (`dist-primitives/src/utils/deg_red.rs:99-115`) for all `n` parties on this device with the king's word
+/// `x + in_mask` checked (`zk_deg_red_checked`).  The word has dimension `4l - 1`, which leaves no redundancy to correct
+/// with (`gao.rs`: cap `(n - k) / 2 = 0`): DETECTION ONLY.  A verdict is `Clean` or `Failed`, and the output is
+/// `deg_red`'s on the same input.
+pub fn deg_red_checked_vec<F: PrimeField + 'static>(ctx: &Context, x_shares: &[Vec<F>], in_mask: Option<&[F]>,
+                                                    out_mask: Option<&[F]>)
+                                                    -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    let (flat, len) = flatten(ctx, x_shares, ctx.n)?;
+    let x = DeviceBuf::from_slice(ctx, &flat)?;
+    let up = |m: Option<&[F]>| -> Result<Option<DeviceBuf>, MpcNetError> {
+        match m {
+            Some(m) if m.len() != flat.len() => Err(MpcNetError::BadInput { err: "DegRedMask length differs from the share vectors" }),
+            Some(m) => Ok(Some(DeviceBuf::from_slice(ctx, m)?)),
+            None => Ok(None),
+        }
+    };
+    let (im, om) = (up(in_mask)?, up(out_mask)?);
+    let p = |b: &Option<DeviceBuf>| b.as_ref().map_or(ptr::null(), |b| b.ptr() as *const core::ffi::c_void);
+    let v = VerdictBufs::alloc(ctx, len)?;
+    check(ctx, unsafe {
+        sys::zk_deg_red_checked(ctx.raw(), x.ptr(), p(&im), p(&om), len, 0, v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32,
+                                v.sm.ptr() as *mut u64, ptr::null_mut())
+    })?;
+    Ok((rows(&x, ctx.n, len)?, v.read(ctx)?))
+}
+
 fn flatten<F: PrimeField>(_ctx: &Context, shares: &[Vec<F>], want: usize) -> Result<(Vec<F>, usize), MpcNetError> {
     if shares.len() != want || shares.is_empty() {
         return Err(MpcNetError::BadInput { err: "unpack: one share vector per listed party expected" });

@@ -198,6 +198,25 @@ class PackedSharingParams(Context):
                                                               _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
+    def _report(self, nchunks, dimension):
+        """the verdict buffers of a repair or of a checked king round: a RobustUnpack without secrets and message"""
+        r = RobustUnpack(self, nchunks, dimension)
+        r.status = DeviceBuffer(self, nchunks)
+        r.errpos = DeviceBuffer(self, 4 * nchunks)
+        r.summary_d = DeviceBuffer(self, 8 * (3 + self.n))
+        return r
+
+    def repair(self, shares_d, nchunks, dimension=None, stream=None):
+        """zk_pss_repair: unpack_robust's verdicts written back into shares_d [n][nchunks], in place: in a corrected chunk the
+        share of every party named in errpos becomes the decoded polynomial's value, every other element keeps its bytes.
+        Returns a RobustUnpack with status, errpos and summary (no secrets, no message); `out` is shares_d."""
+        k = 2 * self.l if dimension is None else int(dimension)
+        r = self._report(nchunks, k)
+        r.out = shares_d
+        self._check(self.lib.zk_pss_repair(self.h, _ptr(shares_d), nchunks, k, _ptr(r.status), _ptr(r.errpos),
+                                           _ptr(r.summary_d), stream))
+        return r
+
     def lagrange_unpack(self, shares_d, nchunks, parties, out=None, stream=None):
         return self.unpack2(shares_d, nchunks, parties, out, stream)
 
@@ -205,7 +224,9 @@ class PackedSharingParams(Context):
 
 
 class RobustUnpack:
-    """Result of PackedSharingParams.unpack_robust.  Device buffers: secrets [nchunks * l] (order 0), status [nchunks] bytes
+    """Result of PackedSharingParams.unpack_robust, and the report of PackedSharingParams.repair and of the checked king rounds
+    (d_fft / d_ifft / deg_red / fft2_king with check=True), which leave secrets and message None and set `out` to the buffer
+    that holds the call's result.  Device buffers: secrets [nchunks * l] (order 0), status [nchunks] bytes
     (0 clean, 1 corrected, 2 failed), errpos [nchunks] u32 (bit p: party p's share was corrected), summary_d [3 + n] u64,
     message [dimension][nchunks] or None.  `summary` downloads summary_d: [clean, corrected, failed] + per party the number
     of chunks in which its share was corrected.  `parties`: the party list the call was given, None for all n."""
@@ -213,7 +234,7 @@ class RobustUnpack:
 
     def __init__(self, ctx, nchunks, dimension, parties=None):
         self.ctx, self.nchunks, self.dimension, self.parties = ctx, nchunks, dimension, parties
-        self.secrets = self.status = self.errpos = self.summary_d = self.message = None
+        self.secrets = self.status = self.errpos = self.summary_d = self.message = self.out = None
 
     @property
     def summary(self):
@@ -316,23 +337,66 @@ def deal_masks(pp, nproofs, log2_m, g1_gen_affine, g2_gen_affine, seed, masks_ct
                                            None if g2 is None else g2.ctypes.data, seed, C.byref(masks_ct), stream))
 
 
-def d_fft(pp, shares_d, fft_mask, rearrange, log2_m, seed=0, out=None, stream=None):
-    """dfft/mod.rs:99-134 for all parties; shares_d [n][m/l].  Result in `out` (or back in shares_d if None)."""
+def fft2_king(pp, in_d, log2_m, inverse=False, g=None, scale_size_inv=False, rearrange=False, seed=0, out=None, out_mask=None,
+              parties=None, check=False, stream=None):
+    """zk_fft2_king, the king of d_fft / d_ifft (dfft/mod.rs:264-304) on in_d [nparties][m/l]; never in place.  Returns `out`.
+    check=True (all n parties): zk_fft2_king_checked -- in_d is repaired in place first (dimension 2l); returns the report, a
+    RobustUnpack whose `out` is the output buffer."""
+    out = out or pp.alloc_fr(pp.n * ((1 << log2_m) // pp.l))
+    garr = None if g is None else pp.fr.encode_one(g)
+    gp = None if garr is None else garr.ctypes.data
+    arr, np_ = (None, pp.n) if parties is None else ((C.c_uint32 * len(parties))(*parties), len(parties))
+    if not check:
+        pp._check(pp.lib.zk_fft2_king(pp.h, _ptr(in_d), arr, np_, log2_m, int(inverse), gp, int(scale_size_inv), int(rearrange),
+                                      seed, _ptr(out), _ptr(out_mask), stream))
+        return out
+    r = pp._report((1 << log2_m) // pp.l, 2 * pp.l)
+    r.out = out
+    pp._check(pp.lib.zk_fft2_king_checked(pp.h, _ptr(in_d), arr, np_, log2_m, int(inverse), gp, int(scale_size_inv),
+                                          int(rearrange), seed, _ptr(out), _ptr(out_mask), _ptr(r.status), _ptr(r.errpos),
+                                          _ptr(r.summary_d), stream))
+    return r
+
+
+def d_fft(pp, shares_d, fft_mask, rearrange, log2_m, seed=0, out=None, stream=None, check=False):
+    """dfft/mod.rs:99-134 for all parties; shares_d [n][m/l].  Result in `out` (or back in shares_d if None).
+    check=True: zk_d_fft_checked -- the word the king receives is repaired first (up to l wrong parties per chunk); returns
+    the report, a RobustUnpack whose `out` is the buffer with the result."""
+    if check:
+        r = pp._report((1 << log2_m) // pp.l, 2 * pp.l)
+        r.out = shares_d if out is None else out
+        pp._check(pp.lib.zk_d_fft_checked(pp.h, _ptr(shares_d), _ptr(fft_mask.in_mask), _ptr(fft_mask.out_mask), int(rearrange),
+                                          log2_m, seed, _ptr(out), _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
     pp._check(pp.lib.zk_d_fft(pp.h, _ptr(shares_d), _ptr(fft_mask.in_mask), _ptr(fft_mask.out_mask), int(rearrange),
                               log2_m, seed, _ptr(out), stream))
     return shares_d if out is None else out
 
 
-def d_ifft(pp, shares_d, fft_mask, rearrange, log2_m, g=None, seed=0, out=None, stream=None):
-    """dfft/mod.rs:137-175; g is an int (coset shift, 1 if None)."""
+def d_ifft(pp, shares_d, fft_mask, rearrange, log2_m, g=None, seed=0, out=None, stream=None, check=False):
+    """dfft/mod.rs:137-175; g is an int (coset shift, 1 if None).  check=True: zk_d_ifft_checked, as d_fft's."""
     garr = None if g is None else pp.fr.encode_one(g)
+    if check:
+        r = pp._report((1 << log2_m) // pp.l, 2 * pp.l)
+        r.out = shares_d if out is None else out
+        pp._check(pp.lib.zk_d_ifft_checked(pp.h, _ptr(shares_d), _ptr(fft_mask.in_mask), _ptr(fft_mask.out_mask),
+                                           int(rearrange), log2_m, None if garr is None else garr.ctypes.data, seed, _ptr(out),
+                                           _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
     pp._check(pp.lib.zk_d_ifft(pp.h, _ptr(shares_d), _ptr(fft_mask.in_mask), _ptr(fft_mask.out_mask), int(rearrange),
                                log2_m, None if garr is None else garr.ctypes.data, seed, _ptr(out), stream))
     return shares_d if out is None else out
 
 
-def deg_red(pp, x_d, mask, length, seed=0, stream=None):
-    """utils/deg_red.rs:80-126 over Fr; x_d [n][length] in place."""
+def deg_red(pp, x_d, mask, length, seed=0, stream=None, check=False):
+    """utils/deg_red.rs:80-126 over Fr; x_d [n][length] in place.  check=True: zk_deg_red_checked -- detection only (the
+    word x + in_mask has dimension 4l - 1: a status is 0 or 2 and nothing is rewritten); returns the report, `out` is x_d."""
+    if check:
+        r = pp._report(length, 4 * pp.l - 1)
+        r.out = x_d
+        pp._check(pp.lib.zk_deg_red_checked(pp.h, _ptr(x_d), _ptr(mask.in_mask), _ptr(mask.out_mask), length, seed,
+                                            _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
     pp._check(pp.lib.zk_deg_red(pp.h, _ptr(x_d), _ptr(mask.in_mask), _ptr(mask.out_mask), length, seed, stream))
     return x_d
 

@@ -397,6 +397,18 @@ class IEngine {
   virtual int pss_unpack_robust_parties(const void* shares, const uint32_t* parties, int nparties, size_t nchunks,
                                         int dimension, void* secrets, void* message, uint8_t* status, uint32_t* errpos,
                                         uint64_t* summary, hipStream_t st) = 0;
+  // zk_pss_repair: the verdicts of pss_unpack_robust, written back into the shares [n][nchunks]
+  virtual int pss_repair(void* shares, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                         hipStream_t st) = 0;
+  // the king rounds with the received word repaired first (all n parties; engine_gao.inc.hpp)
+  virtual int fft2_king_checked(void* in, const uint32_t* parties, int np, int log_m, int inverse, const void* g,
+                                int scale_size_inv, int rearrange, uint64_t seed, void* out, const void* out_mask,
+                                uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  virtual int d_fft_checked(void* shares, const void* in_mask, const void* out_mask, int rearrange, int log_m, int inverse,
+                            const void* g, uint64_t seed, void* out, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                            hipStream_t st) = 0;
+  virtual int deg_red_checked(void* x, const void* in_mask, const void* out_mask, size_t len, uint64_t seed, uint8_t* status,
+                              uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,

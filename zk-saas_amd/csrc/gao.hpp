@@ -8,6 +8,9 @@
 //   gao_load / gao_ifft / gao_is_clean / gao_clean_secrets   one lane (two at l = 8), one chunk: the syndrome test and the
 //                                                 clean unpack (stage 1)
 //   gao_chunk                                     n lanes, one chunk: Gao's decoder (stage 2), written against a lane group
+// zk_pss_repair runs the same two parts without secrets and message: stage 1 up to gao_is_clean (the scan), and the decoder
+// with its flag RE, whose re-encoding h(w_n^p) replaces the share of every party named in errpos (section "repair" below;
+// tests/native/gao_repair_host_test.cpp runs that text).
 // The lane group G gives the decoder its cross-lane operations -- broadcast from a lane, shift by d lanes, ballot, any -- with
 // a value of type G::V<T> holding one T per lane: GaoDevGroup (gao_impl.hpp) maps them to the wave's cross-lane builtins and
 // V<T> = T, GaoHostGroup below is a loop over an array of n lanes.  Lane p holds coefficient p of a polynomial.
@@ -220,12 +223,20 @@ struct GaoHostGroup {
 ZK_HD int gao_top_bit(uint32_t m) { return m ? 31 - __builtin_clz(m) : -1; }
 ZK_HD int gao_popcount(uint32_t m) { return __builtin_popcount(m); }
 
-template <class F, class G>
-struct GaoResult {
+// RE (zk_pss_repair): the result also carries the re-encoding h(w_n^p) every lane computes for the comparison with its share,
+// and the secrets are not evaluated.  A flag and not a member of every result: the unpack kernels keep their registers.
+template <class VF, bool RE>
+struct GaoReencoding {};
+template <class VF>
+struct GaoReencoding<VF, true> {
+  VF ev;                               // lane p: h(w_n^p), zero on failure
+};
+template <class F, class G, bool RE = false>
+struct GaoResult : GaoReencoding<typename G::template V<F>, RE> {
   int status;                          // 1 or 2 (a clean word never reaches the decoder)
   uint32_t errpos;
   typename G::template V<F> h;         // lane j: coefficient j of the message, zero for j >= k and on failure
-  typename G::template V<F> sec;       // lane i < l: secret i
+  typename G::template V<F> sec;       // lane i < l: secret i (zero with RE)
 };
 
 // One chunk, all n lanes of the group together.  y: lane p holds share p; xp, xinv: w_n^p and w_n^-p; sp: g w_2l^p (read in
@@ -238,8 +249,8 @@ struct GaoResult {
 // z = X^n - 1 has n + 1 coefficients: the first step is taken in closed form, lc(R) z - X^(n - deg R) R, whose X^n terms cancel.
 // Every loop has a static bound and runs while any group of the wave is active, so no cross-lane read sits in divergent code
 // and no share vector makes the decoder spin.
-template <class F, class G>
-ZK_HD GaoResult<F, G> gao_chunk(const G& g, const GaoConsts<F>& c, int n, int k, bool live,
+template <class F, class G, bool RE = false>
+ZK_HD GaoResult<F, G, RE> gao_chunk(const G& g, const GaoConsts<F>& c, int n, int k, bool live,
                                 const typename G::template V<F>& y, const typename G::template V<F>& xp,
                                 const typename G::template V<F>& xinv, const typename G::template V<F>& sp) {
   using VF = typename G::template V<F>;
@@ -309,16 +320,28 @@ ZK_HD GaoResult<F, G> gao_chunk(const G& g, const GaoConsts<F>& c, int n, int k,
   for (int j = k - 1; j >= 0; j--) {
     const F hj = g.bcast(h, j);
     ev = g.template make<F>([&](int p) { return g.at(ev, p) * g.at(xp, p) + hj; });
-    sv = g.template make<F>([&](int p) { return g.at(sv, p) * g.at(sp, p) + hj; });
+    if constexpr (!RE) sv = g.template make<F>([&](int p) { return g.at(sv, p) * g.at(sp, p) + hj; });
   }
   const uint32_t diff = g.ballot([&](int p) { return g.at(ev, p) != g.at(y, p); });
   if (gao_popcount(diff) > cap) ok = false;
-  GaoResult<F, G> out;
+  GaoResult<F, G, RE> out;
+  if constexpr (RE) out.ev = g.template make<F>([&](int p) { return ok ? g.at(ev, p) : zero; });
   out.status = ok ? 1 : 2;
   out.errpos = ok ? diff : 0;
   out.h = g.template make<F>([&](int p) { return ok ? g.at(h, p) : zero; });
   out.sec = g.template make<F>([&](int p) { return ok ? g.at(sv, p) : zero; });
   return out;
+}
+
+// ---------------------------------------------------------------- repair (zk_pss_repair)
+// What the decoder's verdict does to the received word, lane by lane: put(p, h(w_n^p)) for every party p named in the errpos
+// of a corrected chunk.  A failed chunk has errpos 0 and a clean one never reaches the decoder: nothing else is written.
+template <class F, class G, class Put>
+ZK_HD void gao_repair_word(const G& g, const GaoResult<F, G, true>& r, Put put) {
+  g.template make<int>([&](int p) {
+    if (r.status == 1 && ((r.errpos >> p) & 1)) put(p, g.at(r.ev, p));
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------- absent parties (zk_pss_unpack_robust_parties)
@@ -439,6 +462,10 @@ struct DevBuf;
 template <class FrP>
 int gao_unpack_robust_run(IEngine* e, DevBuf& wk, int l, const void* shares, size_t nchunks, int dimension, void* secrets,
                           void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
+// zk_pss_repair: shares [n][nchunks] in place, the verdicts of the call above
+template <class FrP>
+int gao_repair_run(IEngine* e, DevBuf& wk, int l, void* shares, size_t nchunks, int dimension, uint8_t* status,
+                   uint32_t* errpos, uint64_t* summary, hipStream_t st);
 // zk_pss_unpack_robust_parties: shares [nparties][nchunks] of the listed parties (NULL: 0 .. nparties - 1)
 template <class FrP>
 int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wk, int l, const void* shares, const uint32_t* parties, int nparties,

@@ -5,6 +5,8 @@
 //   stage 2  one group of n lanes per listed chunk: Gao's decoder (gao_chunk) over the wave's cross-lane builtins.  Launched
 //            unconditionally with a grid derived from nchunks; it reads the count from device memory, strides over the list and
 //            leaves at once when the count is zero -- so the call never synchronises with the host.
+// zk_pss_repair is the all-parties form of both with no secrets and no message: stage 1 ends at the test of the coefficients
+// (SCAN: the scan kernel), stage 2 stores lane p's re-encoding over the share of a party named in errpos (REPAIR).
 #pragma once
 #include <algorithm>
 
@@ -64,7 +66,9 @@ struct GaoWork {
 // ER: the form with absent parties (gao.hpp): the shares are rows of the listed parties, multiplied by Lambda(w^p) as they are
 // loaded -- ab by value, read at compile-time indices -- the word is tested and evaluated at dimension k + rho, a secret's last
 // product is by 1 / (n Lambda(g w_2l^i)) and the message is deflated by the rho roots of Lambda.  tab: the device table.
-template <class P, int L, bool ER>
+// SCAN: the inverse transform and the test only -- status and errpos of a clean chunk, the list of the dirty ones, no secrets
+// and no message: 1 / 5 / 17 products per chunk at l = 1, 2, 4; at l = 8 the two lanes' 17 each and the 15 of the split.
+template <class P, int L, bool ER, bool SCAN = false>
 __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const Fp<P>* __restrict__ shares, size_t nchunks,
                                                 int k, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
                                                 uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, const GaoWork& wk,
@@ -97,34 +101,36 @@ __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const
         status[j] = 0;
         if (errpos) errpos[j] = 0;
       }
-      auto put_message = [&](int i, const F& v) { store_elem(message + (size_t)i * nchunks + j, v); };
-      auto put_secret = [&](int i, const F& v) {
-        F sum = v;
-        if (SP == 2) {           // the two lanes of the chunk are both here: add their parts
-          F o;
+      if constexpr (!SCAN) {
+        auto put_message = [&](int i, const F& v) { store_elem(message + (size_t)i * nchunks + j, v); };
+        auto put_secret = [&](int i, const F& v) {
+          F sum = v;
+          if (SP == 2) {           // the two lanes of the chunk are both here: add their parts
+            F o;
 #pragma unroll
-          for (int w = 0; w < F::N; w++) o.v[w] = (uint32_t)__shfl_xor((int)v.v[w], 1, 64);
-          sum = v + o;
-        }
-        if (q == 0) store_elem(secrets + j * L + i, sum);
-      };
-      if constexpr (!ER) {
-        if (message) gao_clean_message<M, SP>(c, x, k, q, put_message);
-        if (secrets) gao_clean_secrets<M, SP>(c, x, k, q, put_secret);
-      } else {
-        if (secrets) gao_clean_secrets<M, SP>(c, x, kd, q, [&](int i) { return tab->sscale[i]; }, put_secret);
-        if (message) {             // x = n h Lambda -> n h, root by root (the secrets above needed h Lambda)
-#pragma unroll 1
-          for (int e = 0; e < rho; e++) {
-            const F r = tab->root[e];
-            gao_deflate<M, SP>(x, r, q, [&](int, const F& v) {
-              F o;
-#pragma unroll
-              for (int w = 0; w < F::N; w++) o.v[w] = (uint32_t)__shfl_xor((int)v.v[w], 1, 64);
-              return o;
-            });
+            for (int w = 0; w < F::N; w++) o.v[w] = (uint32_t)__shfl_xor((int)v.v[w], 1, 64);
+            sum = v + o;
           }
-          gao_clean_message<M, SP>(c, x, k, q, put_message);
+          if (q == 0) store_elem(secrets + j * L + i, sum);
+        };
+        if constexpr (!ER) {
+          if (message) gao_clean_message<M, SP>(c, x, k, q, put_message);
+          if (secrets) gao_clean_secrets<M, SP>(c, x, k, q, put_secret);
+        } else {
+          if (secrets) gao_clean_secrets<M, SP>(c, x, kd, q, [&](int i) { return tab->sscale[i]; }, put_secret);
+          if (message) {             // x = n h Lambda -> n h, root by root (the secrets above needed h Lambda)
+#pragma unroll 1
+            for (int e = 0; e < rho; e++) {
+              const F r = tab->root[e];
+              gao_deflate<M, SP>(x, r, q, [&](int, const F& v) {
+                F o;
+#pragma unroll
+                for (int w = 0; w < F::N; w++) o.v[w] = (uint32_t)__shfl_xor((int)v.v[w], 1, 64);
+                return o;
+              });
+            }
+            gao_clean_message<M, SP>(c, x, k, q, put_message);
+          }
         }
       }
     }
@@ -153,6 +159,12 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(const GaoConsts
                                                                 uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage1_body<P, L, false>(c, shares, nchunks, k, secrets, message, status, errpos, wk, nullptr, 0, nullptr);
 }
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_scan_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
+                                                              size_t nchunks, int k, uint8_t* __restrict__ status,
+                                                              uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage1_body<P, L, false, true>(c, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr, 0, nullptr);
+}
 // k: the caller's dimension
 template <class P, int L>
 __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
@@ -165,8 +177,12 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
 // ---------------------------------------------------------------- stage 2
 // ER: lane p reads its row and Lambda(w^p) from the device table (a run-time index: not from kernel arguments), the decoder
 // runs at dimension k + rho and gao_absent_finish maps its result back to the listed shares
-template <class P, bool ER>
-__device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n, int l, const Fp<P>* __restrict__ shares,
+// REPAIR: `shares` is written: lane p stores its re-encoding h(w_n^p) when bit p of the final errpos is set; no secrets, no
+// message (the decoder's flag RE)
+template <class P, bool REPAIR>
+using GaoSharesPtr = std::conditional_t<REPAIR, Fp<P>*, const Fp<P>* __restrict__>;
+template <class P, bool ER, bool REPAIR = false>
+__device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n, int l, GaoSharesPtr<P, REPAIR> shares,
                                                 size_t nchunks, int k, Fp<P>* __restrict__ secrets,
                                                 Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
                                                 uint32_t* __restrict__ errpos, const GaoWork& wk,
@@ -195,11 +211,15 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
     F y;
     if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * nchunks + j) * lam : F::zero();
     else y = live ? load_elem(shares + (size_t)p * nchunks + j) : F::zero();
-    GaoResult<F, GaoDevGroup> r = gao_chunk<F, GaoDevGroup>(g, c, n, kd, live, y, xp, xinv, sp);
+    GaoResult<F, GaoDevGroup, REPAIR> r = gao_chunk<F, GaoDevGroup, REPAIR>(g, c, n, kd, live, y, xp, xinv, sp);
     if constexpr (ER) gao_absent_finish<F, GaoDevGroup>(g, k, rho, listed, message != nullptr, slam, lamc, r);
     if (!live) continue;
-    if (message && p < k) store_elem(message + (size_t)p * nchunks + j, r.h);
-    if (secrets && p < l) store_elem(secrets + j * l + p, r.sec);
+    if constexpr (REPAIR) {
+      gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(shares + (size_t)lane * nchunks + j, v); });
+    } else {
+      if (message && p < k) store_elem(message + (size_t)p * nchunks + j, r.h);
+      if (secrets && p < l) store_elem(secrets + j * l + p, r.sec);
+    }
     if (p == 0) {
       status[j] = (uint8_t)r.status;
       if (errpos) errpos[j] = r.errpos;
@@ -219,6 +239,12 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage2_kernel(const GaoConsts
                                                                 uint8_t* __restrict__ status, uint32_t* __restrict__ errpos,
                                                                 GaoWork wk) {
   gao_stage2_body<P, false>(c, n, l, shares, nchunks, k, secrets, message, status, errpos, wk, nullptr);
+}
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_repair_kernel(const GaoConsts<Fp<P>> c, int n, int l, Fp<P>* shares,
+                                                                size_t nchunks, int k, uint8_t* __restrict__ status,
+                                                                uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage2_body<P, false, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr);
 }
 // k: the caller's dimension
 template <class P>
@@ -244,9 +270,11 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_absent_table_kernel(const Gao
     if (_e != hipSuccess) return e->hip_fail(_e, #expr); \
   } while (0)
 
-template <class FrP>
-int gao_unpack_robust_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, size_t nchunks, int dimension, void* secrets,
-                          void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+// REPAIR: zk_pss_repair -- the scan in place of stage 1, the repair form of stage 2, `shares` written
+template <class FrP, bool REPAIR>
+int gao_all_parties_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPAIR, void*, const void*> shares, size_t nchunks,
+                        int dimension, void* secrets, void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                        hipStream_t st) {
   using Fr = Fp<FrP>;
   const int n = 4 * l;
   if (dimension < 1 || dimension > n - 1) return e->fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
@@ -265,10 +293,17 @@ int gao_unpack_robust_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, 
   const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
   const size_t per_wg = GAO_THREADS / gao_split(l);                  // chunks per workgroup of stage 1
   const dim3 blk(GAO_THREADS), grid1((unsigned)((nchunks + per_wg - 1) / per_wg));
-  const Fr* sh = (const Fr*)shares;
+  std::conditional_t<REPAIR, Fr*, const Fr*> sh = (decltype(sh))shares;
   Fr* sec = (Fr*)secrets;
   Fr* msg = (Fr*)message;
-  switch (l) {
+  if constexpr (REPAIR) switch (l) {
+    case 1: gao_scan_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
+    case 2: gao_scan_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
+    case 4: gao_scan_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
+    case 8: gao_scan_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
+    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
+  }
+  else switch (l) {
     case 1: gao_stage1_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, sec, msg, status, errpos, wk); break;
     case 2: gao_stage1_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, sec, msg, status, errpos, wk); break;
     case 4: gao_stage1_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, sec, msg, status, errpos, wk); break;
@@ -277,9 +312,20 @@ int gao_unpack_robust_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, 
   }
   const size_t gpb = GAO_THREADS / n;
   const dim3 grid2((unsigned)std::min<size_t>((nchunks + gpb - 1) / gpb, GAO_STAGE2_GRID));
-  gao_stage2_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, nchunks, dimension, sec, msg, status, errpos, wk);
+  if constexpr (REPAIR) gao_repair_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, nchunks, dimension, status, errpos, wk);
+  else gao_stage2_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, nchunks, dimension, sec, msg, status, errpos, wk);
   GAO_HIP(hipGetLastError());
   return ZK_OK;
+}
+template <class FrP>
+int gao_unpack_robust_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, size_t nchunks, int dimension, void* secrets,
+                          void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+  return gao_all_parties_run<FrP, false>(e, wkbuf, l, shares, nchunks, dimension, secrets, message, status, errpos, summary, st);
+}
+template <class FrP>
+int gao_repair_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, size_t nchunks, int dimension, uint8_t* status,
+                   uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+  return gao_all_parties_run<FrP, true>(e, wkbuf, l, shares, nchunks, dimension, nullptr, nullptr, status, errpos, summary, st);
 }
 // With all n parties listed this is the call above; otherwise the kernels' forms for absent parties, with the table of the
 // party list (gao_make_absent, host) put into working memory by a launch of its own ahead of them.
