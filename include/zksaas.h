@@ -438,6 +438,66 @@ int zk_d_ifft_checked(zk_ctx* ctx, void* shares_d, const void* in_mask_d, const 
  * same input.  status_d is [len]. */
 int zk_deg_red_checked(zk_ctx* ctx, void* x_d, const void* in_mask_d, const void* out_mask_d, size_t len, uint64_t seed,
                        uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
+/* zk_pss_repair_parties: zk_pss_repair for the shares of a party list S -- the verdicts of zk_pss_unpack_robust_parties,
+ * written back into the shares.  secret-sharing/src/gao.rs:11-84 over the points of S, the party list of
+ * unpack_missing_shares, secret-sharing/src/pss.rs:141-221.  shares_d is [nparties][nchunks], row i the shares of party
+ * parties[i]; parties (HOST) holds ascending ids below n, NULL stands for 0 .. nparties - 1.
+ * status_d, errpos_d (by party id), summary_d [3 + n] and every error return are exactly zk_pss_unpack_robust_parties' on
+ * the same input: ZK_ERR_PROTOCOL for nparties <= dimension included, and a status 1 that names an absent party is status 2.
+ * WRITTEN: in a status-1 chunk, the element in row i of every listed party parties[i] named in the final errpos becomes
+ * h(w_n^parties[i]).  NOT WRITTEN: clean chunks, failed chunks, the right shares of a corrected chunk; an absent party has
+ * no row, and its share is not recovered.  A second call on the result reports the former status-1 chunks clean.  With
+ * nparties == n the outputs and the bytes written are zk_pss_repair's.  A party named in errpos once can be left out of the
+ * list afterwards: its chunks are clean again and none reaches the decoder.
+ * No host synchronisation, working memory from the stream's workspace.  Device engine only. */
+int zk_pss_repair_parties(zk_ctx* ctx, void* shares_d /* [nparties][nchunks], in place */,
+                          const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */, int nparties,
+                          size_t nchunks, int dimension, uint8_t* status_d /* [nchunks] */,
+                          uint32_t* errpos_d /* [nchunks], or NULL */, uint64_t* summary_d /* [3 + n], or NULL */,
+                          void* stream);
+/* Checked king rounds with a party list: the calls above for the case that only the listed parties' shares reached the king
+ * (dist-primitives/src/dfft/mod.rs:264-304 with the list of unpack_missing_shares, pss.rs:141-221) -- a dropout, or a party
+ * left out because an earlier report named it.  Each runs zk_pss_repair_parties at dimension 2l on the word the king
+ * receives and then the unchecked king with the same list.  The refusals are zk_pss_repair_parties': a bad list is
+ * ZK_ERR_BAD_INPUT, nparties <= 2l is ZK_ERR_PROTOCOL -- and the unchecked king's, whose unpack_missing_shares takes a list
+ * only with more than 4l - 2 shares (pss.rs:183-186): nparties < 4l - 1 is ZK_ERR_PROTOCOL as it is for zk_fft2_king, so
+ * a list is all n parties or n - 1 of them.  Every refusal is made before anything is written.
+ * cap = (nparties - 2l) / 2 wrong shares per chunk are corrected and
+ * named by party id; a failed chunk is not an error return.  With nparties == n the outputs are the all-parties checked
+ * call's.  deg_red has no such form: at dimension 4l - 1 a list of n - 1 parties has no redundancy left, nothing could even
+ * be detected.
+ *
+ * zk_fft2_king_checked_parties: in_d is [nparties][m/l], row i the shares of parties[i], REPAIRED IN PLACE; out_d is
+ * [n][m/l].  in_d == out_d -> ZK_ERR_BAD_INPUT.  status_d is [m/l]. */
+int zk_fft2_king_checked_parties(zk_ctx* ctx, void* in_d, const uint32_t* parties, int nparties, int log2_m, int inverse,
+                                 const void* g, int scale_size_inv, int rearrange, uint64_t seed, void* out_d,
+                                 const void* out_mask_d, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d,
+                                 void* stream);
+/* zk_d_fft_checked_parties / zk_d_ifft_checked_parties: zk_d_fft_checked / zk_d_ifft_checked when only the listed parties'
+ * words reach the king (dfft/mod.rs:159, :254-258, the king :264-304).  shares_d, in_mask_d and the outputs are [n][m/l] as
+ * before; only the rows of the listed parties are read: fft1 of row parties[i], (for the inverse: times 1 / m,) plus the
+ * in-mask row of parties[i] is row i of the king's word, which is repaired and handed to the king with the list.  The rows
+ * of absent parties in shares_d and in_mask_d are never read; shares_d is left untouched when out_d is given.  status_d is
+ * [m/l]. */
+int zk_d_fft_checked_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, const void* in_mask_d,
+                             const void* out_mask_d, int rearrange, int log2_m, uint64_t seed, void* out_d,
+                             uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
+int zk_d_ifft_checked_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, const void* in_mask_d,
+                              const void* out_mask_d, int rearrange, int log2_m, const void* g, uint64_t seed, void* out_d,
+                              uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
+/* zk_d_pp_checked: zk_d_pp with the king's word checked.  The king of dist-primitives/src/dpp/mod.rs:37-52 receives
+ * num ++ den per party and unpacks it with unpack_missing_shares: packed shares of degree < 2l, so the dimension is 2l and
+ * up to (nparties - 2l) / 2 wrong shares per chunk are corrected.  num_d and den_d are [nparties][len] each, row i the shares
+ * of parties[i] (NULL list: 0 .. nparties - 1), and are REPAIRED IN PLACE by two zk_pss_repair_parties calls; then the
+ * unchecked king runs with the list.  Chunk c of the reference's word is num's chunk c for c < len and den's chunk c - len
+ * above: status_d and errpos_d are [2 len] in that order, summary_d is [2][3 + n], num's then den's.  in_mask_d, out_mask_d
+ * and out_d are [n][len] as in zk_d_pp.  The zero-denominator ZK_ERR_GENERIC is unchanged, and a den chunk that failed
+ * (status 2: its shares go to the king as received) may cause it.  NOT CHECKED: the deg_red that ends d_pp (mod.rs:86) --
+ * the king produced that word itself, and its cap is 0.  The refusals are those of the checked kings with a list above
+ * (zk_d_pp's king reads its list the same way); len == 0 is ZK_OK. */
+int zk_d_pp_checked(zk_ctx* ctx, void* num_d, void* den_d, const uint32_t* parties, int nparties, const void* in_mask_d,
+                    const void* out_mask_d, size_t len, uint64_t seed, void* out_d, uint8_t* status_d, uint32_t* errpos_d,
+                    uint64_t* summary_d, void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

@@ -294,6 +294,141 @@ pub fn deg_red_checked_vec<F: PrimeField + 'static>(ctx: &Context, x_shares: &[V
     Ok((rows(&x, ctx.n, len)?, v.read(ctx)?))
 }
 
+/// `zk_pss_repair_parties`: [`repair_vec`] for the share vectors of the listed parties only (ascending ids, the list of
+/// `unpack_missing_shares`, `secret-sharing/src/pss.rs:141-221`).  The verdicts are [`unpack_robust_parties_vec`]'s; in a
+/// corrected chunk the share of every listed party named in `errpos` -- by party id -- is replaced in that party's row.
+/// An absent party has no row and its share is not recovered.  `parties.len() <= dimension` is `MpcNetError::Protocol`.
+pub fn repair_parties_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], parties: &[u32], dimension: usize)
+                                                   -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, parties.len())?;
+    let sh = DeviceBuf::from_slice(ctx, &flat)?;
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    check(ctx, unsafe {
+        sys::zk_pss_repair_parties(ctx.raw(), sh.ptr(), parties.as_ptr(), parties.len() as i32, nchunks, dimension as i32,
+                                   v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64, ptr::null_mut())
+    })?;
+    Ok((rows(&sh, parties.len(), nchunks)?, v.read(ctx)?))
+}
+
+/// [`fft2_king_checked_vec`] when only the listed parties' vectors reached the king (`zk_fft2_king_checked_parties`):
+/// `shares` holds one vector per listed party; up to `(parties.len() - 2l) / 2` wrong shares per chunk are corrected.
+/// Returns the `n` parties' output shares, the repaired input rows and the verdicts per input chunk.
+#[allow(clippy::too_many_arguments)]
+pub fn fft2_king_checked_parties_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], parties: &[u32], log2_m: u32,
+                                                              inverse: bool, g: F, scale_size_inv: bool, rearrange: bool,
+                                                              out_mask: Option<&[F]>)
+                                                              -> Result<(Vec<Vec<F>>, Vec<Vec<F>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, parties.len())?;
+    let sh = DeviceBuf::from_slice(ctx, &flat)?;
+    let out = DeviceBuf::alloc(ctx, ctx.n * nchunks * core::mem::size_of::<F>())?;
+    let om = match out_mask { Some(m) => Some(DeviceBuf::from_slice(ctx, m)?), None => None };
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    let gl = [g];
+    check(ctx, unsafe {
+        sys::zk_fft2_king_checked_parties(ctx.raw(), sh.ptr(), parties.as_ptr(), parties.len() as i32, log2_m as i32,
+                                          inverse as i32, fr_ptr(&gl), scale_size_inv as i32, rearrange as i32, 0, out.ptr(),
+                                          om.as_ref().map_or(ptr::null(), |b| b.ptr() as *const core::ffi::c_void),
+                                          v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64,
+                                          ptr::null_mut())
+    })?;
+    Ok((rows(&out, ctx.n, nchunks)?, rows(&sh, parties.len(), nchunks)?, v.read(ctx)?))
+}
+
+/// [`d_fft_checked_vec`] when only the listed parties' words reach the king (`zk_d_fft_checked_parties`).  `shares` and
+/// the masks stay `[n][m/l]`; the rows of absent parties are never read.  A party named in an earlier report can be left
+/// out of the list: its chunks are clean again and none reaches the decoder.
+pub fn d_fft_checked_parties_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], parties: &[u32],
+                                                          in_mask: Option<&[F]>, out_mask: Option<&[F]>, rearrange: bool,
+                                                          log2_m: u32) -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    transform_checked_parties(ctx, shares, parties, in_mask, out_mask, rearrange, log2_m, None)
+}
+
+/// `d_ifft` in the same way (`zk_d_ifft_checked_parties`).
+#[allow(clippy::too_many_arguments)]
+pub fn d_ifft_checked_parties_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], parties: &[u32],
+                                                           in_mask: Option<&[F]>, out_mask: Option<&[F]>, rearrange: bool,
+                                                           log2_m: u32, g: F) -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    transform_checked_parties(ctx, shares, parties, in_mask, out_mask, rearrange, log2_m, Some(g))
+}
+
+#[allow(clippy::too_many_arguments)]
+fn transform_checked_parties<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<F>], parties: &[u32], in_mask: Option<&[F]>,
+                                                      out_mask: Option<&[F]>, rearrange: bool, log2_m: u32, g: Option<F>)
+                                                      -> Result<(Vec<Vec<F>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten(ctx, shares, ctx.n)?;
+    let sh = DeviceBuf::from_slice(ctx, &flat)?;
+    let up = |m: Option<&[F]>| -> Result<Option<DeviceBuf>, MpcNetError> {
+        match m {
+            Some(m) if m.len() != flat.len() => Err(MpcNetError::BadInput { err: "FftMask length differs from the share vectors" }),
+            Some(m) => Ok(Some(DeviceBuf::from_slice(ctx, m)?)),
+            None => Ok(None),
+        }
+    };
+    let (im, om) = (up(in_mask)?, up(out_mask)?);
+    let p = |b: &Option<DeviceBuf>| b.as_ref().map_or(ptr::null(), |b| b.ptr() as *const core::ffi::c_void);
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    check(ctx, unsafe {
+        match g {
+            None => sys::zk_d_fft_checked_parties(ctx.raw(), sh.ptr(), parties.as_ptr(), parties.len() as i32, p(&im), p(&om),
+                                                  rearrange as i32, log2_m as i32, 0, ptr::null_mut(), v.st.ptr() as *mut u8,
+                                                  v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64, ptr::null_mut()),
+            Some(g) => {
+                let gl = [g];
+                sys::zk_d_ifft_checked_parties(ctx.raw(), sh.ptr(), parties.as_ptr(), parties.len() as i32, p(&im), p(&om),
+                                               rearrange as i32, log2_m as i32, fr_ptr(&gl), 0, ptr::null_mut(),
+                                               v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64,
+                                               ptr::null_mut())
+            }
+        }
+    })?;
+    Ok((rows(&sh, ctx.n, nchunks)?, v.read(ctx)?))
+}
+
+/// `d_pp` (`dist-primitives/src/dpp/mod.rs:15-87`) with the king's word `num ++ den` (`:37-52`) repaired first
+/// (`zk_d_pp_checked`): packed shares of degree below `2l`, so up to `(parties.len() - 2l) / 2` wrong shares per chunk are
+/// corrected in each half.  `num` and `den` hold one vector per listed party (`None`: all `n`).  Returns the `n` parties'
+/// output shares and the verdicts of `num`'s and of `den`'s chunks.  The `deg_red` that ends `d_pp` is not checked.
+#[allow(clippy::type_complexity)]
+pub fn d_pp_checked_vec<F: PrimeField + 'static>(ctx: &Context, num: &[Vec<F>], den: &[Vec<F>], parties: Option<&[u32]>,
+                                                 in_mask: Option<&[F]>, out_mask: Option<&[F]>)
+                                                 -> Result<(Vec<Vec<F>>, Verdicts, Verdicts), MpcNetError> {
+    let np = parties.map_or(ctx.n, |p| p.len());
+    let (nflat, len) = flatten(ctx, num, np)?;
+    let (dflat, dlen) = flatten(ctx, den, np)?;
+    if dlen != len {
+        return Err(MpcNetError::BadInput { err: "d_pp: num and den differ in length" });
+    }
+    let (nd, dd) = (DeviceBuf::from_slice(ctx, &nflat)?, DeviceBuf::from_slice(ctx, &dflat)?);
+    let up = |m: Option<&[F]>| -> Result<Option<DeviceBuf>, MpcNetError> {
+        match m {
+            Some(m) if m.len() != ctx.n * len => Err(MpcNetError::BadInput { err: "DegRedMask length differs from the share vectors" }),
+            Some(m) => Ok(Some(DeviceBuf::from_slice(ctx, m)?)),
+            None => Ok(None),
+        }
+    };
+    let (im, om) = (up(in_mask)?, up(out_mask)?);
+    let p = |b: &Option<DeviceBuf>| b.as_ref().map_or(ptr::null(), |b| b.ptr() as *const core::ffi::c_void);
+    let out = DeviceBuf::alloc(ctx, ctx.n * len * core::mem::size_of::<F>())?;
+    let w = 3 + ctx.n;
+    let (st, ep, sm) = (DeviceBuf::alloc(ctx, 2 * len)?, DeviceBuf::alloc(ctx, 2 * len * 4)?, DeviceBuf::alloc(ctx, 2 * w * 8)?);
+    check(ctx, unsafe {
+        sys::zk_d_pp_checked(ctx.raw(), nd.ptr(), dd.ptr(), parties.map_or(ptr::null(), |p| p.as_ptr()), np as i32, p(&im),
+                             p(&om), len, 0, out.ptr(), st.ptr() as *mut u8, ep.ptr() as *mut u32, sm.ptr() as *mut u64,
+                             ptr::null_mut())
+    })?;
+    let status: Vec<u8> = st.to_vec(2 * len)?;
+    let errpos: Vec<u32> = ep.to_vec(2 * len)?;
+    let summary: Vec<u64> = if len == 0 { vec![0; 2 * w] } else { sm.to_vec(2 * w)? };
+    let half = |i: usize| Verdicts {
+        verdicts: status[i * len..(i + 1) * len].iter()
+            .map(|s| match s { 0 => Verdict::Clean, 1 => Verdict::Corrected, _ => Verdict::Failed }).collect(),
+        errpos: errpos[i * len..(i + 1) * len].to_vec(),
+        counts: [summary[i * w], summary[i * w + 1], summary[i * w + 2]],
+        corrected_per_party: summary[i * w + 3..(i + 1) * w].to_vec(),
+    };
+    Ok((rows(&out, ctx.n, len)?, half(0), half(1)))
+}
+
 fn flatten<F: PrimeField>(_ctx: &Context, shares: &[Vec<F>], want: usize) -> Result<(Vec<F>, usize), MpcNetError> {
     if shares.len() != want || shares.is_empty() {
         return Err(MpcNetError::BadInput { err: "unpack: one share vector per listed party expected" });

@@ -33,6 +33,8 @@ SYMBOLS = [
     "zk_points_subgroup_check", "zk_points_decompress_checked", "zk_groth16_verify_bytes", "zk_groth16_verify_all_bytes",
     "zk_pss_unpack_robust", "zk_pss_unpack_robust_parties",
     "zk_pss_repair", "zk_fft2_king_checked", "zk_d_fft_checked", "zk_d_ifft_checked", "zk_deg_red_checked",
+    "zk_pss_repair_parties", "zk_fft2_king_checked_parties", "zk_d_fft_checked_parties", "zk_d_ifft_checked_parties",
+    "zk_d_pp_checked",
 ]
 
 _lib = None
@@ -225,6 +227,12 @@ def load():
     lib.zk_d_fft_checked.argtypes = [vp, vp, vp, vp, i32, i32, u64, vp, vp, vp, vp, vp]
     lib.zk_d_ifft_checked.argtypes = [vp, vp, vp, vp, i32, i32, vp, u64, vp, vp, vp, vp, vp]
     lib.zk_deg_red_checked.argtypes = [vp, vp, vp, vp, sz, u64, vp, vp, vp, vp]
+    ids = C.POINTER(C.c_uint32)
+    lib.zk_pss_repair_parties.argtypes = [vp, vp, ids, i32, sz, i32, vp, vp, vp, vp]
+    lib.zk_fft2_king_checked_parties.argtypes = [vp, vp, ids, i32, i32, i32, vp, i32, i32, u64, vp, vp, vp, vp, vp, vp]
+    lib.zk_d_fft_checked_parties.argtypes = [vp, vp, ids, i32, vp, vp, i32, i32, u64, vp, vp, vp, vp, vp]
+    lib.zk_d_ifft_checked_parties.argtypes = [vp, vp, ids, i32, vp, vp, i32, i32, vp, u64, vp, vp, vp, vp, vp]
+    lib.zk_d_pp_checked.argtypes = [vp, vp, vp, ids, i32, vp, vp, sz, u64, vp, vp, vp, vp, vp]
     lib.zk_points_subgroup_check.argtypes = [vp, i32, vp, sz, vp, vp]
     lib.zk_points_decompress_checked.argtypes = [vp, i32, vp, sz, vp, vp, vp]
     lib.zk_groth16_verify_bytes.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]

@@ -198,23 +198,31 @@ class PackedSharingParams(Context):
                                                               _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
-    def _report(self, nchunks, dimension):
-        """the verdict buffers of a repair or of a checked king round: a RobustUnpack without secrets and message"""
-        r = RobustUnpack(self, nchunks, dimension)
+    def _report(self, nchunks, dimension, parties=None, words=1):
+        """the verdict buffers of a repair or of a checked king round: a RobustUnpack without secrets and message.  words:
+        the number of words checked (d_pp: 2) -- nchunks counts all their chunks, summary_d holds one summary per word"""
+        r = RobustUnpack(self, nchunks, dimension, None if parties is None else list(parties))
         r.status = DeviceBuffer(self, nchunks)
         r.errpos = DeviceBuffer(self, 4 * nchunks)
-        r.summary_d = DeviceBuffer(self, 8 * (3 + self.n))
+        r.summary_d = DeviceBuffer(self, 8 * (3 + self.n) * words)
         return r
 
-    def repair(self, shares_d, nchunks, dimension=None, stream=None):
+    def repair(self, shares_d, nchunks, dimension=None, stream=None, parties=None):
         """zk_pss_repair: unpack_robust's verdicts written back into shares_d [n][nchunks], in place: in a corrected chunk the
         share of every party named in errpos becomes the decoded polynomial's value, every other element keeps its bytes.
+        With `parties` (ascending ids) shares_d is [len(parties)][nchunks], the other parties are absent and the call is
+        zk_pss_repair_parties: the verdicts are unpack_robust's with that list, a named party's share is written at its row.
         Returns a RobustUnpack with status, errpos and summary (no secrets, no message); `out` is shares_d."""
         k = 2 * self.l if dimension is None else int(dimension)
-        r = self._report(nchunks, k)
+        r = self._report(nchunks, k, parties)
         r.out = shares_d
-        self._check(self.lib.zk_pss_repair(self.h, _ptr(shares_d), nchunks, k, _ptr(r.status), _ptr(r.errpos),
-                                           _ptr(r.summary_d), stream))
+        if parties is None:
+            self._check(self.lib.zk_pss_repair(self.h, _ptr(shares_d), nchunks, k, _ptr(r.status), _ptr(r.errpos),
+                                               _ptr(r.summary_d), stream))
+        else:
+            arr = (C.c_uint32 * len(r.parties))(*r.parties)
+            self._check(self.lib.zk_pss_repair_parties(self.h, _ptr(shares_d), arr, len(r.parties), nchunks, k, _ptr(r.status),
+                                                       _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
     def lagrange_unpack(self, shares_d, nchunks, parties, out=None, stream=None):
@@ -229,7 +237,9 @@ class RobustUnpack:
     that holds the call's result.  Device buffers: secrets [nchunks * l] (order 0), status [nchunks] bytes
     (0 clean, 1 corrected, 2 failed), errpos [nchunks] u32 (bit p: party p's share was corrected), summary_d [3 + n] u64,
     message [dimension][nchunks] or None.  `summary` downloads summary_d: [clean, corrected, failed] + per party the number
-    of chunks in which its share was corrected.  `parties`: the party list the call was given, None for all n."""
+    of chunks in which its share was corrected.  `parties`: the party list the call was given, None for all n.
+    d_pp with check=True checks two words, num then den: status and errpos are [2 * length] in that order, summary_d is
+    [2][3 + n], `summary` is num's and `summaries` holds both."""
     CLEAN, CORRECTED, FAILED = 0, 1, 2
 
     def __init__(self, ctx, nchunks, dimension, parties=None):
@@ -240,7 +250,16 @@ class RobustUnpack:
     def summary(self):
         if not self.nchunks:            # the call writes nothing for an empty vector
             return [0] * (3 + self.ctx.n)
-        return [int(v) for v in self.summary_d.to_numpy(np.uint64)]
+        return [int(v) for v in self.summary_d.to_numpy(np.uint64)[:3 + self.ctx.n]]
+
+    @property
+    def summaries(self):
+        """one summary per word the call checked"""
+        w = 3 + self.ctx.n
+        if not self.nchunks:
+            return [[0] * w for _ in range(self.summary_d.nbytes // (8 * w))]
+        flat = [int(v) for v in self.summary_d.to_numpy(np.uint64)]
+        return [flat[i:i + w] for i in range(0, len(flat) - w + 1, w)]
 
     def status_host(self):
         return self.status.to_numpy(np.uint8) if self.nchunks else np.zeros(0, np.uint8)
@@ -358,10 +377,38 @@ def fft2_king(pp, in_d, log2_m, inverse=False, g=None, scale_size_inv=False, rea
     return r
 
 
-def d_fft(pp, shares_d, fft_mask, rearrange, log2_m, seed=0, out=None, stream=None, check=False):
+def fft2_king_checked_parties(pp, in_d, parties, log2_m, inverse=False, g=None, scale_size_inv=False, rearrange=False, seed=0,
+                              out=None, out_mask=None, stream=None):
+    """zk_fft2_king_checked_parties: in_d [len(parties)][m/l], the words of the listed parties (ascending ids; None: all n),
+    is repaired in place with the list (dimension 2l, up to (len(parties) - 2l) // 2 wrong shares per chunk), then the king
+    runs with the same list; never in place.  Returns the report, a RobustUnpack whose `out` is the output buffer [n][m/l]."""
+    out = out or pp.alloc_fr(pp.n * ((1 << log2_m) // pp.l))
+    garr = None if g is None else pp.fr.encode_one(g)
+    gp = None if garr is None else garr.ctypes.data
+    arr, np_ = (None, pp.n) if parties is None else ((C.c_uint32 * len(parties))(*parties), len(parties))
+    r = pp._report((1 << log2_m) // pp.l, 2 * pp.l, parties)
+    r.out = out
+    pp._check(pp.lib.zk_fft2_king_checked_parties(pp.h, _ptr(in_d), arr, np_, log2_m, int(inverse), gp, int(scale_size_inv),
+                                                  int(rearrange), seed, _ptr(out), _ptr(out_mask), _ptr(r.status),
+                                                  _ptr(r.errpos), _ptr(r.summary_d), stream))
+    return r
+
+
+def d_fft(pp, shares_d, fft_mask, rearrange, log2_m, seed=0, out=None, stream=None, check=False, parties=None):
     """dfft/mod.rs:99-134 for all parties; shares_d [n][m/l].  Result in `out` (or back in shares_d if None).
     check=True: zk_d_fft_checked -- the word the king receives is repaired first (up to l wrong parties per chunk); returns
-    the report, a RobustUnpack whose `out` is the buffer with the result."""
+    the report, a RobustUnpack whose `out` is the buffer with the result.  With `parties` (ascending ids; check=True only)
+    the call is zk_d_fft_checked_parties: only the listed rows of shares_d and of the in-mask reach the king."""
+    if parties is not None and not check:
+        raise ValueError("a party list is the checked call's: pass check=True")
+    if check and parties is not None:
+        r = pp._report((1 << log2_m) // pp.l, 2 * pp.l, parties)
+        r.out = shares_d if out is None else out
+        arr = (C.c_uint32 * len(r.parties))(*r.parties)
+        pp._check(pp.lib.zk_d_fft_checked_parties(pp.h, _ptr(shares_d), arr, len(r.parties), _ptr(fft_mask.in_mask),
+                                                  _ptr(fft_mask.out_mask), int(rearrange), log2_m, seed, _ptr(out),
+                                                  _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
     if check:
         r = pp._report((1 << log2_m) // pp.l, 2 * pp.l)
         r.out = shares_d if out is None else out
@@ -373,9 +420,21 @@ def d_fft(pp, shares_d, fft_mask, rearrange, log2_m, seed=0, out=None, stream=No
     return shares_d if out is None else out
 
 
-def d_ifft(pp, shares_d, fft_mask, rearrange, log2_m, g=None, seed=0, out=None, stream=None, check=False):
-    """dfft/mod.rs:137-175; g is an int (coset shift, 1 if None).  check=True: zk_d_ifft_checked, as d_fft's."""
+def d_ifft(pp, shares_d, fft_mask, rearrange, log2_m, g=None, seed=0, out=None, stream=None, check=False, parties=None):
+    """dfft/mod.rs:137-175; g is an int (coset shift, 1 if None).  check=True: zk_d_ifft_checked, as d_fft's; with `parties`
+    zk_d_ifft_checked_parties."""
     garr = None if g is None else pp.fr.encode_one(g)
+    if parties is not None and not check:
+        raise ValueError("a party list is the checked call's: pass check=True")
+    if check and parties is not None:
+        r = pp._report((1 << log2_m) // pp.l, 2 * pp.l, parties)
+        r.out = shares_d if out is None else out
+        arr = (C.c_uint32 * len(r.parties))(*r.parties)
+        pp._check(pp.lib.zk_d_ifft_checked_parties(pp.h, _ptr(shares_d), arr, len(r.parties), _ptr(fft_mask.in_mask),
+                                                   _ptr(fft_mask.out_mask), int(rearrange), log2_m,
+                                                   None if garr is None else garr.ctypes.data, seed, _ptr(out),
+                                                   _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
     if check:
         r = pp._report((1 << log2_m) // pp.l, 2 * pp.l)
         r.out = shares_d if out is None else out
@@ -401,9 +460,21 @@ def deg_red(pp, x_d, mask, length, seed=0, stream=None, check=False):
     return x_d
 
 
-def d_pp(pp, num_d, den_d, mask, length, seed=0, out=None, stream=None):
-    """dpp/mod.rs:15-87; num_d, den_d [n][length]."""
+def d_pp(pp, num_d, den_d, mask, length, seed=0, out=None, stream=None, check=False, parties=None):
+    """dpp/mod.rs:15-87; num_d, den_d [n][length].  check=True: zk_d_pp_checked -- the king's word num ++ den is repaired
+    first, num_d and den_d IN PLACE (dimension 2l); with `parties` (ascending ids) they are [len(parties)][length], the
+    words of the listed parties.  Returns the report, a RobustUnpack over 2 * length chunks (num's, then den's) whose
+    `summaries` are num's and den's and whose `out` is the result [n][length]."""
     out = out or pp.alloc_fr(pp.n * length)
+    if parties is not None and not check:
+        raise ValueError("a party list is the checked call's: pass check=True")
+    if check:
+        r = pp._report(2 * length, 2 * pp.l, parties, words=2)
+        r.out = out
+        arr, np_ = (None, pp.n) if parties is None else ((C.c_uint32 * len(r.parties))(*r.parties), len(r.parties))
+        pp._check(pp.lib.zk_d_pp_checked(pp.h, _ptr(num_d), _ptr(den_d), arr, np_, _ptr(mask.in_mask), _ptr(mask.out_mask),
+                                         length, seed, _ptr(out), _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
     pp._check(pp.lib.zk_d_pp(pp.h, _ptr(num_d), _ptr(den_d), _ptr(mask.in_mask), _ptr(mask.out_mask), length, seed,
                              _ptr(out), stream))
     return out

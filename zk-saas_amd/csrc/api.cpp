@@ -856,6 +856,42 @@ int zk_deg_red_checked(zk_ctx* ctx, void* x_d, const void* in_mask_d, const void
   CTX_OR_FAIL();
   return e->deg_red_checked(x_d, in_mask_d, out_mask_d, len, seed, status_d, errpos_d, summary_d, S(stream));
 }
+int zk_pss_repair_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, size_t nchunks, int dimension,
+                          uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_repair_parties(shares_d, parties, nparties, nchunks, dimension, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_fft2_king_checked_parties(zk_ctx* ctx, void* in_d, const uint32_t* parties, int nparties, int log2_m, int inverse,
+                                 const void* g, int scale_size_inv, int rearrange, uint64_t seed, void* out_d,
+                                 const void* out_mask_d, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d,
+                                 void* stream) {
+  CTX_OR_FAIL();
+  if (in_d == out_d)
+    return e->fail(ZK_ERR_BAD_INPUT, "zk_fft2_king_checked_parties cannot run in place (workgroups exchange chunks)");
+  return e->fft2_king_checked_parties(in_d, parties, nparties, log2_m, inverse, g, scale_size_inv, rearrange, seed, out_d,
+                                      out_mask_d, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_d_fft_checked_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, const void* in_mask_d,
+                             const void* out_mask_d, int rearrange, int log2_m, uint64_t seed, void* out_d,
+                             uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->d_fft_checked_parties(shares_d, parties, nparties, in_mask_d, out_mask_d, rearrange, log2_m, 0, nullptr, seed,
+                                  out_d, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_d_ifft_checked_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, const void* in_mask_d,
+                              const void* out_mask_d, int rearrange, int log2_m, const void* g, uint64_t seed, void* out_d,
+                              uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->d_fft_checked_parties(shares_d, parties, nparties, in_mask_d, out_mask_d, rearrange, log2_m, 1, g, seed, out_d,
+                                  status_d, errpos_d, summary_d, S(stream));
+}
+int zk_d_pp_checked(zk_ctx* ctx, void* num_d, void* den_d, const uint32_t* parties, int nparties, const void* in_mask_d,
+                    const void* out_mask_d, size_t len, uint64_t seed, void* out_d, uint8_t* status_d, uint32_t* errpos_d,
+                    uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->d_pp_checked(num_d, den_d, parties, nparties, in_mask_d, out_mask_d, len, seed, out_d, status_d, errpos_d,
+                         summary_d, S(stream));
+}
 int zk_circom_h(zk_ctx* ctx, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
                 const zk_groth16_masks* masks, uint64_t seed, void* h_d, void* stream) {
   CTX_OR_FAIL();

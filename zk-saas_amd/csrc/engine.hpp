@@ -409,6 +409,19 @@ class IEngine {
                             hipStream_t st) = 0;
   virtual int deg_red_checked(void* x, const void* in_mask, const void* out_mask, size_t len, uint64_t seed, uint8_t* status,
                               uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  // zk_pss_repair_parties: the verdicts of pss_unpack_robust_parties, written back into the shares [nparties][nchunks]
+  virtual int pss_repair_parties(void* shares, const uint32_t* parties, int nparties, size_t nchunks, int dimension,
+                                 uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  // the king rounds with the word of a party list repaired first (engine_gao.inc.hpp)
+  virtual int fft2_king_checked_parties(void* in, const uint32_t* parties, int np, int log_m, int inverse, const void* g,
+                                        int scale_size_inv, int rearrange, uint64_t seed, void* out, const void* out_mask,
+                                        uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  virtual int d_fft_checked_parties(void* shares, const uint32_t* parties, int np, const void* in_mask, const void* out_mask,
+                                    int rearrange, int log_m, int inverse, const void* g, uint64_t seed, void* out,
+                                    uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  virtual int d_pp_checked(void* num, void* den, const uint32_t* parties, int np, const void* in_mask, const void* out_mask,
+                           size_t len, uint64_t seed, void* out, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                           hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,

@@ -1,5 +1,5 @@
 // Part of class Engine<Cfg> (engine_impl.hpp includes this file INSIDE the class body): zk_pss_unpack_robust and
-// zk_pss_unpack_robust_parties, the error-correcting unpack; zk_pss_repair and the checked king rounds built on it.  Kernels and driver: gao_impl.hpp, compiled in gao_<curve>.hip.  Not a stand-alone header.
+// zk_pss_unpack_robust_parties, the error-correcting unpack; zk_pss_repair, zk_pss_repair_parties and the checked king rounds built on them.  Kernels and driver: gao_impl.hpp, compiled in gao_<curve>.hip.  Not a stand-alone header.
 
   // ---------------------------------------------------------------- zk_pss_unpack_robust
   // shares [n][nchunks] of all n parties; any of secrets, message, errpos, summary may be null.  Working memory is the caller
@@ -85,4 +85,97 @@
     if (in_mask && (rc = vec_add(x, in_mask, (size_t)n * len, st))) return rc;
     if ((rc = pss_repair(x, len, 4 * l - 1, status, errpos, summary, st))) return rc;
     return deg_red_np((const Fr*)x, nullptr, nullptr, n, len, seed, (Fr*)x, (const Fr*)out_mask, st);
+  }
+
+  // ---------------------------------------------------------------- zk_pss_repair_parties
+  // shares [nparties][nchunks] of the listed parties, in place: status, errpos and summary are pss_unpack_robust_parties'; in a
+  // corrected chunk the element in the row of every listed party named in errpos becomes h(w_n^p), every other element keeps
+  // its bytes.  With nparties == n this is pss_repair.
+  int pss_repair_parties(void* shares, const uint32_t* parties, int nparties, size_t nchunks, int dimension, uint8_t* status,
+                         uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    return gao_repair_parties_run<FrP>(this, ws(st)->hwork, l, shares, parties, nparties, nchunks, dimension, status, errpos,
+                                       summary, st);
+  }
+
+  // ---------------------------------------------------------------- checked king rounds with a party list
+  // Only the listed parties' words reached the king: repair with the list at dimension 2l, cap = (np - 2l) / 2, then the
+  // unchecked king with the same list (umat_for).  The refusals are pss_repair_parties' and the unchecked king's (checked_list).
+  // deg_red has no such form: at dimension 4l - 1 a list of n - 1 parties has no redundancy left.
+  int fft2_king_checked_parties(void* in, const uint32_t* parties, int np, int log_m, int inverse, const void* g,
+                                int scale_size_inv, int rearrange, uint64_t seed, void* out, const void* out_mask,
+                                uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    if (!in || !out) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (log_m < ilog2(l)) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    uint32_t ids[GAO_MAX_N];
+    int rc = checked_list(parties, np, 2 * l, ids);
+    if (rc) return rc;
+    if ((rc = pss_repair_parties(in, ids, np, ((size_t)1 << log_m) / l, 2 * l, status, errpos, summary, st))) return rc;
+    return fft2_king(in, nullptr, ids, np, log_m, inverse, g, scale_size_inv, rearrange, seed, out, out_mask, st);
+  }
+  // the list as pss_repair_parties reads it, refused as it refuses it, and as the king's umat_for refuses it: the reference's
+  // unpack_missing_shares takes a list only with more than 2 (t + l - 1) = 4l - 2 shares (pss.rs:183-186), so a list is all n
+  // parties or n - 1 of them.  Asked before anything is written: a refusal leaves the caller's buffers as they were.
+  int checked_list(const uint32_t* parties, int np, int dimension, uint32_t* ids) {
+    if (np <= 0 || np > n) return fail(ZK_ERR_BAD_INPUT, "bad party count");
+    for (int i = 0; i < np; i++) {
+      ids[i] = parties ? parties[i] : (uint32_t)i;
+      if (ids[i] >= (uint32_t)n || (i > 0 && ids[i] <= ids[i - 1]))
+        return fail(ZK_ERR_BAD_INPUT, "party ids must be ascending and < n");
+    }
+    if (np <= dimension || (np < n && np <= 4 * l - 2))
+      return fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
+    return ZK_OK;
+  }
+  // d_fft / d_ifft: shares, in_mask and the outputs are [n][m/l]; the king's word is compact, [np][m/l] in king_tmp: row i is
+  // fft1 of the row of parties[i] (NttSrc with one vector per pointer), for the inverse times 1 / m, plus that party's in-mask
+  // row -- built as d_fft_checked builds its word, row by row.
+  int d_fft_checked_parties(void* shares, const uint32_t* parties, int np, const void* in_mask, const void* out_mask,
+                            int rearrange, int log_m, int inverse, const void* g, uint64_t seed, void* out, uint8_t* status,
+                            uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    if (!shares) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (out == shares) out = nullptr;
+    const int log_l = ilog2(l);
+    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    uint32_t ids[GAO_MAX_N];
+    int rc = checked_list(parties, np, 2 * l, ids);
+    if (rc) return rc;
+    if (np == n) return d_fft_checked(shares, in_mask, out_mask, rearrange, log_m, inverse, g, seed, out, status, errpos,
+                                      summary, st);
+    const size_t Lc = ((size_t)1 << log_m) / l, cnt = (size_t)np * Lc;
+    DevBuf& king_tmp_ = ws(st)->king_tmp;
+    ZK_HIP(king_tmp_.ensure(cnt * sizeof(Fr)));
+    Fr* word = (Fr*)king_tmp_.p;
+    const bool scaled = inverse && in_mask;
+    const Fr minv = scaled ? Fr::from_u64((uint64_t)1 << log_m).inverse() : Fr::one();
+    static_assert(GAO_MAX_N <= NTT_SRC_MAX, "one pointer per listed row");
+    NttSrc<Fr> src{};
+    for (int i = 0; i < np; i++) src.p[i] = (const Fr*)shares + (size_t)ids[i] * Lc;
+    src.per = 1;
+    // (a mask folded into fft1's last pass is one contiguous [batch][m/l] vector: the rows of a list are not, they are added below)
+    if ((rc = fft1_src(word, log_m, inverse, (size_t)np, nullptr, st, src))) return rc;
+    if (scaled && (rc = vec_scale(word, &minv, cnt, st))) return rc;
+    if (in_mask)
+      for (int i = 0; i < np; i++)
+        if ((rc = vec_add(word + (size_t)i * Lc, (const Fr*)in_mask + (size_t)ids[i] * Lc, Lc, st))) return rc;
+    if ((rc = pss_repair_parties(word, ids, np, Lc, 2 * l, status, errpos, summary, st))) return rc;
+    return fft2_king(word, nullptr, ids, np, log_m, inverse, g, inverse && !scaled ? 1 : 0, rearrange, seed,
+                     out ? out : shares, out_mask, st);
+  }
+  // d_pp (dpp/mod.rs:37-52): the king's word is num ++ den per party, packed shares of degree < 2l; two repairs, then the
+  // unchecked king with the list.  status / errpos [2 len], summary [2][3 + n]: num's, then den's.  The deg_red that ends
+  // d_pp is not checked: the king produced that word itself and its cap is 0.
+  int d_pp_checked(void* num, void* den, const uint32_t* parties, int np, const void* in_mask, const void* out_mask, size_t len,
+                   uint64_t seed, void* out, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    uint32_t ids[GAO_MAX_N];
+    int rc = checked_list(parties, np, 2 * l, ids);
+    if (rc) return rc;
+    if (!len) return ZK_OK;
+    if (!num || !den || !out || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (len >= ((size_t)1 << 31)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
+    if ((rc = pss_repair_parties(num, ids, np, len, 2 * l, status, errpos, summary, st))) return rc;
+    if ((rc = pss_repair_parties(den, ids, np, len, 2 * l, status + len, errpos ? errpos + len : nullptr,
+                                 summary ? summary + 3 + n : nullptr, st)))
+      return rc;
+    return d_pp_king((const Fr*)num, (const Fr*)den, ids, np, len, seed, (Fr*)out, st, true, (const Fr*)in_mask,
+                     (const Fr*)out_mask);
   }

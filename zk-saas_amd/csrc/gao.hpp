@@ -15,7 +15,8 @@
 // a value of type G::V<T> holding one T per lane: GaoDevGroup (gao_impl.hpp) maps them to the wave's cross-lane builtins and
 // V<T> = T, GaoHostGroup below is a loop over an array of n lanes.  Lane p holds coefficient p of a polynomial.
 // zk_pss_unpack_robust_parties -- the shares of a party list, the others absent -- runs the same two parts on a word made
-// full-length again: the section "absent parties" below (tests/native/gao_erasure_host_test.cpp runs that text).
+// full-length again: the section "absent parties" below (tests/native/gao_erasure_host_test.cpp runs that text), and
+// zk_pss_repair_parties is its repair form (tests/native/gao_repair_parties_host_test.cpp).
 #pragma once
 #include <type_traits>
 
@@ -433,26 +434,64 @@ ZK_HD void gao_deflate(F* x, const F& r, int q, Xch xch) {
 // Stage 2's result for the word y~ (h' = h Lambda, errpos over all n places) -> the result for the listed shares.  slam: lane
 // i < l holds 1 / Lambda(g w_2l^i); lamc: lane j holds coefficient j of Lambda.  All lanes of the wave take every cross-lane
 // step; k division steps by the monic Lambda, and only when the message is wanted.
-template <class F, class G>
+// RE (zk_pss_repair_parties): errpos is masked against the list and the verdict demoted as above; the secrets are not scaled
+// and h' is not divided -- what the repair needs is ev, lane p's h'(w_n^p) = h(w_n^p) Lambda(w_n^p), zeroed on a demotion.
+template <class F, class G, bool RE = false>
 ZK_HD void gao_absent_finish(const G& g, int k, int rho, uint32_t listed, bool want_message,
                              const typename G::template V<F>& slam, const typename G::template V<F>& lamc,
-                             GaoResult<F, G>& r) {
+                             GaoResult<F, G, RE>& r) {
   using VF = typename G::template V<F>;
   const F zero = F::zero();
   const bool ok = r.status != 2 && !(r.errpos & ~listed);
   r.status = ok ? r.status : 2;
   r.errpos = ok ? r.errpos : 0;
-  r.sec = g.template make<F>([&](int p) { return ok ? g.at(r.sec, p) * g.at(slam, p) : zero; });
-  VF rem = g.template make<F>([&](int p) { return ok ? g.at(r.h, p) : zero; });
-  VF h = g.template make<F>([&](int) { return zero; });
-  if (want_message)
-    for (int j = k - 1; j >= 0; j--) {
-      const F q = g.bcast(rem, rho + j);
-      const VF sh = g.shift(lamc, j);
-      rem = g.template make<F>([&](int p) { return g.at(rem, p) - q * g.at(sh, p); });
-      h = g.template make<F>([&](int p) { return p == j ? q : g.at(h, p); });
-    }
-  r.h = h;
+  if constexpr (RE) {
+    r.ev = g.template make<F>([&](int p) { return ok ? g.at(r.ev, p) : zero; });
+  } else {
+    r.sec = g.template make<F>([&](int p) { return ok ? g.at(r.sec, p) * g.at(slam, p) : zero; });
+    VF rem = g.template make<F>([&](int p) { return ok ? g.at(r.h, p) : zero; });
+    VF h = g.template make<F>([&](int) { return zero; });
+    if (want_message)
+      for (int j = k - 1; j >= 0; j--) {
+        const F q = g.bcast(rem, rho + j);
+        const VF sh = g.shift(lamc, j);
+        rem = g.template make<F>([&](int p) { return g.at(rem, p) - q * g.at(sh, p); });
+        h = g.template make<F>([&](int p) { return p == j ? q : g.at(h, p); });
+      }
+    r.h = h;
+  }
+}
+
+// ---------------------------------------------------------------- repair with a party list (zk_pss_repair_parties)
+// The decoder's re-encoding of y~ is h'(w_n^p) = h(w_n^p) Lambda(w_n^p); the share to write is that times 1 / Lambda(w_n^p).
+// The n inverses are the one table the repair adds: a device table of its own (GaoAbsent travels as a launch argument and
+// has no room), read at a run-time index by the lanes that store.
+template <class F>
+struct GaoInvLambda {
+  F v[GAO_MAX_N];          // 1 / Lambda(w_n^p) for a listed party p, zero for an absent one
+};
+// one batch inversion: prefix products, the inverse of the last, and back
+template <class P>
+inline GaoInvLambda<Fp<P>> gao_make_inv_lambda(const GaoAbsent<Fp<P>>& a) {
+  using F = Fp<P>;
+  GaoInvLambda<F> t;
+  F pre[GAO_MAX_N];
+  F acc = F::one();
+  for (int p = 0; p < GAO_MAX_N; p++) {
+    t.v[p] = F::zero(), pre[p] = acc;
+    if ((a.listed >> p) & 1) acc = acc * a.ld.lam[p];
+  }
+  F inv = acc.inverse();
+  for (int p = GAO_MAX_N - 1; p >= 0; p--)
+    if ((a.listed >> p) & 1) t.v[p] = inv * pre[p], inv = inv * a.ld.lam[p];
+  return t;
+}
+// put(p, row of party p, h(w_n^p)) for every listed party p named in the errpos of a corrected chunk: gao_repair_word for a
+// result gao_absent_finish has passed.  row, ilam: lane p's row of the share matrix and 1 / Lambda(w_n^p); ilam(p) is read
+// only by a lane that stores.
+template <class F, class G, class Row, class ILam, class Put>
+ZK_HD void gao_repair_word_parties(const G& g, const GaoResult<F, G, true>& r, Row row, ILam ilam, Put put) {
+  gao_repair_word<F, G>(g, r, [&](int p, const F& v) { put(p, row(p), v * ilam(p)); });
 }
 
 #if defined(__HIPCC__)
@@ -471,6 +510,10 @@ template <class FrP>
 int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wk, int l, const void* shares, const uint32_t* parties, int nparties,
                                   size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
                                   uint32_t* errpos, uint64_t* summary, hipStream_t st);
+// zk_pss_repair_parties: shares [nparties][nchunks] of the listed parties in place, the verdicts of the call above
+template <class FrP>
+int gao_repair_parties_run(IEngine* e, DevBuf& wk, int l, void* shares, const uint32_t* parties, int nparties, size_t nchunks,
+                           int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
 #endif
 
 }  // namespace zk

@@ -1,4 +1,4 @@
-// zk_pss_unpack_robust, zk_pss_unpack_robust_parties and zk_pss_repair over the scalar field of this curve (gao_impl.hpp).
+// zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair and zk_pss_repair_parties over the scalar field of this curve (gao_impl.hpp).
 #include "curves.hpp"
 #include "gao_impl.hpp"
 
@@ -8,4 +8,6 @@ template int gao_unpack_robust_run<Bn254Fr>(IEngine*, DevBuf&, int, const void*,
 template int gao_unpack_robust_parties_run<Bn254Fr>(IEngine*, DevBuf&, int, const void*, const uint32_t*, int, size_t, int, void*,
                                                void*, uint8_t*, uint32_t*, uint64_t*, hipStream_t);
 template int gao_repair_run<Bn254Fr>(IEngine*, DevBuf&, int, void*, size_t, int, uint8_t*, uint32_t*, uint64_t*, hipStream_t);
+template int gao_repair_parties_run<Bn254Fr>(IEngine*, DevBuf&, int, void*, const uint32_t*, int, size_t, int, uint8_t*, uint32_t*,
+                                        uint64_t*, hipStream_t);
 }  // namespace zk

@@ -1,4 +1,4 @@
-// Kernels and host drivers of zk_pss_unpack_robust and zk_pss_unpack_robust_parties (gao.hpp says what they compute).  Included
+// Kernels and host drivers of zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair and zk_pss_repair_parties (gao.hpp says what they compute).  Included
 // by gao_<curve>.hip only.  Each stage is one body with two kernels: the all-parties one, and the one for a party list (ER).
 //   stage 1  one lane per chunk (two at l = 8): the n shares are loaded once, transformed in registers, coefficients k .. n - 1 tested; a
 //            clean chunk gets its secrets (and message) and status 0, a dirty one is appended to a compact list
@@ -7,6 +7,8 @@
 //            leaves at once when the count is zero -- so the call never synchronises with the host.
 // zk_pss_repair is the all-parties form of both with no secrets and no message: stage 1 ends at the test of the coefficients
 // (SCAN: the scan kernel), stage 2 stores lane p's re-encoding over the share of a party named in errpos (REPAIR).
+// zk_pss_repair_parties is SCAN and REPAIR together with ER: the scan loads with the multiplication by Lambda(w^p) and tests
+// at k + rho, the repair divides lane p's re-encoding by Lambda(w^p) again and stores it into the party's row.
 #pragma once
 #include <algorithm>
 
@@ -68,12 +70,13 @@ struct GaoWork {
 // product is by 1 / (n Lambda(g w_2l^i)) and the message is deflated by the rho roots of Lambda.  tab: the device table.
 // SCAN: the inverse transform and the test only -- status and errpos of a clean chunk, the list of the dirty ones, no secrets
 // and no message: 1 / 5 / 17 products per chunk at l = 1, 2, 4; at l = 8 the two lanes' 17 each and the 15 of the split.
+// SCAN with ER (zk_pss_repair_parties): listed -- bit p: party p is listed; its row is the number of listed parties below it.
 template <class P, int L, bool ER, bool SCAN = false>
 __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const Fp<P>* __restrict__ shares, size_t nchunks,
                                                 int k, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
                                                 uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, const GaoWork& wk,
                                                 const GaoAbsentLoad<Fp<P>>* ab, int rho,
-                                                const GaoAbsent<Fp<P>>* __restrict__ tab) {
+                                                const GaoAbsent<Fp<P>>* __restrict__ tab, uint32_t listed = 0) {
   using F = Fp<P>;
   constexpr int N = 4 * L, SP = gao_split(L), M = N / SP;
   const int kd = ER ? k + rho : k;       // the dimension the word is tested and evaluated at
@@ -88,6 +91,11 @@ __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const
     F x[M];
     if constexpr (ER)
       gao_load<M, SP>(c, q, [&](int p) {
+        if constexpr (SCAN) {      // the row from the list's bit mask, two scalar operations: 32 row numbers held in scalar
+                                   // registers beside the constants made the l = 8 scan spill some
+          const int row = __builtin_popcount(listed & ((1u << p) - 1));
+          return (listed >> p) & 1 ? load_elem(shares + (size_t)row * nchunks + j) * ab->lam[p] : F::zero();
+        }
         const int row = ab->row[p];
         return row < 0 ? F::zero() : load_elem(shares + (size_t)row * nchunks + j) * ab->lam[p];
       }, x);
@@ -165,6 +173,13 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_scan_kernel(const GaoConsts<F
                                                               uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage1_body<P, L, false, true>(c, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr, 0, nullptr);
 }
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_scan_parties_kernel(const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab,
+                                                                      const Fp<P>* __restrict__ shares, size_t nchunks, int k,
+                                                                      int rho, uint32_t listed, uint8_t* __restrict__ status,
+                                                                      uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage1_body<P, L, true, true>(c, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, &ab, rho, nullptr, listed);
+}
 // k: the caller's dimension
 template <class P, int L>
 __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
@@ -178,7 +193,8 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
 // ER: lane p reads its row and Lambda(w^p) from the device table (a run-time index: not from kernel arguments), the decoder
 // runs at dimension k + rho and gao_absent_finish maps its result back to the listed shares
 // REPAIR: `shares` is written: lane p stores its re-encoding h(w_n^p) when bit p of the final errpos is set; no secrets, no
-// message (the decoder's flag RE)
+// message (the decoder's flag RE).  With ER the store is h'(w^p) / Lambda(w^p) into the party's row; ilam: the device table of
+// the inverses, read at a run-time index by a lane that stores
 template <class P, bool REPAIR>
 using GaoSharesPtr = std::conditional_t<REPAIR, Fp<P>*, const Fp<P>* __restrict__>;
 template <class P, bool ER, bool REPAIR = false>
@@ -186,7 +202,8 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
                                                 size_t nchunks, int k, Fp<P>* __restrict__ secrets,
                                                 Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
                                                 uint32_t* __restrict__ errpos, const GaoWork& wk,
-                                                const GaoAbsent<Fp<P>>* __restrict__ tab) {
+                                                const GaoAbsent<Fp<P>>* __restrict__ tab,
+                                                const Fp<P>* __restrict__ ilam = nullptr) {
   using F = Fp<P>;
   const uint32_t cnt = *wk.count;
   const uint32_t gpb = GAO_THREADS / n, stride = gridDim.x * gpb;
@@ -212,9 +229,13 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
     if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * nchunks + j) * lam : F::zero();
     else y = live ? load_elem(shares + (size_t)p * nchunks + j) : F::zero();
     GaoResult<F, GaoDevGroup, REPAIR> r = gao_chunk<F, GaoDevGroup, REPAIR>(g, c, n, kd, live, y, xp, xinv, sp);
-    if constexpr (ER) gao_absent_finish<F, GaoDevGroup>(g, k, rho, listed, message != nullptr, slam, lamc, r);
+    if constexpr (ER) gao_absent_finish<F, GaoDevGroup, REPAIR>(g, k, rho, listed, message != nullptr, slam, lamc, r);
     if (!live) continue;
-    if constexpr (REPAIR) {
+    if constexpr (REPAIR && ER) {
+      gao_repair_word_parties<F, GaoDevGroup>(
+          g, r, [&](int) { return row; }, [&](int lane) { return load_elem(ilam + lane); },
+          [&](int, int at, const F& v) { store_elem(shares + (size_t)at * nchunks + j, v); });
+    } else if constexpr (REPAIR) {
       gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(shares + (size_t)lane * nchunks + j, v); });
     } else {
       if (message && p < k) store_elem(message + (size_t)p * nchunks + j, r.h);
@@ -254,6 +275,15 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage2_parties_kernel(
     uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage2_body<P, true>(c, n, l, shares, nchunks, k, secrets, message, status, errpos, wk, tab);
 }
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_repair_parties_kernel(const GaoConsts<Fp<P>> c,
+                                                                        const GaoAbsent<Fp<P>>* __restrict__ tab,
+                                                                        const Fp<P>* __restrict__ ilam, int n, int l,
+                                                                        Fp<P>* shares, size_t nchunks, int k,
+                                                                        uint8_t* __restrict__ status,
+                                                                        uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage2_body<P, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, tab, ilam);
+}
 // the table of a call, from the launch's arguments to working memory: one word per lane
 template <class F>
 __global__ __launch_bounds__(GAO_THREADS) void gao_absent_table_kernel(const GaoAbsent<F> a, GaoAbsent<F>* __restrict__ out) {
@@ -261,6 +291,15 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_absent_table_kernel(const Gao
   const uint32_t* src = (const uint32_t*)&a;
   uint32_t* dst = (uint32_t*)out;
   for (uint32_t i = threadIdx.x; i < sizeof(GaoAbsent<F>) / 4; i += blockDim.x) dst[i] = src[i];
+}
+
+// the same for the inverses of a repair with a party list
+template <class F>
+__global__ __launch_bounds__(GAO_THREADS) void gao_inv_lambda_table_kernel(const GaoInvLambda<F> a, GaoInvLambda<F>* __restrict__ out) {
+  static_assert(sizeof(GaoInvLambda<F>) % 4 == 0, "words");
+  const uint32_t* src = (const uint32_t*)&a;
+  uint32_t* dst = (uint32_t*)out;
+  for (uint32_t i = threadIdx.x; i < sizeof(GaoInvLambda<F>) / 4; i += blockDim.x) dst[i] = src[i];
 }
 
 // ---------------------------------------------------------------- host driver
@@ -329,10 +368,12 @@ int gao_repair_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, size_t nchunk
 }
 // With all n parties listed this is the call above; otherwise the kernels' forms for absent parties, with the table of the
 // party list (gao_make_absent, host) put into working memory by a launch of its own ahead of them.
-template <class FrP>
-int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, const uint32_t* parties, int np,
-                                  size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
-                                  uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+// REPAIR: zk_pss_repair_parties -- the scan in place of stage 1, the repair form of stage 2, `shares` written; the inverses
+// 1 / Lambda(w^p) go into a second table behind the first, by a launch of their own.
+template <class FrP, bool REPAIR>
+int gao_party_list_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPAIR, void*, const void*> shares,
+                       const uint32_t* parties, int np, size_t nchunks, int dimension, void* secrets, void* message,
+                       uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
   using Fr = Fp<FrP>;
   const int n = 4 * l;
   if (l != 1 && l != 2 && l != 4 && l != 8) return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
@@ -346,18 +387,21 @@ int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wkbuf, int l, const void* 
   if (dimension < 1 || dimension > n - 1) return e->fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
   if (np <= dimension) return e->fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
   if (np == n)
-    return gao_unpack_robust_run<FrP>(e, wkbuf, l, shares, nchunks, dimension, secrets, message, status, errpos, summary, st);
+    return gao_all_parties_run<FrP, REPAIR>(e, wkbuf, l, shares, nchunks, dimension, secrets, message, status, errpos, summary,
+                                            st);
   if (nchunks == 0) return ZK_OK;
   if (!shares || !status) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
   if (nchunks >= ((size_t)1 << 32)) return e->fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
   using Tab = GaoAbsent<Fr>;
   constexpr size_t head = 320, tab_bytes = (sizeof(Tab) + 31) / 32 * 32;      // count, summary words, then the table
   static_assert(sizeof(Tab) + 64 <= 4096, "the table travels as a kernel argument");
-  GAO_HIP(wkbuf.ensure(head + tab_bytes + nchunks * 4));
+  constexpr size_t inv_bytes = REPAIR ? sizeof(GaoInvLambda<Fr>) : 0;
+  static_assert(inv_bytes % 32 == 0, "the list stays aligned");
+  GAO_HIP(wkbuf.ensure(head + tab_bytes + inv_bytes + nchunks * 4));
   GaoWork wk;
   wk.count = (uint32_t*)wkbuf.p;
   wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkbuf.p + 32);
-  wk.list = (uint32_t*)((char*)wkbuf.p + head + tab_bytes);
+  wk.list = (uint32_t*)((char*)wkbuf.p + head + tab_bytes + inv_bytes);
   Tab* tab = (Tab*)((char*)wkbuf.p + head);
   GAO_HIP(hipMemsetAsync(wkbuf.p, 0, head, st));
   if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)(3 + n) * 8, st));
@@ -365,13 +409,21 @@ int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wkbuf, int l, const void* 
   const Tab a = gao_make_absent<FrP>(c, l, ids, np, dimension);
   const dim3 blk(GAO_THREADS);
   gao_absent_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(a, tab);
+  [[maybe_unused]] GaoInvLambda<Fr>* inv = (GaoInvLambda<Fr>*)((char*)wkbuf.p + head + tab_bytes);
+  if constexpr (REPAIR) gao_inv_lambda_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(gao_make_inv_lambda<FrP>(a), inv);
   const size_t per_wg = GAO_THREADS / gao_split(l);
   const dim3 grid1((unsigned)((nchunks + per_wg - 1) / per_wg));
-  const Fr* sh = (const Fr*)shares;
+  std::conditional_t<REPAIR, Fr*, const Fr*> sh = (decltype(sh))shares;
   Fr* sec = (Fr*)secrets;
   Fr* msg = (Fr*)message;
   const int k = dimension, rho = a.rho;
-  switch (l) {
+  if constexpr (REPAIR) switch (l) {
+    case 1: gao_scan_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
+    case 2: gao_scan_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
+    case 4: gao_scan_parties_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
+    default: gao_scan_parties_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
+  }
+  else switch (l) {
     case 1: gao_stage1_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
     case 2: gao_stage1_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
     case 4: gao_stage1_parties_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
@@ -379,9 +431,23 @@ int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wkbuf, int l, const void* 
   }
   const size_t gpb = GAO_THREADS / n;
   const dim3 grid2((unsigned)std::min<size_t>((nchunks + gpb - 1) / gpb, GAO_STAGE2_GRID));
-  gao_stage2_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, n, l, sh, nchunks, k, sec, msg, status, errpos, wk);
+  if constexpr (REPAIR) gao_repair_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, inv->v, n, l, sh, nchunks, k, status, errpos, wk);
+  else gao_stage2_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, n, l, sh, nchunks, k, sec, msg, status, errpos, wk);
   GAO_HIP(hipGetLastError());
   return ZK_OK;
+}
+template <class FrP>
+int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, const uint32_t* parties, int np,
+                                  size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
+                                  uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+  return gao_party_list_run<FrP, false>(e, wkbuf, l, shares, parties, np, nchunks, dimension, secrets, message, status, errpos,
+                                        summary, st);
+}
+template <class FrP>
+int gao_repair_parties_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, const uint32_t* parties, int np, size_t nchunks,
+                           int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+  return gao_party_list_run<FrP, true>(e, wkbuf, l, shares, parties, np, nchunks, dimension, nullptr, nullptr, status, errpos,
+                                       summary, st);
 }
 #undef GAO_HIP
 
