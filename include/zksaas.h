@@ -498,6 +498,51 @@ int zk_d_ifft_checked_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parti
 int zk_d_pp_checked(zk_ctx* ctx, void* num_d, void* den_d, const uint32_t* parties, int nparties, const void* in_mask_d,
                     const void* out_mask_d, size_t len, uint64_t seed, void* out_d, uint8_t* status_d, uint32_t* errpos_d,
                     uint64_t* summary_d, void* stream);
+/* zk_pss_unpack_points_robust: the robust unpack of packed POINT shares -- the CRS vectors a party holds and the words the
+ * d_msm kings receive are Reed-Solomon words over the share domain H_n whose symbols are curve points, Y_p = y_p G.
+ * secret-sharing/src/pss.rs:125-166 with T = a group element; the code is that of secret-sharing/src/gao.rs, the decoder is
+ * not: gao.rs divides polynomials by their coefficients, and there is no division in the exponent.  What can be formed are
+ * fixed scalar combinations of the shares: the syndromes S_j = sum_p w_n^(-p j) Y_p, j = dimension .. n - 1, which are all the
+ * identity exactly for a codeword, and which for ONE wrong share, E at party q, are S_j = w_n^(-q j) E -- q is the one
+ * candidate with S_(j+1) = w_n^(-q) S_j, the honest share is Y_q - w_n^(q dimension) S_dimension.
+ * CORRECTION CAPACITY: cap = 1 when n - dimension >= 2, cap = 0 when n - dimension = 1.  This is deliberately below gao.rs's
+ * (n - dimension) / 2: locating e errors without division means trying error sets, C(n, e) of them with a linear system
+ * each, and that does not scale to l = 8 (n = 32); one error is the model of the checked king rounds, one lying party.
+ *   status 0  all syndromes are the identity.  out_d is zk_pss_unpack_points' result at dimension <= 2l and
+ *             zk_pss_unpack2_points' above, byte for byte (affine output is canonical)
+ *   status 1  exactly one share differs from a codeword of that dimension: errpos has that one bit, out_d is the unpack of
+ *             the corrected word
+ *   status 2  anything else: out_d is identities, errpos is 0.  For l >= 2 two to 2l - 1 wrong shares are always status 2
+ *             (minimum distance 2l + 1 at dimension 2l); for l = 1 two wrong shares can lie within one of another codeword,
+ *             the caveat of zk_pss_unpack_robust
+ * summary_d is laid out as zk_pss_unpack_robust's.  shares_d is [n][nchunks] affine in party order, out_d [nchunks][l] affine.
+ * PRECONDITION: every share is on the curve and in the order-r subgroup (zk_points_decompress_checked /
+ * zk_points_subgroup_check establish it for wire input).  Outside it the verdicts mean nothing; the kernels still terminate,
+ * every loop has a fixed trip count.
+ * Errors: a bad group, a dimension outside 1 .. n - 1, or NULL shares_d / status_d with nchunks > 0 -> ZK_ERR_BAD_INPUT (the
+ * context stays usable); nchunks == 0 is ZK_OK.  No host synchronisation inside the call, working memory from the stream's
+ * workspace (the unpack matrix is the cached one of zk_pss_unpack_points).  All n parties only.  Device engine only. */
+int zk_pss_unpack_points_robust(zk_ctx* ctx, int group, const void* shares_d /* [n][nchunks] affine */, size_t nchunks,
+                                int dimension, void* out_d /* [nchunks][l] affine, or NULL */,
+                                uint8_t* status_d /* [nchunks] */, uint32_t* errpos_d /* [nchunks], or NULL */,
+                                uint64_t* summary_d /* [3 + n], or NULL */, void* stream);
+/* zk_pss_repair_points: the verdicts of zk_pss_unpack_points_robust written back into the shares (pss.rs:125-166 over group
+ * elements, gao.rs's code).  status_d, errpos_d, summary_d and the error returns are exactly that call's on the same input.
+ * WRITTEN: in a status-1 chunk the one element errpos names becomes Y_q - E, in affine form.  NOT WRITTEN: anything else --
+ * clean chunks, failed chunks, the other shares of a corrected chunk.  A second call finds the former status-1 chunks clean.
+ * All n parties only.  No host synchronisation, working memory from the stream's workspace.  Device engine only. */
+int zk_pss_repair_points(zk_ctx* ctx, int group, void* shares_d /* [n][nchunks] affine, in place */, size_t nchunks,
+                         int dimension, uint8_t* status_d /* [nchunks] */, uint32_t* errpos_d /* [nchunks], or NULL */,
+                         uint64_t* summary_d /* [3 + n], or NULL */, void* stream);
+/* zk_d_msm_checked: zk_d_msm with the king's word checked.  The word is c_p = msm_p + in_mask_p
+ * (dist-primitives/src/dmsm/mod.rs:73-85), of degree up to 4l - 2: dimension 4l - 1, one syndrome, sum_p w_n^p c_p --
+ * DETECTION ONLY, as zk_deg_red_checked.  *status (HOST, one byte) is 0 when the syndrome is the identity and 2 otherwise;
+ * `out` is written by zk_d_msm itself and never touched again: the same n group elements for the same input (Jacobian
+ * coordinates are not canonical, and two zk_d_msm calls on one input need not agree in their bytes).  The syndrome is a second fused MSM over the same bases
+ * and scalars with the coefficients w_n^p, so the call costs two zk_d_msm.  NULL status -> ZK_ERR_BAD_INPUT; the other
+ * errors are zk_d_msm's.  There is no party-list form: with n - 1 parties no redundancy is left.  Device engine only. */
+int zk_d_msm_checked(zk_ctx* ctx, int group, const void* bases_d, const void* scalars_d, size_t len, const void* in_mask,
+                     const void* out_mask, void* out, uint8_t* status /* host, 1 byte */, void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

@@ -75,6 +75,29 @@ pub fn d_msm_rows<C: SWCurveConfig>(
     Ok(unpack_jacobian::<C>(&out, k))
 }
 
+/// `zk_d_msm_checked`: `d_msm` for all `n` parties on one device with the king's word `msm_p + in_mask_p`
+/// (`dmsm/mod.rs:73-85`) checked at dimension `4l - 1`: detection only.  Rows `[n][len]`, `n` masks; returns the `n` output
+/// shares -- exactly the unchecked call's -- and whether the word was a codeword.
+pub fn d_msm_checked_rows<C: SWCurveConfig>(ctx: &crate::Context, bases: &[Affine<C>], scalars: &[C::ScalarField], len: usize,
+                                            in_masks: &[Projective<C>], out_masks: &[Projective<C>])
+                                            -> Result<(Vec<Projective<C>>, bool), MpcNetError> {
+    let n = ctx.n;
+    if bases.len() != n * len || scalars.len() != n * len || in_masks.len() != n || out_masks.len() != n {
+        return Err(MpcNetError::BadInput { err: "d_msm_checked_rows: [n][len] rows and n masks expected" });
+    }
+    let b = DeviceBuf::from_slice(ctx, &pack_affine(bases))?;
+    let s = DeviceBuf::from_slice(ctx, scalars)?;
+    let im = pack_jacobian(in_masks);
+    let om = pack_jacobian(out_masks);
+    let mut out = vec![0u64; im.len()];
+    let mut status = 0u8;
+    check(ctx, unsafe {
+        sys::zk_d_msm_checked(ctx.raw(), group_of::<C>(), b.ptr(), s.ptr(), len, im.as_ptr() as *const c_void,
+                              om.as_ptr() as *const c_void, out.as_mut_ptr() as *mut c_void, &mut status, ptr::null_mut())
+    })?;
+    Ok((unpack_jacobian::<C>(&out, n), status == 0))
+}
+
 /// `MsmMask::sample` (`dmsm/mod.rs:21-47`) by the library's dealer: one `(in_mask, out_mask)` per party.
 pub fn sample_msm_masks<C: SWCurveConfig>(ctx: &crate::Context, gen: Affine<C>)
                                           -> Result<Vec<(Projective<C>, Projective<C>)>, MpcNetError> {

@@ -3,11 +3,12 @@
 //! here a whole vector is packed / unpacked per launch and the party-major layout `[n][m/l]` needs no transpose.
 use core::ptr;
 
+use ark_ec::short_weierstrass::{Affine, SWCurveConfig};
 use ark_ff::PrimeField;
 use mpc_net::MpcNetError;
 use zksaas_hip_sys as sys;
 
-use crate::{check, fr_ptr, Context, DeviceBuf};
+use crate::{check, fr_ptr, group_of, pack_affine, unpack_affine, Context, DeviceBuf};
 
 /// `pack_vec` + `transpose` (`pack.rs:8-35`): secrets `[m]` -> `n` share vectors of length `m / l`.
 pub fn pack_vec<F: PrimeField + 'static>(ctx: &Context, secrets: &[F]) -> Result<Vec<Vec<F>>, MpcNetError> {
@@ -308,6 +309,50 @@ pub fn repair_parties_vec<F: PrimeField + 'static>(ctx: &Context, shares: &[Vec<
                                    v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64, ptr::null_mut())
     })?;
     Ok((rows(&sh, parties.len(), nchunks)?, v.read(ctx)?))
+}
+
+/// `zk_pss_unpack_points_robust`: the robust unpack of all `n` parties' packed POINT shares, one vector of affine points per
+/// party (`secret-sharing/src/pss.rs:125-166` with `T` a group element).  One wrong share per chunk is located and corrected
+/// when `n - dimension >= 2`; at dimension `4l - 1` the call only detects.  Returns `[nchunks][l]` points -- the unpack of the
+/// clean or corrected word, the identity for a failed chunk -- and the verdicts.
+pub fn unpack_points_robust_vec<C: SWCurveConfig>(ctx: &Context, shares: &[Vec<Affine<C>>], dimension: usize)
+                                                  -> Result<(Vec<Affine<C>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten_points::<C>(shares, ctx.n)?;
+    let limbs = pack_affine(&flat);
+    let per = if flat.is_empty() { 0 } else { limbs.len() / flat.len() };
+    let sh = DeviceBuf::from_slice(ctx, &limbs)?;
+    let out = DeviceBuf::alloc(ctx, nchunks * ctx.l * per * 8)?;
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    check(ctx, unsafe {
+        sys::zk_pss_unpack_points_robust(ctx.raw(), group_of::<C>(), sh.ptr(), nchunks, dimension as i32, out.ptr(),
+                                         v.st.ptr() as *mut u8, v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64, ptr::null_mut())
+    })?;
+    let got: Vec<u64> = out.to_vec(nchunks * ctx.l * per)?;
+    Ok((unpack_affine::<C>(&got, nchunks * ctx.l), v.read(ctx)?))
+}
+
+/// `zk_pss_repair_points`: the verdicts of [`unpack_points_robust_vec`] written back into the shares: in a corrected chunk
+/// the one share `errpos` names is replaced by the honest one, every other point is returned as it came.
+pub fn repair_points_vec<C: SWCurveConfig>(ctx: &Context, shares: &[Vec<Affine<C>>], dimension: usize)
+                                           -> Result<(Vec<Vec<Affine<C>>>, Verdicts), MpcNetError> {
+    let (flat, nchunks) = flatten_points::<C>(shares, ctx.n)?;
+    let limbs = pack_affine(&flat);
+    let sh = DeviceBuf::from_slice(ctx, &limbs)?;
+    let v = VerdictBufs::alloc(ctx, nchunks)?;
+    check(ctx, unsafe {
+        sys::zk_pss_repair_points(ctx.raw(), group_of::<C>(), sh.ptr(), nchunks, dimension as i32, v.st.ptr() as *mut u8,
+                                  v.ep.ptr() as *mut u32, v.sm.ptr() as *mut u64, ptr::null_mut())
+    })?;
+    let got: Vec<u64> = sh.to_vec(limbs.len())?;
+    let pts = unpack_affine::<C>(&got, flat.len());
+    Ok((pts.chunks(nchunks.max(1)).map(|c| c.to_vec()).collect(), v.read(ctx)?))
+}
+
+fn flatten_points<C: SWCurveConfig>(shares: &[Vec<Affine<C>>], want: usize) -> Result<(Vec<Affine<C>>, usize), MpcNetError> {
+    if shares.len() != want || shares.iter().any(|r| r.len() != shares[0].len()) {
+        return Err(MpcNetError::BadInput { err: "one vector of equal length per party expected" });
+    }
+    Ok((shares.iter().flat_map(|r| r.iter().copied()).collect(), shares[0].len()))
 }
 
 /// [`fft2_king_checked_vec`] when only the listed parties' vectors reached the king (`zk_fft2_king_checked_parties`):

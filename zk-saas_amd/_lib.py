@@ -35,6 +35,7 @@ SYMBOLS = [
     "zk_pss_repair", "zk_fft2_king_checked", "zk_d_fft_checked", "zk_d_ifft_checked", "zk_deg_red_checked",
     "zk_pss_repair_parties", "zk_fft2_king_checked_parties", "zk_d_fft_checked_parties", "zk_d_ifft_checked_parties",
     "zk_d_pp_checked",
+    "zk_pss_unpack_points_robust", "zk_pss_repair_points", "zk_d_msm_checked",
 ]
 
 _lib = None
@@ -233,6 +234,9 @@ def load():
     lib.zk_d_fft_checked_parties.argtypes = [vp, vp, ids, i32, vp, vp, i32, i32, u64, vp, vp, vp, vp, vp]
     lib.zk_d_ifft_checked_parties.argtypes = [vp, vp, ids, i32, vp, vp, i32, i32, vp, u64, vp, vp, vp, vp, vp]
     lib.zk_d_pp_checked.argtypes = [vp, vp, vp, ids, i32, vp, vp, sz, u64, vp, vp, vp, vp, vp]
+    lib.zk_pss_unpack_points_robust.argtypes = [vp, i32, vp, sz, i32, vp, vp, vp, vp, vp]
+    lib.zk_pss_repair_points.argtypes = [vp, i32, vp, sz, i32, vp, vp, vp, vp]
+    lib.zk_d_msm_checked.argtypes = [vp, i32, vp, vp, sz, vp, vp, vp, vp, vp]
     lib.zk_points_subgroup_check.argtypes = [vp, i32, vp, sz, vp, vp]
     lib.zk_points_decompress_checked.argtypes = [vp, i32, vp, sz, vp, vp, vp]
     lib.zk_groth16_verify_bytes.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]

@@ -225,6 +225,45 @@ class PackedSharingParams(Context):
                                                        _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
+    def unpack_points_robust(self, group, shares_d, nchunks, dimension=None, want_out=True, stream=None):
+        """zk_pss_unpack_points_robust: the robust unpack of all n parties' packed POINT shares [n][nchunks] affine (pss.rs:125-166
+        over group elements).  One wrong share per chunk is located and corrected when n - dimension >= 2; at dimension
+        4l - 1 the call only detects.  dimension: 2l (the default) up to 4l - 1.  Returns a RobustUnpack with status, errpos
+        and summary; `out` is [nchunks][l] affine (None with want_out=False): the unpack of the clean or corrected word,
+        identities for a failed chunk."""
+        k = 2 * self.l if dimension is None else int(dimension)
+        r = self._report(nchunks, k)
+        width = self.fq.nl * (4 if group == ZK_G2 else 2) * 8
+        r.out = DeviceBuffer(self, max(1, nchunks * self.l) * width) if want_out else None
+        self._check(self.lib.zk_pss_unpack_points_robust(self.h, group, _ptr(shares_d), nchunks, k, _ptr(r.out), _ptr(r.status),
+                                                         _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
+
+    def repair_points(self, group, shares_d, nchunks, dimension=None, stream=None):
+        """zk_pss_repair_points: unpack_points_robust's verdicts written back into shares_d [n][nchunks] affine, in place: in a
+        corrected chunk the one share errpos names becomes the honest one, every other element keeps its bytes.  Returns a
+        RobustUnpack with status, errpos and summary; `out` is shares_d."""
+        k = 2 * self.l if dimension is None else int(dimension)
+        r = self._report(nchunks, k)
+        r.out = shares_d
+        self._check(self.lib.zk_pss_repair_points(self.h, group, _ptr(shares_d), nchunks, k, _ptr(r.status), _ptr(r.errpos),
+                                                  _ptr(r.summary_d), stream))
+        return r
+
+    def d_msm_checked(self, group, bases_d, scalars_d, length, msm_mask=None, stream=None):
+        """zk_d_msm_checked: d_msm with the king's word msm_p + in_mask_p checked at dimension 4l - 1 (detection only).
+        Returns (out, status): out as d_msm's, [n][3 * coord limbs] Jacobian; status 0 (the word is a codeword) or 2."""
+        msm_mask = msm_mask or MsmMask.zero()
+        nl = self.fq.nl * (2 if group == ZK_G2 else 1)
+        out = np.zeros((self.n, 3 * nl), dtype=np.uint64)
+        status = C.c_uint8(255)
+        im = None if msm_mask.in_mask is None else np.ascontiguousarray(msm_mask.in_mask, dtype=np.uint64)
+        om = None if msm_mask.out_mask is None else np.ascontiguousarray(msm_mask.out_mask, dtype=np.uint64)
+        self._check(self.lib.zk_d_msm_checked(self.h, group, _ptr(bases_d), _ptr(scalars_d), length,
+                                              None if im is None else im.ctypes.data, None if om is None else om.ctypes.data,
+                                              out.ctypes.data, C.addressof(status), stream))
+        return out, status.value
+
     def lagrange_unpack(self, shares_d, nchunks, parties, out=None, stream=None):
         return self.unpack2(shares_d, nchunks, parties, out, stream)
 

@@ -856,6 +856,21 @@ int zk_deg_red_checked(zk_ctx* ctx, void* x_d, const void* in_mask_d, const void
   CTX_OR_FAIL();
   return e->deg_red_checked(x_d, in_mask_d, out_mask_d, len, seed, status_d, errpos_d, summary_d, S(stream));
 }
+int zk_pss_unpack_points_robust(zk_ctx* ctx, int group, const void* shares_d, size_t nchunks, int dimension, void* out_d,
+                                uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_unpack_points_robust(group, shares_d, nchunks, dimension, out_d, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_pss_repair_points(zk_ctx* ctx, int group, void* shares_d, size_t nchunks, int dimension, uint8_t* status_d,
+                         uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_repair_points(group, shares_d, nchunks, dimension, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_d_msm_checked(zk_ctx* ctx, int group, const void* bases_d, const void* scalars_d, size_t len, const void* in_mask,
+                     const void* out_mask, void* out, uint8_t* status, void* stream) {
+  CTX_OR_FAIL();
+  return e->d_msm_checked(group, bases_d, scalars_d, len, in_mask, out_mask, out, status, S(stream));
+}
 int zk_pss_repair_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, size_t nchunks, int dimension,
                           uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
   CTX_OR_FAIL();

@@ -422,6 +422,15 @@ class IEngine {
   virtual int d_pp_checked(void* num, void* den, const uint32_t* parties, int np, const void* in_mask, const void* out_mask,
                            size_t len, uint64_t seed, void* out, uint8_t* status, uint32_t* errpos, uint64_t* summary,
                            hipStream_t st) = 0;
+  // the robust unpack of packed point shares [n][nchunks] affine and its repair form (gao_points.hpp); out, errpos, summary
+  // may be null
+  virtual int pss_unpack_points_robust(int group, const void* shares, size_t nchunks, int dimension, void* out, uint8_t* status,
+                                       uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  virtual int pss_repair_points(int group, void* shares, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos,
+                                uint64_t* summary, hipStream_t st) = 0;
+  // d_msm with the king's word checked: status (host, one byte) is 0 or 2
+  virtual int d_msm_checked(int group, const void* bases, const void* scalars, size_t len, const void* in_mask,
+                            const void* out_mask, void* out, uint8_t* status, hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,

@@ -12,6 +12,7 @@
 #include "qap.hpp"
 #include "setup.hpp"
 #include "gao.hpp"
+#include "gao_points.hpp"
 #include "msm.hpp"
 #include "hostpool.hpp"
 #include "points.hpp"
@@ -81,6 +82,7 @@ class Engine : public IEngine {
     if (u2c_) (void)hipFree(u2c_);
     for (auto& kv : ucanon_) (void)hipFree(kv.second);
     if (pmc_) (void)hipFree(pmc_);
+    if (gao_pt_tab_) (void)hipFree(gao_pt_tab_);
   }
 
   size_t fr_bytes() const override { return sizeof(Fr); }
@@ -385,6 +387,7 @@ class Engine : public IEngine {
 #include "engine_dist.inc.hpp"       // zk_dist_*: per-rank collective forms
 #include "engine_setup.inc.hpp"      // zk_groth16_setup_scalars: R1CS and trapdoor -> CRS scalars
 #include "engine_gao.inc.hpp"        // zk_pss_unpack_robust: the error-correcting unpack
+#include "engine_gao_points.inc.hpp" // zk_pss_unpack_points_robust, zk_pss_repair_points, zk_d_msm_checked
 
   int ensure_streams() {
     std::lock_guard<std::mutex> lk(mu_);
