@@ -543,6 +543,49 @@ int zk_pss_repair_points(zk_ctx* ctx, int group, void* shares_d /* [n][nchunks] 
  * errors are zk_d_msm's.  There is no party-list form: with n - 1 parties no redundancy is left.  Device engine only. */
 int zk_d_msm_checked(zk_ctx* ctx, int group, const void* bases_d, const void* scalars_d, size_t len, const void* in_mask,
                      const void* out_mask, void* out, uint8_t* status /* host, 1 byte */, void* stream);
+/* zk_pss_repair_batch: zk_pss_repair of several share matrices the way a batched king takes them -- item i is a matrix
+ * [n][nchunks] at shares_d + i * item_stride elements (the three words of a king round of circom_h, ext_wit.rs:127-170, lie
+ * like this).  secret-sharing/src/gao.rs:47-84 per chunk, as zk_pss_repair.  status_d, errpos_d and summary_d follow
+ * zk_pss_repair's definitions per item, the shares of an item change only where zk_pss_repair would change them, elements
+ * between the items keep their bytes, and with nitems == 1 every output equals zk_pss_repair's byte for byte.
+ * One clear, one scan launch and one decoder launch serve all items: a single call's fixed cost, not nitems of them.
+ * Errors (ZK_ERR_BAD_INPUT, nothing written): nitems outside 1 .. 48, item_stride < n * nchunks,
+ * nitems * nchunks >= 2^32, and the refusals of zk_pss_repair.  nchunks == 0 is ZK_OK.
+ * All n parties only.  No host synchronisation, working memory from the stream's workspace.  Device engine only. */
+int zk_pss_repair_batch(zk_ctx* ctx, void* shares_d /* in place */, size_t item_stride /* elements */, int nitems,
+                        size_t nchunks, int dimension, uint8_t* status_d /* [nitems][nchunks] */,
+                        uint32_t* errpos_d /* [nitems][nchunks], or NULL */,
+                        uint64_t* summary_d /* [nitems][3 + n], or NULL */, void* stream);
+/* zk_circom_h_checked: zk_circom_h with every word a king receives checked (groth16/src/ext_wit.rs:104-181; the kings
+ * dist-primitives/src/dfft/mod.rs:264-304 and utils/deg_red.rs:99-115).  Seven words, in this order of items:
+ *   0..2  the d_ifft words of a, b, c (ext_wit.rs:127-159): fft1(x) / m + in_mask; without an in-mask fft1(x), with the
+ *         1 / m in the king's table -- the words of zk_d_ifft_checked
+ *   3..5  the d_fft words (ext_wit.rs:161-170): fft1(x) + in_mask -- the words of zk_d_fft_checked
+ *   6     the deg_red word (ext_wit.rs:173-179): a*b - c + in_mask at dimension 4l - 1 -- DETECTION ONLY as in
+ *         zk_deg_red_checked: status 0 or 2, errpos 0, nothing rewritten
+ * Items 0..5 have dimension 2l: up to l wrong parties per chunk are named and corrected, and h_share_d is then the honest
+ * h.  The three words of a round are repaired by one zk_pss_repair_batch.  status_d and errpos_d are [7][m/l], summary_d
+ * [7][3 + n], each item's as zk_pss_repair defines it.  On honest input h_share_d equals zk_circom_h's bit for bit under the
+ * same seed and masks and every status is 0.  A failed chunk is no error return: its shares go to the king as received and
+ * the item's summary_d[2] counts it.  The in-masks of a round may be partly present.
+ * Errors: those of zk_circom_h, and a NULL status_d -> ZK_ERR_BAD_INPUT.  Device engine only. */
+int zk_circom_h_checked(zk_ctx* ctx, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
+                        const zk_groth16_masks* masks, uint64_t seed, void* h_share_d, uint8_t* status_d /* [7][m/l] */,
+                        uint32_t* errpos_d /* [7][m/l], or NULL */, uint64_t* summary_d /* [7][3 + n], or NULL */,
+                        void* stream);
+/* zk_groth16_prove_checked: zk_groth16_prove (groth16/src/prove.rs, examples/sha256.rs:32-129) with h computed by the chain
+ * of zk_circom_h_checked on the prover's own stream and work buffers; everything else -- the MSMs, the host terms, the
+ * assembly -- is zk_groth16_prove's.  Synchronous: when the call returns the proof is on the host and the report buffers
+ * status_d / errpos_d / summary_d (device, the [7] layouts above) are complete.
+ * COVERED: the seven king words of circom_h.  A party whose QAP shares or round-2 in-mask rows are wrong -- up to l of them
+ * per chunk -- is named, and the proof is the honest proof.
+ * NOT COVERED: the five d_msm rounds.  Their word has dimension 4l - 1, so checking them is detection only and costs a
+ * second MSM each (zk_d_msm_checked); a caller who wants that calls it.  There is no async or batch form.
+ * Errors: those of zk_groth16_prove, and a NULL status_d -> ZK_ERR_BAD_INPUT. */
+int zk_groth16_prove_checked(zk_ctx* ctx, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
+                             const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
+                             int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                             uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

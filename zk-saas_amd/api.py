@@ -225,6 +225,19 @@ class PackedSharingParams(Context):
                                                        _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
+    def repair_batch(self, shares_d, nitems, nchunks, dimension=None, item_stride=None, stream=None):
+        """zk_pss_repair_batch: repair of nitems share matrices [n][nchunks], item i at element i * item_stride of shares_d
+        (default n * nchunks: back to back), with one scan and one decoder launch for all of them.  Returns ONE RobustUnpack
+        with an item axis: status and errpos are [nitems][nchunks] (`nchunks` of the report counts all of them), `summaries`
+        holds one summary per item, `nitems` is set and `out` is shares_d."""
+        k = 2 * self.l if dimension is None else int(dimension)
+        stride = self.n * nchunks if item_stride is None else int(item_stride)
+        r = self._report(max(0, nitems) * nchunks, k, words=max(1, nitems))
+        r.out, r.nitems = shares_d, nitems
+        self._check(self.lib.zk_pss_repair_batch(self.h, _ptr(shares_d), stride, nitems, nchunks, k, _ptr(r.status),
+                                                 _ptr(r.errpos), _ptr(r.summary_d), stream))
+        return r
+
     def unpack_points_robust(self, group, shares_d, nchunks, dimension=None, want_out=True, stream=None):
         """zk_pss_unpack_points_robust: the robust unpack of all n parties' packed POINT shares [n][nchunks] affine (pss.rs:125-166
         over group elements).  One wrong share per chunk is located and corrected when n - dimension >= 2; at dimension
@@ -382,6 +395,41 @@ def base_mul_few(pp, group, base_affine, scalars_d, length, out=None, stream=Non
     out = out or DeviceBuffer(pp, max(1, length) * 3 * nl * 8)
     pp._check(pp.lib.zk_base_mul_few(pp.h, group, base.ctypes.data, _ptr(scalars_d), length, _ptr(out), stream))
     return out
+
+
+H_ITEMS = 7                   # the king words of circom_h: three of d_ifft, three of d_fft, one of deg_red
+
+
+def h_report(pp, log2_m):
+    """the report buffers of zk_circom_h_checked / zk_groth16_prove_checked: a RobustUnpack with an item axis, status and
+    errpos [7][m/l], one summary per item in `summaries` (items 0..5 at dimension 2l, item 6 at 4l - 1: detection only)"""
+    lc = (1 << log2_m) // pp.l
+    r = pp._report(H_ITEMS * lc, 2 * pp.l, words=H_ITEMS)
+    r.nitems = H_ITEMS
+    return r
+
+
+def circom_h(pp, wit_or_bufs, masks=None, seed=0, check=False, log2_m=None, stream=None):
+    """zk_circom_h (ext_wit.rs:104-181) on the QAP share vectors of a Witness (`.qap`, `.log_m`) or on three device buffers
+    [n][m/l] with log2_m given.  masks: a zk_groth16_masks structure, an object that holds one as `.ct`, or None.
+    Returns h [n][m/l]; with check=True zk_circom_h_checked and (h, report), the report as h_report's."""
+    if hasattr(wit_or_bufs, "qap"):
+        qap, log2_m = wit_or_bufs.qap, wit_or_bufs.log_m
+    else:
+        qap = list(wit_or_bufs)
+    if log2_m is None or len(qap) != 3:
+        raise ValueError("three QAP share vectors and log2_m")
+    masks = getattr(masks, "ct", masks)
+    mk = None if masks is None else C.byref(masks)
+    h = pp.alloc_fr(pp.n * ((1 << log2_m) // pp.l))
+    if not check:
+        pp._check(pp.lib.zk_circom_h(pp.h, _ptr(qap[0]), _ptr(qap[1]), _ptr(qap[2]), log2_m, mk, seed, h.ptr, stream))
+        return h
+    rep = h_report(pp, log2_m)
+    rep.out = h
+    pp._check(pp.lib.zk_circom_h_checked(pp.h, _ptr(qap[0]), _ptr(qap[1]), _ptr(qap[2]), log2_m, mk, seed, h.ptr,
+                                         _ptr(rep.status), _ptr(rep.errpos), _ptr(rep.summary_d), stream))
+    return h, rep
 
 
 def deal_masks(pp, nproofs, log2_m, g1_gen_affine, g2_gen_affine, seed, masks_ct, stream=None):

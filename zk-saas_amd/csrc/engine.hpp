@@ -431,8 +431,20 @@ class IEngine {
   // d_msm with the king's word checked: status (host, one byte) is 0 or 2
   virtual int d_msm_checked(int group, const void* bases, const void* scalars, size_t len, const void* in_mask,
                             const void* out_mask, void* out, uint8_t* status, hipStream_t st) = 0;
+  // zk_pss_repair_batch: pss_repair of nitems matrices, item_stride elements apart, with one scan and one decoder launch
+  virtual int pss_repair_batch(void* shares, size_t item_stride, int nitems, size_t nchunks, int dimension, uint8_t* status,
+                               uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
+  // circom_h with its seven king words repaired first; status / errpos [7][m/l], summary [7][3 + n] (engine_gao.inc.hpp)
+  virtual int circom_h_checked(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
+                               uint64_t seed, void* h, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                               hipStream_t st) = 0;
+  // groth16_prove on the checked h chain; the report as circom_h_checked's, complete when the call returns
+  virtual int groth16_prove_checked(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
+                                    const void* a_share, const void* ax_share, const void* r, const void* s, int log_m,
+                                    const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                                    uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
                             const void* a_share, const void* ax_share, const void* r, const void* s, int log_m,
                             const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,

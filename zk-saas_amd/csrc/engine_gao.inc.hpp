@@ -28,6 +28,31 @@
     return gao_repair_run<FrP>(this, ws(st)->hwork, l, shares, nchunks, dimension, status, errpos, summary, st);
   }
 
+  // ---------------------------------------------------------------- zk_pss_repair_batch
+  // nitems matrices [n][nchunks], item i at shares + i * item_stride (KingBatch::stride; circom_h's W0 / W1): pss_repair of
+  // each, with ONE clear, ONE scan launch (the item on grid.y) and ONE decoder launch over one list of dirty (item, chunk)
+  // entries.  status / errpos [nitems][nchunks], summary [nitems][3 + n].  A refusal writes nothing.
+  static_assert(GAO_BATCH_MAX == KING_BATCH, "a repair batch takes the items of a king batch");
+  int repair_batch_check(const void* shares, size_t item_stride, int nitems, size_t nchunks, int dimension,
+                         const uint8_t* status) {
+    if (nitems < 1 || nitems > KING_BATCH) return fail(ZK_ERR_BAD_INPUT, "bad repair batch");
+    if (dimension < 1 || dimension > n - 1) return fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
+    if (nchunks == 0) return ZK_OK;
+    if (!shares || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (!gao_batch_fits((uint64_t)nitems, nchunks)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
+    if (item_stride < (size_t)n * nchunks) return fail(ZK_ERR_BAD_INPUT, "item stride below n * nchunks");
+    return ZK_OK;
+  }
+  int pss_repair_batch(void* shares, size_t item_stride, int nitems, size_t nchunks, int dimension, uint8_t* status,
+                       uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    int rc = repair_batch_check(shares, item_stride, nitems, nchunks, dimension, status);
+    if (rc || !nchunks) return rc;
+    DevBuf& wk = ws(st)->hwork;
+    ZK_HIP(wk.ensure(gao_batch_work_bytes(n, nitems, nchunks)));
+    return gao_repair_batch_run<FrP>(this, wk.p, l, shares, item_stride, nitems, nchunks, dimension, status, errpos, summary,
+                                     st);
+  }
+
   // ---------------------------------------------------------------- checked king rounds (all n parties)
   // Each repairs the word the king receives, then runs the unchecked king launch on the repaired matrix.  A failed chunk is
   // no error return: its shares go to the king as received and the caller reads summary[2].

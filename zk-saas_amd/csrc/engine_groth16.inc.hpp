@@ -59,6 +59,100 @@
                       mk ? (const Fr*)mk->degred_out : nullptr, st, 0, 0, W0 + per, W0 + 2 * per);
   }
 
+  // ---------------------------------------------------------------- the checked h chain (zk_circom_h_checked)
+  // circom_h with each of its seven king words repaired before the king reads it.  Items 0..2: the d_ifft words of a, b, c;
+  // 3..5: the d_fft words; 6: the deg_red word.  The words are those of the single-word checked calls (engine_gao.inc.hpp
+  // d_fft_checked, deg_red_checked; ext_wit.rs:127-179): fft1(x) / m + in_mask (without a mask fft1(x), the 1 / m in the
+  // king's table), fft1(x) + in_mask, a*b - c + in_mask.  Each is materialised in W0 / W1, so the kings run with null
+  // in-masks; a round's three words are repaired by ONE pss_repair_batch.  Item 6 has dimension 4l - 1: detection only.
+  // The repair's working memory lies behind the six vectors of the work buffer.
+  struct HReport {
+    uint8_t* status;        // [7][m/l]
+    uint32_t* errpos;       // [7][m/l] or null
+    uint64_t* summary;      // [7][3 + n] or null
+  };
+  // the words of a round in place: W + k * per is fft1 of vector k; masked[k]: item k has an in-mask
+  int h_round_words(Fr* W, const zk_groth16_masks* mk, int first, int log_m, int inverse, size_t per, bool* masked,
+                    hipStream_t st) {
+    int nm = 0, rc;
+    for (int k = 0; k < 3; k++) nm += masked[k] = mk && mk->fft_in[first + k];
+    if (inverse && nm) {
+      const Fr minv = Fr::from_u64((uint64_t)1 << log_m).inverse();
+      if (nm == 3) {
+        if ((rc = vec_scale(W, &minv, 3 * per, st))) return rc;
+      } else {
+        for (int k = 0; k < 3; k++)
+          if (masked[k] && (rc = vec_scale(W + k * per, &minv, per, st))) return rc;
+      }
+    }
+    for (int k = 0; k < 3; k++)
+      if (masked[k] && (rc = vec_add(W + k * per, mk->fft_in[first + k], per, st))) return rc;
+    return ZK_OK;
+  }
+  // king3 on materialised words: no in-masks, so one batched launch unless the 1 / m is in some words and not in others
+  int king3_checked(const Fr* in, const zk_groth16_masks* mk, int first, int log_m, int inverse, const void* g, int rearrange,
+                    uint64_t seed, Fr* out, size_t per, const bool* masked, hipStream_t st) {
+    const Fr* U = nullptr;
+    int rc = umat_for(nullptr, n, &U);
+    if (rc) return rc;
+    KingBatch<Fr> kb{};
+    kb.stride = per;
+    for (int k = 0; k < 3; k++) kb.out_mask[k] = mk ? (const Fr*)mk->fft_out[first + k] : nullptr;
+    if (!inverse || (masked[0] == masked[1] && masked[1] == masked[2]))
+      return king_dispatch_batch(in, kb, 3, n, log_m, inverse, U, g, inverse && !masked[0] ? 1 : 0, rearrange, seed, out, false,
+                                 st);
+    for (int k = 0; k < 3; k++) {
+      rc = king_dispatch(in + k * per, nullptr, n, log_m, inverse, U, g, masked[k] ? 0 : 1, rearrange, seed + k, out + k * per,
+                         kb.out_mask[k], false, st);
+      if (rc) return rc;
+    }
+    return ZK_OK;
+  }
+  int circom_h_checked(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* mk, uint64_t seed,
+                       void* h, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, h, HReport{status, errpos, summary}, ws(st)->hwork, st);
+  }
+  int circom_h_checked_ws(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* mk, uint64_t seed,
+                          void* h, const HReport& rep, DevBuf& hwork, hipStream_t st) {
+    int log_l = ilog2(l);
+    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
+    if (!qa || !qb || !qc || !h || !rep.status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
+    if (!gao_batch_fits(3, Lc)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
+    const size_t vec_bytes = 6 * per * sizeof(Fr);
+    static_assert(sizeof(Fr) % 32 == 0, "the repair's working memory stays aligned behind the vectors");
+    ZK_HIP(hwork.ensure(vec_bytes + gao_batch_work_bytes(n, 3, Lc)));
+    Fr* W0 = (Fr*)hwork.p;
+    Fr* W1 = W0 + 3 * per;
+    void* gwk = (char*)hwork.p + vec_bytes;
+    auto repair = [&](Fr* W, int first, int items, int dimension) {
+      return gao_repair_batch_run<FrP>(this, gwk, l, W, per, items, Lc, dimension, rep.status + first * Lc,
+                                       rep.errpos ? rep.errpos + first * Lc : nullptr,
+                                       rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr, st);
+    };
+    Fr w2m = root_of_unity(log_m + 1);
+    bool masked[3];
+    // round 1: 3 x d_ifft(rearrange = true, g = w_2m)   (ext_wit.rs:127-159)
+    int rc = fft1_src(W0, log_m, 1, 3 * (size_t)n, nullptr, st,
+                      NttSrc<Fr>{{(const Fr*)qa, (const Fr*)qb, (const Fr*)qc}, (uint32_t)n});
+    if (rc) return rc;
+    if ((rc = h_round_words(W0, mk, 0, log_m, 1, per, masked, st))) return rc;
+    if ((rc = repair(W0, 0, 3, 2 * l))) return rc;
+    if ((rc = king3_checked(W0, mk, 0, log_m, 1, &w2m, 1, seed, W1, per, masked, st))) return rc;
+    // round 2: 3 x d_fft(rearrange = false)             (ext_wit.rs:161-170)
+    if ((rc = fft1(W1, log_m, 0, 3 * (size_t)n, nullptr, st))) return rc;
+    if ((rc = h_round_words(W1, mk, 3, log_m, 0, per, masked, st))) return rc;
+    if ((rc = repair(W1, 3, 3, 2 * l))) return rc;
+    if ((rc = king3_checked(W1, mk, 3, log_m, 0, nullptr, 0, seed + 3, W0, per, masked, st))) return rc;
+    // a*b - c + in_mask, then deg_red               (ext_wit.rs:173-179)
+    // (into W1, which the second king has read: the kernel's pointers do not alias)
+    if ((rc = vec_mul_sub(W1, W0, W0 + per, W0 + 2 * per, per, st))) return rc;
+    if (mk && mk->degred_in && (rc = vec_add(W1, mk->degred_in, per, st))) return rc;
+    if ((rc = repair(W1, 6, 1, 4 * l - 1))) return rc;
+    return deg_red_np(W1, nullptr, nullptr, n, Lc, seed + 6, (Fr*)h, mk ? (const Fr*)mk->degred_out : nullptr, st);
+  }
+
   // circom_h of `nb` proofs as ONE launch chain (zk_groth16_prove_batch): the 3 nb vectors go through every NTT pass,
   // king and deg_red launch together (grid.y), so the chain's dozen dependent launches are paid once per batch.
   // q*[b]: [n][Lc]; mk: nb mask sets or nullptr; h: [nb][n][Lc]; proof b draws the randomness a single circom_h with
@@ -428,11 +522,11 @@
   int prove_begin(ProveJob& j, const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
                   const void* a_share, const void* ax_share, const Fr& r, const Fr& s, int log_m,
                   const zk_groth16_masks* mk, uint64_t seed, bool full, int first, int count, hipStream_t st,
-                  bool gate_sorts = false) {
+                  bool gate_sorts = false, const HReport* report = nullptr) {
     if (j.active) return fail(ZK_ERR_BAD_INPUT, "a proof is already in flight on this slot");
     j.sharded = false;
     int rc = prove_begin_impl(j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, full, first, count, st,
-                              gate_sorts);
+                              gate_sorts, report);
     return rc && j.active ? bail(j, rc) : rc;
   }
   // the gate of a proof's U-MSM: its sort is event 3 of the "all sorts first" barrier (prove_begin_impl)
@@ -447,7 +541,7 @@
   int prove_begin_impl(ProveJob& j, const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
                        const void* a_share, const void* ax_share, const Fr& r, const Fr& s, int log_m,
                        const zk_groth16_masks* mk, uint64_t seed, bool full, int first, int count, hipStream_t st,
-                       bool gate_sorts) {
+                       bool gate_sorts, const HReport* report = nullptr) {
     if (!Cfg::HAS_G2) return fail(ZK_ERR_BAD_INPUT, "G2 is not available for this curve");
     auto t_mark = std::chrono::steady_clock::now();
     auto host_span = [&](int slot) {                 // host:launch.* (zk_profile_read)
@@ -508,11 +602,17 @@
       if (g.n_wait_sorted) g.sorted_ev = J->ev_role[role];
       return g;
     };
+    // report (zk_groth16_prove_checked): the checked h chain on the same stream with the same work buffers, its report into
+    // the caller's buffers -- complete once the job's join has waited for the U chain; nothing else of the proof differs
+    auto h_chain = [&](hipStream_t hs) {
+      if (report) return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, *report, J->hwork, hs);
+      return circom_h_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, J->hwork, hs);
+    };
     bool hu_done = false;
     if (full && gated) {
       hipError_t he = j.hshare.ensure((size_t)n * Lc * sizeof(Fr));
       if (he != hipSuccess) return hip_fail(he, "h share buffer");
-      rc = circom_h_ws(qa, qb, qc, log_m, mk, seed, j.hshare.p, j.hwork, streams_[5]);
+      rc = h_chain(streams_[5]);
       if (rc) return rc;
       rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
                                       msm_.coef_d_, crs->len_u, streams_[5], &j.msm[ROLE_U], nullptr, u_gate(j));
@@ -539,7 +639,7 @@
       hipStream_t hs = streams_[5];
       hipError_t he = j.hshare.ensure((size_t)n * Lc * sizeof(Fr));
       if (he != hipSuccess) return hip_fail(he, "h share buffer");
-      rc = circom_h_ws(qa, qb, qc, log_m, mk, seed, j.hshare.p, j.hwork, hs);
+      rc = h_chain(hs);
       if (rc) return rc;
       host_span(PROF_HOST_H);
       rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
@@ -708,16 +808,34 @@
     if (prof.on) prof.host_add(PROF_HOST_LAUNCH, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return groth16_wait(h, pi_a, pi_b, pi_c);
   }
+  // zk_groth16_prove_checked: the proof above with circom_h's seven king words checked (circom_h_checked_ws).  The five d_msm
+  // rounds stay unchecked.  Synchronous: the join orders the report buffers.
+  int groth16_prove_checked(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
+                            const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk,
+                            uint64_t seed, void* pi_a, void* pi_b, void* pi_c, uint8_t* status, uint32_t* errpos,
+                            uint64_t* summary, hipStream_t st) override {
+    if (!pi_a || !pi_b || !pi_c || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    const HReport report{status, errpos, summary};
+    int h = -1;
+    int rc = prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, &h, &report);
+    if (rc) return rc;
+    return groth16_wait(h, pi_a, pi_b, pi_c);
+  }
   int groth16_prove_async(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
                           const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk,
                           uint64_t seed, hipStream_t st, int* handle) override {
+    return prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, handle, nullptr);
+  }
+  int prove_start(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
+                  const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk, uint64_t seed,
+                  hipStream_t st, int* handle, const HReport* report) {
     int rc = check_prove_args(crs, r_, s_, log_m);
     if (rc) return rc;
     if (!qa || !qb || !qc || !a_share || !ax_share || !handle) return fail(ZK_ERR_BAD_INPUT, "null pointer");
     ProveJob* j = free_job(jobs_);
     if (!j) return fail(ZK_ERR_BAD_INPUT, "too many proofs in flight (zk_groth16_wait one first)");
     Fr r = Fr::from_limbs((const uint32_t*)r_), s = Fr::from_limbs((const uint32_t*)s_);
-    rc = prove_begin(*j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, true, 0, n, st);
+    rc = prove_begin(*j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, true, 0, n, st, false, report);
     if (rc) return rc;
     *handle = j->slot;
     return ZK_OK;

@@ -494,9 +494,36 @@ ZK_HD void gao_repair_word_parties(const G& g, const GaoResult<F, G, true>& r, R
   gao_repair_word<F, G>(g, r, [&](int p, const F& v) { put(p, row(p), v * ilam(p)); });
 }
 
+// ---------------------------------------------------------------- a batch of words (zk_pss_repair_batch)
+// Item i is a share matrix [n][nchunks] at shares + i * item_stride.  The items share ONE list of dirty chunks: an entry names
+// (item, chunk) as item * nchunks + chunk in 32 bits -- also the index of the chunk in status and errpos [nitems][nchunks].
+constexpr int GAO_BATCH_MAX = 48;      // KING_BATCH (pss.hpp): the items of one king launch
+// the refusal: every entry fits 32 bits
+ZK_HD bool gao_batch_fits(uint64_t nitems, uint64_t nchunks) {
+  return nitems >= 1 && nitems <= (uint64_t)GAO_BATCH_MAX && nchunks < ((uint64_t)1 << 32) &&
+         nitems * nchunks < ((uint64_t)1 << 32);
+}
+ZK_HD uint32_t gao_batch_entry(uint32_t item, uint32_t chunk, uint32_t nchunks) { return item * nchunks + chunk; }
+ZK_HD void gao_batch_decode(uint32_t entry, uint32_t nchunks, uint32_t& item, uint32_t& chunk) {
+  item = entry / nchunks;
+  chunk = entry - item * nchunks;
+}
+// Working memory of a batch: [0] the count of dirty chunks, shared; from byte 32 the summary words of the items, (3 + n) each,
+// when the caller passes none; the list behind this head.
+constexpr size_t gao_batch_head(int n, int nitems) { return (32 + (size_t)nitems * (3 + n) * 8 + 31) / 32 * 32; }
+constexpr size_t gao_batch_work_bytes(int n, int nitems, size_t nchunks) {
+  return gao_batch_head(n, nitems) + (size_t)nitems * nchunks * 4;
+}
+
 #if defined(__HIPCC__)
 class IEngine;
 struct DevBuf;
+// zk_pss_repair_batch: nitems share matrices [n][nchunks], item_stride elements apart, in place; status and errpos
+// [nitems][nchunks], summary [nitems][3 + n] or null.  wk: working memory of gao_batch_work_bytes(4 l, nitems, nchunks) bytes
+// that the caller holds (behind the words of a chain, for instance); the argument checks are the caller's (engine_gao.inc.hpp).
+template <class FrP>
+int gao_repair_batch_run(IEngine* e, void* wk, int l, void* shares, size_t item_stride, int nitems, size_t nchunks,
+                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
 // zk_pss_unpack_robust over the scalar field FrP (engine_gao.inc.hpp has the argument list); wk: working memory
 template <class FrP>
 int gao_unpack_robust_run(IEngine* e, DevBuf& wk, int l, const void* shares, size_t nchunks, int dimension, void* secrets,

@@ -1,4 +1,4 @@
-// Kernels and host drivers of zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair and zk_pss_repair_parties (gao.hpp says what they compute).  Included
+// Kernels and host drivers of zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair, zk_pss_repair_parties and zk_pss_repair_batch (gao.hpp says what they compute).  Included
 // by gao_<curve>.hip only.  Each stage is one body with two kernels: the all-parties one, and the one for a party list (ER).
 //   stage 1  one lane per chunk (two at l = 8): the n shares are loaded once, transformed in registers, coefficients k .. n - 1 tested; a
 //            clean chunk gets its secrets (and message) and status 0, a dirty one is appended to a compact list
@@ -71,12 +71,14 @@ struct GaoWork {
 // SCAN: the inverse transform and the test only -- status and errpos of a clean chunk, the list of the dirty ones, no secrets
 // and no message: 1 / 5 / 17 products per chunk at l = 1, 2, 4; at l = 8 the two lanes' 17 each and the 15 of the split.
 // SCAN with ER (zk_pss_repair_parties): listed -- bit p: party p is listed; its row is the number of listed parties below it.
+// entry0: the list entry of this item's chunk 0 (gao_batch_entry; zk_pss_repair_batch), 0 for a single word.
 template <class P, int L, bool ER, bool SCAN = false>
 __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const Fp<P>* __restrict__ shares, size_t nchunks,
                                                 int k, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
                                                 uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, const GaoWork& wk,
                                                 const GaoAbsentLoad<Fp<P>>* ab, int rho,
-                                                const GaoAbsent<Fp<P>>* __restrict__ tab, uint32_t listed = 0) {
+                                                const GaoAbsent<Fp<P>>* __restrict__ tab, uint32_t listed = 0,
+                                                uint32_t entry0 = 0) {
   using F = Fp<P>;
   constexpr int N = 4 * L, SP = gao_split(L), M = N / SP;
   const int kd = ER ? k + rho : k;       // the dimension the word is tested and evaluated at
@@ -158,7 +160,7 @@ __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const
     if (in_wg > wg_dirty) atomicAdd(wk.summary, (unsigned long long)(in_wg - wg_dirty));
   }
   __syncthreads();
-  if (dirty) wk.list[wg_base + wave_off + rank] = (uint32_t)j;
+  if (dirty) wk.list[wg_base + wave_off + rank] = entry0 + (uint32_t)j;
 }
 template <class P, int L>
 __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
@@ -180,6 +182,19 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_scan_parties_kernel(const Gao
                                                                       uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage1_body<P, L, true, true>(c, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, &ab, rho, nullptr, listed);
 }
+// zk_pss_repair_batch: the scan of item blockIdx.y -- its matrix, its rows of status and errpos, its summary words; the count
+// and the list are the batch's
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_scan_batch_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
+                                                                    size_t item_stride, size_t nchunks, int k,
+                                                                    uint8_t* __restrict__ status,
+                                                                    uint32_t* __restrict__ errpos, GaoWork wk) {
+  const uint32_t item = blockIdx.y;
+  wk.summary += (size_t)item * (3 + 4 * L);
+  gao_stage1_body<P, L, false, true>(c, shares + item * item_stride, nchunks, k, nullptr, nullptr, status + item * nchunks,
+                                     errpos ? errpos + item * nchunks : nullptr, wk, nullptr, 0, nullptr, 0,
+                                     gao_batch_entry(item, 0, (uint32_t)nchunks));
+}
 // k: the caller's dimension
 template <class P, int L>
 __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
@@ -195,16 +210,26 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
 // REPAIR: `shares` is written: lane p stores its re-encoding h(w_n^p) when bit p of the final errpos is set; no secrets, no
 // message (the decoder's flag RE).  With ER the store is h'(w^p) / Lambda(w^p) into the party's row; ilam: the device table of
 // the inverses, read at a run-time index by a lane that stores
+// BATCH (zk_pss_repair_batch): a list entry names (item, chunk) and is the chunk's index in status and errpos; the item's matrix
+// is at shares + item * item_stride and its summary words at wk.summary + item * (3 + n), added to chunk by chunk -- the
+// entries of a lane's walk belong to any items in any order
 template <class P, bool REPAIR>
 using GaoSharesPtr = std::conditional_t<REPAIR, Fp<P>*, const Fp<P>* __restrict__>;
-template <class P, bool ER, bool REPAIR = false>
+template <class P>
+struct GaoBatchItem {
+  Fp<P>* sh;
+  size_t chunk;
+  unsigned long long* sum;
+};
+template <class P, bool ER, bool REPAIR = false, bool BATCH = false>
 __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n, int l, GaoSharesPtr<P, REPAIR> shares,
                                                 size_t nchunks, int k, Fp<P>* __restrict__ secrets,
                                                 Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
                                                 uint32_t* __restrict__ errpos, const GaoWork& wk,
                                                 const GaoAbsent<Fp<P>>* __restrict__ tab,
-                                                const Fp<P>* __restrict__ ilam = nullptr) {
+                                                const Fp<P>* __restrict__ ilam = nullptr, size_t item_stride = 0) {
   using F = Fp<P>;
+  static_assert(!BATCH || (REPAIR && !ER), "the batch is the all-parties repair");
   const uint32_t cnt = *wk.count;
   const uint32_t gpb = GAO_THREADS / n, stride = gridDim.x * gpb;
   if (blockIdx.x * gpb >= cnt) return;
@@ -224,9 +249,20 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
   for (uint32_t first = blockIdx.x * gpb; first < cnt; first += stride) {       // (uniform over the workgroup)
     const uint32_t gi = first + threadIdx.x / n;
     const bool live = gi < cnt;
-    const size_t j = live ? wk.list[gi] : 0;
+    const size_t j = live ? wk.list[gi] : 0;       // BATCH: the entry -- the chunk's index in status and errpos
+    // BATCH: the item's matrix, the chunk in it, the item's summary words
+    [[maybe_unused]] const auto it = [&] {
+      if constexpr (BATCH) {
+        uint32_t item, chunk;
+        gao_batch_decode((uint32_t)j, (uint32_t)nchunks, item, chunk);
+        return GaoBatchItem<P>{shares + item * item_stride, chunk, wk.summary + (size_t)item * (3 + n)};
+      } else {
+        return 0;
+      }
+    }();
     F y;
     if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * nchunks + j) * lam : F::zero();
+    else if constexpr (BATCH) y = live ? load_elem(it.sh + (size_t)p * nchunks + it.chunk) : F::zero();
     else y = live ? load_elem(shares + (size_t)p * nchunks + j) : F::zero();
     GaoResult<F, GaoDevGroup, REPAIR> r = gao_chunk<F, GaoDevGroup, REPAIR>(g, c, n, kd, live, y, xp, xinv, sp);
     if constexpr (ER) gao_absent_finish<F, GaoDevGroup, REPAIR>(g, k, rho, listed, message != nullptr, slam, lamc, r);
@@ -235,11 +271,22 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
       gao_repair_word_parties<F, GaoDevGroup>(
           g, r, [&](int) { return row; }, [&](int lane) { return load_elem(ilam + lane); },
           [&](int, int at, const F& v) { store_elem(shares + (size_t)at * nchunks + j, v); });
+    } else if constexpr (BATCH) {
+      gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(it.sh + (size_t)lane * nchunks + it.chunk, v); });
     } else if constexpr (REPAIR) {
       gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(shares + (size_t)lane * nchunks + j, v); });
     } else {
       if (message && p < k) store_elem(message + (size_t)p * nchunks + j, r.h);
       if (secrets && p < l) store_elem(secrets + j * l + p, r.sec);
+    }
+    if constexpr (BATCH) {
+      if (p == 0) {
+        status[j] = (uint8_t)r.status;
+        if (errpos) errpos[j] = r.errpos;
+        atomicAdd(it.sum + (r.status == 1 ? 1 : 2), 1ull);
+      }
+      if ((r.errpos >> p) & 1) atomicAdd(it.sum + 3 + p, 1ull);
+      continue;
     }
     if (p == 0) {
       status[j] = (uint8_t)r.status;
@@ -266,6 +313,14 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_repair_kernel(const GaoConsts
                                                                 size_t nchunks, int k, uint8_t* __restrict__ status,
                                                                 uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage2_body<P, false, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr);
+}
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_repair_batch_kernel(const GaoConsts<Fp<P>> c, int n, int l, Fp<P>* shares,
+                                                                      size_t item_stride, size_t nchunks, int k,
+                                                                      uint8_t* __restrict__ status,
+                                                                      uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage2_body<P, false, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr, nullptr,
+                                        item_stride);
 }
 // k: the caller's dimension
 template <class P>
@@ -365,6 +420,36 @@ template <class FrP>
 int gao_repair_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, size_t nchunks, int dimension, uint8_t* status,
                    uint32_t* errpos, uint64_t* summary, hipStream_t st) {
   return gao_all_parties_run<FrP, true>(e, wkbuf, l, shares, nchunks, dimension, nullptr, nullptr, status, errpos, summary, st);
+}
+// zk_pss_repair_batch: one clear, one scan with the item on grid.y, one repair launch over the one list of all items
+template <class FrP>
+int gao_repair_batch_run(IEngine* e, void* wkp, int l, void* shares, size_t item_stride, int nitems, size_t nchunks,
+                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+  using Fr = Fp<FrP>;
+  const int n = 4 * l;
+  const size_t head = gao_batch_head(n, nitems);
+  GaoWork wk;
+  wk.count = (uint32_t*)wkp;
+  wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkp + 32);
+  wk.list = (uint32_t*)((char*)wkp + head);
+  GAO_HIP(hipMemsetAsync(wkp, 0, head, st));
+  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)nitems * (3 + n) * 8, st));
+  const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
+  const size_t per_wg = GAO_THREADS / gao_split(l);
+  const dim3 blk(GAO_THREADS), grid1((unsigned)((nchunks + per_wg - 1) / per_wg), (unsigned)nitems);
+  Fr* sh = (Fr*)shares;
+  switch (l) {
+    case 1: gao_scan_batch_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
+    case 2: gao_scan_batch_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
+    case 4: gao_scan_batch_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
+    case 8: gao_scan_batch_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
+    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
+  }
+  const size_t gpb = GAO_THREADS / n, total = (size_t)nitems * nchunks;
+  const dim3 grid2((unsigned)std::min<size_t>((total + gpb - 1) / gpb, GAO_STAGE2_GRID));
+  gao_repair_batch_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, item_stride, nchunks, dimension, status, errpos, wk);
+  GAO_HIP(hipGetLastError());
+  return ZK_OK;
 }
 // With all n parties listed this is the call above; otherwise the kernels' forms for absent parties, with the table of the
 // party list (gao_make_absent, host) put into working memory by a launch of its own ahead of them.
