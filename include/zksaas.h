@@ -652,6 +652,14 @@ int zk_groth16_batch_wait(zk_ctx* ctx, int handle, void* pi_a, void* pi_b, void*
  * once per witness): one Pippenger pass with bucket sets per scalar vector.  out: nvec Jacobian points (host). */
 int zk_msm_batch(zk_ctx* ctx, int group, const void* bases_d, size_t len, const void* const* scalars_d, int nvec,
                  void* out, void* stream);
+/* sum_i G::msm(bases_d[i] [lens[i]], scalars_d[i] [lens[i]]) for k = 1..3 MSMs over one group, as ONE Jacobian point (host).
+ * Bucket accumulation is linear: the launches whose bucket geometry (window bits and count, bucket sets, buckets per set:
+ * equal for vectors registered with the same table width, or table-free vectors of lengths the cost model gives the same
+ * window) equals the LAST vector's stop behind their bucket sums, the last launch adds their buckets to its own and ONE
+ * bucket set is reduced and folded for all of them; the others are reduced on their own and added on the host.  The full
+ * prover ends r*H + W + U this way.  shared (optional): how many of the first k - 1 launches shared the last one's set. */
+int zk_msm_sum(zk_ctx* ctx, int group, int k, const void* const* bases_d, const void* const* scalars_d, const size_t* lens,
+               void* out, int* shared, void* stream);
 /* unpack / unpack2 over GROUP elements (secret-sharing/src/pss.rs:125-166 with T = curve point; lagrange_unpack
  * :170-221 for a party subset): shares_d [nparties][nchunks] affine points of the listed parties (ascending ids, NULL =
  * 0..nparties-1) -> out_d [nchunks][l] affine.  zk_pss_unpack_points needs all n parties. */

@@ -37,6 +37,7 @@ SYMBOLS = [
     "zk_d_pp_checked",
     "zk_pss_unpack_points_robust", "zk_pss_repair_points", "zk_d_msm_checked",
     "zk_pss_repair_batch", "zk_circom_h_checked", "zk_groth16_prove_checked",
+    "zk_msm_sum",
 ]
 
 _lib = None
@@ -200,6 +201,7 @@ def load():
                                                  C.POINTER(vp), vp, vp, i32, vp, u64, vp, C.POINTER(i32)]
     lib.zk_groth16_batch_wait.argtypes = [vp, i32, vp, vp, vp]
     lib.zk_msm_batch.argtypes = [vp, i32, vp, sz, C.POINTER(vp), i32, vp, vp]
+    lib.zk_msm_sum.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), vp, C.POINTER(i32), vp]
     lib.zk_pss_unpack_points.argtypes = [vp, i32, vp, sz, vp, vp]
     lib.zk_pss_unpack2_points.argtypes = [vp, i32, vp, C.POINTER(C.c_uint32), i32, sz, vp, vp]
     lib.zk_groth16_reconstruct.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_uint32), i32, vp, vp, vp]

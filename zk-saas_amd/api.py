@@ -587,6 +587,29 @@ def msm_batch(pp, group, bases_d, scalar_vectors, length, stream=None):
     return out
 
 
+def msm_stats(pp):
+    """zk_msm_stats: the context's running counts [G1 mixed additions, G2 mixed additions, G1 (point, window) pairs offered
+    to the sorts, G2 pairs offered]."""
+    st = (C.c_uint64 * 4)()
+    pp._check(pp.lib.zk_msm_stats(pp.h, st))
+    return list(st)
+
+
+def msm_sum(pp, group, triples, stream=None, with_shared=False):
+    """zk_msm_sum: the sum of up to three MSMs [(bases_d, scalars_d, length), ...] over one group as ONE Jacobian point,
+    through one shared bucket set where the launches' geometries match.  with_shared: also how many of the first k - 1
+    launches shared the last one's bucket set."""
+    nl = pp.fq.nl * (2 if group == ZK_G2 else 1)
+    k = len(triples)
+    out = np.zeros(3 * nl, dtype=np.uint64)
+    ba = (C.c_void_p * k)(*[_ptr(t[0]) for t in triples])
+    sa = (C.c_void_p * k)(*[_ptr(t[1]) for t in triples])
+    la = (C.c_size_t * k)(*[int(t[2]) for t in triples])
+    shared = C.c_int32(0)
+    pp._check(pp.lib.zk_msm_sum(pp.h, group, k, ba, sa, la, out.ctypes.data, C.byref(shared), stream))
+    return (out, shared.value) if with_shared else out
+
+
 def unpack_points(pp, group, shares_d, nchunks, parties=None, two=True, out=None, stream=None):
     """pss.rs:125-166 over group elements: shares_d [nparties][nchunks] affine -> [nchunks][l] affine (device).
     two=False: unpack (all n parties); parties: ascending ids of the shares present (lagrange_unpack)."""

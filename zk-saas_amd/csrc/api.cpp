@@ -502,6 +502,11 @@ int zk_msm_batch(zk_ctx* ctx, int group, const void* bases_d, size_t len, const 
   CTX_OR_FAIL();
   return e->msm_batch(group, bases_d, len, scalars_d, nvec, out, S(stream));
 }
+int zk_msm_sum(zk_ctx* ctx, int group, int k, const void* const* bases_d, const void* const* scalars_d, const size_t* lens,
+               void* out, int* shared, void* stream) {
+  CTX_OR_FAIL();
+  return e->msm_sum(group, k, bases_d, scalars_d, lens, out, shared, S(stream));
+}
 int zk_pss_unpack_points(zk_ctx* ctx, int group, const void* shares_d, size_t nchunks, void* out_d, void* stream) {
   CTX_OR_FAIL();
   return e->pss_unpack_points(group, shares_d, nullptr, e->n, nchunks, 0, out_d, S(stream));

@@ -345,6 +345,8 @@ class IEngine {
   virtual int groth16_batch_wait(int handle, void* pi_a, void* pi_b, void* pi_c) = 0;
   virtual int msm_batch(int group, const void* bases, size_t len, const void* const* scalars, int nb, void* out,
                         hipStream_t st) = 0;
+  virtual int msm_sum(int group, int k, const void* const* bases, const void* const* scalars, const size_t* lens, void* out,
+                      int* shared, hipStream_t st) = 0;
   virtual int groth16_abort(int handle) = 0;
   virtual int deg_red_points(int group, const void* x, const void* in_mask, const void* out_mask, size_t len,
                              const void* gen_affine, uint64_t seed, void* out, hipStream_t st) = 0;

@@ -245,7 +245,9 @@
     bool has_mk = false, r_zero = false, full = true;
     int first = 0, count = 0;
     Fr r, s;
-    P1 S, H, W, U, sS, rH;
+    P1 S, H, W, U, sS, rH;                          // (a full proof whose H and W launches donate their buckets to U's --
+                                                    // prove_begin_impl "one bucket set for C" -- leaves H, W and rH the
+                                                    // identity and U holds T = r*H + W + U)
     P2 V0;
     P1 rN, sK, rsM, s_cA, r_cB1;
     P2 sK2;
@@ -271,9 +273,12 @@
     hipEvent_t ev_in = nullptr;                     // orders the job's streams behind the caller's
     hipEvent_t ev_role[NROLES] = {};                // by MsmRole: behind the sort (a proof's "all sorts first" barrier,
                                                     // prove_begin_impl) or behind the accumulate kernel (a batch's chain)
+    hipEvent_t ev_don = nullptr;                    // behind the finalize kernel of the S+H launch when H's buckets are donated
+    std::atomic<int> don_flag[2] = {};              // the S+H / W launch has donated (1) or failed (-1): MsmShare::from_flag
     explicit JobCore(bool batch) : is_batch(batch) {}
     ~JobCore() {
       if (ev_in) (void)hipEventDestroy(ev_in);
+      if (ev_don) (void)hipEventDestroy(ev_don);
       for (hipEvent_t e : ev_role)
         if (e) (void)hipEventDestroy(e);
     }
@@ -324,6 +329,7 @@
   // every handle is checked on its own: a failure half-way leaves the rest to be created by the next call
   int ensure_events(JobCore& c) {
     if (!c.ev_in) ZK_HIP(hipEventCreateWithFlags(&c.ev_in, hipEventDisableTiming));
+    if (!c.ev_don) ZK_HIP(hipEventCreateWithFlags(&c.ev_don, hipEventDisableTiming));
     for (hipEvent_t& e : c.ev_role)
       if (!e) ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return ZK_OK;
@@ -349,6 +355,13 @@
     return q == hipSuccess ? "done" : (q == hipErrorNotReady ? "PENDING" : hipGetErrorString(q));
   }
   MsmSlot& job_slot(const JobCore& c, int role) { return msm_.slots_[c.ws0 + role]; }
+  // Slots whose launches donated buckets to the job's U launch stay busy beyond their own event (MsmSlot::lent): they are
+  // released here, once the U chain has been waited for (or was never enqueued) and the job's pool tasks are joined.
+  void release_loans(JobCore& c) {
+    if (job_slot(c, ROLE_U).busy) return;
+    for (int r : {(int)ROLE_SH, (int)ROLE_W})
+      if (job_slot(c, r).lent) (void)job_slot(c, r).release_loan(this);
+  }
   // once the job's tasks are joined, a busy slot is a wait that expired: its work may still run
   bool busy(const JobCore& c) {
     for (int r = 0; r < NROLES; r++)
@@ -383,6 +396,8 @@
     // a proof's tasks waiting at the sort barrier go on (and fail or finish); a batch's gates are always raised (msm_task)
     if (!c.is_batch) static_cast<ProveJob&>(c).sorted_cnt.fetch_add(1 << 20, std::memory_order_release);
     bool ok = drain(c);
+    ok = ok && job_slot(c, ROLE_U).wait(this) != hipErrorNotReady;
+    if (ok) release_loans(c);
     for (int r = 0; r < NROLES; r++) ok = ok && job_slot(c, r).wait(this) != hipErrorNotReady;
     if (!ok) {
       dump("abort", "work of the job is still pending after the deadline", c);
@@ -417,6 +432,7 @@
     const bool expired = rc && job_slot(c, ROLE_U).busy;
     if (expired) dump(who, "the U-MSM chain did not finish within the deadline", c);
     if (int rd = drain_or_wedge(c, who)) return rd;
+    release_loans(c);
     if (busy(c)) {                        // a chain's event did not signal within the deadline: nothing may be reused
       if (!expired) dump(who, "an MSM chain did not finish within the deadline", c);
       return wedge(expired ? keep.msg : std::string(last.msg));
@@ -468,8 +484,10 @@
   template <class Fld, class Then>
   void msm_task(JobCore& c, MsmRole role, const void* bases, const void* bases2, const void* scal, const MsmBatchArg* batch,
                 size_t npts, const Fr* coef, size_t plen, hipStream_t stream, const MsmGate& gate, std::atomic<int>* raise,
-                Then then) {
+                Then then, const MsmShare<Fr>* share = nullptr, std::atomic<int>* donated = nullptr) {
     JobCore* C = &c;
+    const bool shared = share != nullptr;
+    const MsmShare<Fr> sh = shared ? *share : MsmShare<Fr>{};
     const int dev = device;
     const bool batched = batch != nullptr;
     const MsmBatchArg ba = batched ? *batch : MsmBatchArg{};
@@ -477,7 +495,8 @@
       (void)hipSetDevice(dev);
       MsmPending* pend = &C->msm[role];
       int rc2 = msm_.template launch_t<Fld>(this, C->ws0 + role, bases, scal, npts, coef, plen, stream, pend, bases2, gate,
-                                            batched ? &ba : nullptr);
+                                            batched ? &ba : nullptr, shared ? &sh : nullptr);
+      if (donated) donated->store(rc2 ? -1 : 1, std::memory_order_release);      // (the U launch may be waiting for it)
       if (raise) raise->store(1, std::memory_order_release);
       else if (rc2 && gate.sorted_cnt) gate.sorted_cnt->fetch_add(1, std::memory_order_release);
       XYZZ<Fld> res[2 * MSM_MAXB];
@@ -608,6 +627,34 @@
       if (report) return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, *report, J->hwork, hs);
       return circom_h_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, J->hwork, hs);
     };
+    // ---- one bucket set for C.  C needs r*H + W + U only as a sum, and bucket accumulation is linear: where the launches
+    // of H (the second vector of the S+H launch), W and U have the same bucket geometry -- with the registered SHA-256 CRS
+    // all three use one set of 2^14 buckets -- H runs with r * coef_p as its coefficients, H and W stop behind their
+    // finalize kernels and U's finalize kernel adds their buckets to its own (msm.hpp "SHARED BUCKET SET"): three bucket
+    // sets are reduced and folded per proof instead of five and r*H costs no host multiplication.  Each of H and W shares
+    // when ITS geometry equals U's (a table on one vector only, other "msm_table_c", table-free vectors of other lengths:
+    // that launch is reduced on its own as before).  Not with the "all sorts first" order of large domains, where U is
+    // enqueued ahead of the witness launches it would have to wait for on the host.
+    const void* hd = j.pt.r_zero ? nullptr : crs->h_d;
+    bool don_h = false, don_w = false;
+    if (full && !gated) {
+      MsmGeo gu, gd;
+      if (msm_.template geometry<Fq_>(crs->u_d, nullptr, (size_t)n * crs->len_u, &gu)) {
+        don_h = hd && msm_.template geometry<Fq_>(crs->s_d, hd, (size_t)count * cstride, &gd) && gd == gu;
+        don_w = msm_.template geometry<Fq_>(crs->w_d, nullptr, (size_t)count * crs->len_w, &gd) && gd == gu;
+      }
+    }
+    for (auto& f : j.don_flag) f.store(0, std::memory_order_relaxed);
+    MsmShare<Fr> sh_h, sh_w, sh_u;
+    if (don_h) {
+      sh_h.keep = 1, sh_h.donated_ev = j.ev_don;
+      sh_h.scale1_on = true, sh_h.scale1 = r;
+      sh_u.from[sh_u.n_absorb] = &j.msm[ROLE_SH], sh_u.from_vec[sh_u.n_absorb] = 1, sh_u.from_flag[sh_u.n_absorb++] = &j.don_flag[0];
+    }
+    if (don_w) {
+      sh_w.keep = 0;
+      sh_u.from[sh_u.n_absorb] = &j.msm[ROLE_W], sh_u.from_vec[sh_u.n_absorb] = 0, sh_u.from_flag[sh_u.n_absorb++] = &j.don_flag[1];
+    }
     bool hu_done = false;
     if (full && gated) {
       hipError_t he = j.hshare.ensure((size_t)n * Lc * sizeof(Fr));
@@ -623,11 +670,13 @@
                    role_gate(ROLE_V), nullptr, [this, J](const P2* res) { take_V(*J, res); });
     // S and H multiply two base vectors by the same witness shares: ONE launch over both vectors, each with its own sort
     // (their identity bases differ: b_query is the identity for every wire no B-row mentions, 59 % in the SHA-256 circuit)
-    const void* hd = j.pt.r_zero ? nullptr : crs->h_d;
+    const bool fold_h = hd != nullptr && !don_h;
     msm_task<Fq_>(j, ROLE_SH, crs->s_d, hd, a_share, nullptr, (size_t)count * cstride, cf, cstride, streams_[0],
-                  role_gate(ROLE_SH), nullptr, [this, J, hd](const P1* res) { take_SH(*J, res, hd != nullptr); });
+                  role_gate(ROLE_SH), nullptr, [this, J, fold_h](const P1* res) { take_SH(*J, res, fold_h); },
+                  don_h ? &sh_h : nullptr, don_h ? &j.don_flag[0] : nullptr);
     msm_task<Fq_>(j, ROLE_W, crs->w_d, nullptr, ax_share, nullptr, (size_t)count * crs->len_w, cf, crs->len_w, streams_[3],
-                  role_gate(ROLE_W), nullptr, [this, J](const P1* res) { take_W(*J, res); });
+                  role_gate(ROLE_W), nullptr, [this, J](const P1* res) { take_W(*J, res); },
+                  don_w ? &sh_w : nullptr, don_w ? &j.don_flag[1] : nullptr);
     // (the host terms are two dozen pool submissions: behind circom_h's launches when those are still to come -- they
     // are the head of the proof's longest chain and the terms are not needed before prove_end)
     if (!(full && !hu_done)) submit_host_terms(&j.pt, j.fut);
@@ -643,7 +692,8 @@
       if (rc) return rc;
       host_span(PROF_HOST_H);
       rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
-                                      msm_.coef_d_, crs->len_u, hs, &j.msm[ROLE_U]);
+                                      msm_.coef_d_, crs->len_u, hs, &j.msm[ROLE_U], nullptr, MsmGate{}, nullptr,
+                                      sh_u.n_absorb ? &sh_u : nullptr);
       if (rc) return rc;
       submit_host_terms(&j.pt, j.fut);
       host_span(PROF_HOST_U);

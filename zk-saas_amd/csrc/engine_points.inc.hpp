@@ -9,6 +9,11 @@
     }
     return msm_.run(this, group, bases, scalars, nb, out, st);
   }
+  // zk_msm_sum: the sum of up to three MSMs as one point, through one shared bucket set where their geometries match
+  int msm_sum(int group, int k, const void* const* bases, const void* const* scalars, const size_t* lens, void* out,
+              int* shared, hipStream_t st) override {
+    return msm_.sum(this, group, k, bases, scalars, lens, out, shared, st);
+  }
   int d_msm(int group, const void* bases, const void* scalars, size_t len, const void* in_mask, const void* out_mask,
             void* out, hipStream_t st) override {
     return msm_.d_msm(this, group, bases, scalars, len, in_mask, out_mask, out, st);

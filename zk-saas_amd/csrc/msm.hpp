@@ -57,7 +57,9 @@ constexpr int ws_job(int j, int r) { return j * NROLES + r; }
 constexpr int ws_batch(int b, int r) { return (NJOBS + b) * NROLES + r; }
 constexpr int ws_dist(int sid) { return (NJOBS + NBATCH) * NROLES + sid; }
 constexpr int WS_STANDALONE = ws_dist(NET_NSID);
-constexpr int MSM_WS = WS_STANDALONE + 1;
+constexpr int WS_SUM = WS_STANDALONE + 1;      // the donors of zk_msm_sum (its absorbing launch runs on WS_STANDALONE)
+constexpr int MSM_SUM_MAX = 3;                 // most MSMs of one zk_msm_sum
+constexpr int MSM_WS = WS_SUM + MSM_SUM_MAX - 1;
 constexpr bool msm_ws_disjoint() {
   int uses[MSM_WS] = {};
   for (int r = 0; r < NROLES; r++) {
@@ -66,6 +68,7 @@ constexpr bool msm_ws_disjoint() {
   }
   for (int s = 0; s < NET_NSID; s++) uses[ws_dist(s)]++;
   uses[WS_STANDALONE]++;
+  for (int d = 0; d < MSM_SUM_MAX - 1; d++) uses[WS_SUM + d]++;
   for (int u : uses)
     if (u != 1) return false;
   return true;
@@ -113,6 +116,14 @@ struct MsmBaseId {
   const void* b1 = nullptr;   // second base vector of the launch (own sort when ys != 0: blockIdx.y picks the vector)
   uint32_t elem16 = 0;        // bytes per affine point / 16
 };
+// Two base vectors with a sort each (ys != 0): the scalars of the SECOND vector may carry one more factor -- the prover
+// multiplies b_g1_query by r times the witness (engine_groth16.inc.hpp prove_begin_impl) -- applied where the sort makes
+// the scalar canonical anyway: one more field multiplication per point of that vector.
+template <class F>
+struct MsmScale1 {
+  F k;
+  uint32_t on;
+};
 ZK_D bool msm_base_zero(const void* bases, uint32_t elem16, uint32_t i) {
   const uint4* p = reinterpret_cast<const uint4*>(bases) + (size_t)i * elem16;
   uint4 a = p[0];
@@ -141,7 +152,7 @@ __global__ void msm_digits_kernel(MsmScalars<Fp<FrP>> sc, const Fp<FrP>* __restr
                                   uint32_t* __restrict__ cursor, uint32_t* __restrict__ sorted,
                                   MsmBaseId bid /* identity bases get a zero scalar in pass 0 */,
                                   Fp<FrP>* __restrict__ canon /* canonical scalars: written by pass 0, read by pass 1 */,
-                                  size_t ys) {
+                                  size_t ys, MsmScale1<Fp<FrP>> sc1) {
   __builtin_amdgcn_s_setprio(3);   // short sort-stage kernel: win issue arbitration against the bulk accumulate waves
   ZK_YSHIFT(counts);
   ZK_YSHIFT(cursor);
@@ -158,6 +169,7 @@ __global__ void msm_digits_kernel(MsmScalars<Fp<FrP>> sc, const Fp<FrP>* __restr
     }
     s = load_elem(sc.p[vb] + i);
     if (coef) s = s * coef[i / part_len];
+    if (sc1.on && blockIdx.y) s = s * sc1.k;
     s = s.from_mont();
     store_elem(canon + g, s);
   } else {
@@ -365,11 +377,13 @@ __device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* sh /* 
 // scalar of (vector vb of the batch, point i); identity bases give zero (no digit, no entry)
 template <class FrP>
 __device__ __forceinline__ Fp<FrP> msm_canon_scalar(const MsmScalars<Fp<FrP>>& sc, const Fp<FrP>* coef, size_t part_len,
-                                                    uint32_t vb, uint32_t i, const MsmBaseId& bid, size_t ys) {
+                                                    uint32_t vb, uint32_t i, const MsmBaseId& bid, size_t ys,
+                                                    const MsmScale1<Fp<FrP>>& sc1) {
   Fp<FrP> s = Fp<FrP>::zero();
   if (!msm_base_is_identity(bid, i, ys)) {
     s = load_elem(sc.p[vb] + i);
     if (coef) s = s * coef[i / part_len];
+    if (sc1.on && blockIdx.y) s = s * sc1.k;
     s = s.from_mont();
   }
   return s;
@@ -388,7 +402,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_hist_kernel(MsmScalars<Fp<FrP
                                                                uint16_t* __restrict__ tile_counts /* optional
                                                                [tiles][bins of one vector]: the staged scatter, whose
                                                                tiles these then are, does not count again */,
-                                                               size_t ys) {
+                                                               size_t ys, MsmScale1<Fp<FrP>> sc1) {
   __builtin_amdgcn_s_setprio(3);   // short sort-stage kernel: win issue arbitration against the bulk accumulate waves
   ZK_YSHIFT(bins);
   ZK_YSHIFT(canon);
@@ -412,7 +426,7 @@ __global__ __launch_bounds__(BIG_THREADS) void msm_hist_kernel(MsmScalars<Fp<FrP
   for (int k = 0; k < ppt; k++) {
     const uint32_t i = pt0 + (uint32_t)k * BIG_THREADS + threadIdx.x;
     if (i >= sc.npts) break;
-    const Fp<FrP> s = ((idmask >> k) & 1u) ? Fp<FrP>::zero() : msm_canon_scalar<FrP>(sc, coef, part_len, vb, i, no_id, ys);
+    const Fp<FrP> s = ((idmask >> k) & 1u) ? Fp<FrP>::zero() : msm_canon_scalar<FrP>(sc, coef, part_len, vb, i, no_id, ys, sc1);
     store_elem(canon + (size_t)vb * sc.npts + i, s);
     msm_for_each_digit<FrP>(s, c, nwin, wide, [&](int w, uint32_t b, uint32_t) {
       atomicAdd(&big_lds[(((uint32_t)w & wmask) << hi_bits) | (b >> lo_bits)], 1u);
@@ -1311,7 +1325,20 @@ __global__ __launch_bounds__(64) void msm_heavy_kernel(const XYZZ<Fld>* __restri
 // inside one lane's range, or already summed by msm_heavy_kernel -> untouched; otherwise tail + heads.  (Forming the sum
 // inside the reduction's bucket load instead was measured and rejected: it puts independent work into the reduction's
 // dependent chains -- 434 vs 490 proofs/s one at a time.)
+//
+// SHARED BUCKET SET.  Bucket accumulation is linear: MSMs whose launches have the same bucket geometry (msm_plan.hpp MsmGeo)
+// can end in ONE bucket set and one reduction.  A DONOR launch stops behind this kernel -- its buckets are then final, the
+// empty ones hold the identity -- and an ABSORBING launch adds up to two donated arrays to its own buckets here, bucket by
+// bucket, before its reduction (`ab`).  With donors EVERY bucket is visited: the ones the accumulate kernel wrote itself and
+// the ones msm_heavy_kernel finished are read back, the empty ones start from the identity; the sums go through qadd, which
+// handles equal, opposite and identity operands (two MSMs may well put the same point into the same bucket).  Buckets whose
+// chunk sums the extra workgroups add (msm_heavy_splits > 1) are merged by those, so that each bucket has one writer.
+// A launch that donates ALL its vectors has no reduce stage B: the entry counts of its sorts (zk_msm_stats) leave from here.
 constexpr int FIN_THREADS = 64;
+template <class Fld>
+struct MsmAbsorb {
+  const XYZZ<Fld>* d[2];           // donated bucket arrays, nkeys buckets each (nullptr: none; d[1] only with d[0])
+};
 template <class Fld>
 __global__ __launch_bounds__(FIN_THREADS) void msm_finalize_kernel(const XYZZ<Fld>* __restrict__ edge0, uint32_t nlanes,
                                                                uint32_t tmin, uint32_t cap,
@@ -1319,13 +1346,16 @@ __global__ __launch_bounds__(FIN_THREADS) void msm_finalize_kernel(const XYZZ<Fl
                                                                XYZZ<Fld>* __restrict__ buckets0,
                                                                const uint32_t* __restrict__ heavy,
                                                                const XYZZ<Fld>* __restrict__ hpart0, uint32_t vcap,
-                                                               uint32_t fin_wgs, size_t ys) {
+                                                               uint32_t fin_wgs, size_t ys, MsmAbsorb<Fld> ab,
+                                                               uint32_t* __restrict__ cnt_dst, uint32_t ncnt) {
   __builtin_amdgcn_s_setprio(3);   // latency-bound: win issue arbitration against the bulk accumulate waves
   ZK_YSHIFT(offsets);
   const XYZZ<Fld>* __restrict__ head = edge0 + (size_t)blockIdx.y * 2 * nlanes;
   const XYZZ<Fld>* __restrict__ tail = head + nlanes;
   XYZZ<Fld>* __restrict__ buckets = buckets0 + (size_t)blockIdx.y * nkeys;
   const int q = threadIdx.x & 3;
+  const bool merge = ab.d[0] != nullptr;            // (absorbing launches have one base vector: blockIdx.y = 0)
+  if (cnt_dst && blockIdx.x == 0 && threadIdx.x == 0 && blockIdx.y < ncnt) cnt_dst[2 * blockIdx.y] = offsets[nkeys];
   if (blockIdx.x >= fin_wgs) {
     // extra workgroups: the chunk sums msm_heavy_kernel left for buckets with several virtual workgroups
     ZK_YSHIFT(heavy);
@@ -1341,7 +1371,14 @@ __global__ __launch_bounds__(FIN_THREADS) void msm_finalize_kernel(const XYZZ<Fl
       bool have = false;
       for (uint32_t j = (uint32_t)vl; j < S; j += FIN_THREADS / 4) qaccum(acc, have, hpart + vb + j, q);
       acc = wg_quad_sum(acc, sh, vl, q, FIN_THREADS / 4);
-      if (vl == 0) qstore(buckets + heavy[2 + 2 * h], q, acc);
+      if (vl == 0) {
+        const uint32_t kh = heavy[2 + 2 * h];
+        if (merge) {
+          acc = qadd(acc, qload(ab.d[0] + kh, q), q);
+          if (ab.d[1]) acc = qadd(acc, qload(ab.d[1] + kh, q), q);
+        }
+        qstore(buckets + kh, q, acc);
+      }
       __syncthreads();
     }
     return;
@@ -1352,14 +1389,22 @@ __global__ __launch_bounds__(FIN_THREADS) void msm_finalize_kernel(const XYZZ<Fl
   for (size_t k = (size_t)blockIdx.x * (FIN_THREADS / 4) + (threadIdx.x >> 2); k < nkeys;
        k += (size_t)fin_wgs * (FIN_THREADS / 4)) {
     const uint32_t o0 = offsets[k], o1 = offsets[k + 1];
-    if (o0 == o1) {
-      qstore(buckets + k, q, qidentity<Fld>(q));
-      continue;
+    Fld acc = qidentity<Fld>(q);
+    if (o0 != o1) {
+      const uint32_t l0 = o0 / T, l1 = (o1 - 1) / T;
+      if (l1 == l0 || l1 - l0 > FIN_SEQ) {
+        // final already (inside one lane's range, or summed by msm_heavy_kernel) -- or left to the extra workgroups
+        if (!merge || (l1 != l0 && msm_heavy_splits(l1 - l0) > 1)) continue;
+        acc = qload(buckets + k, q);
+      } else {
+        acc = qload(tail + l0, q);
+        for (uint32_t l = l0 + 1; l <= l1; l++) acc = qadd(acc, qload(head + l, q), q);
+      }
     }
-    const uint32_t l0 = o0 / T, l1 = (o1 - 1) / T;
-    if (l1 == l0 || l1 - l0 > FIN_SEQ) continue;
-    Fld acc = qload(tail + l0, q);
-    for (uint32_t l = l0 + 1; l <= l1; l++) acc = qadd(acc, qload(head + l, q), q);
+    if (merge) {
+      acc = qadd(acc, qload(ab.d[0] + k, q), q);
+      if (ab.d[1]) acc = qadd(acc, qload(ab.d[1] + k, q), q);
+    }
     qstore(buckets + k, q, acc);
   }
 }
@@ -1484,6 +1529,9 @@ struct MsmSlot {
   size_t pinned_bytes = 0;
   hipEvent_t ev = nullptr;
   std::atomic<bool> busy{false};
+  // The launch DONATED buckets (MsmShare): they lie in `ws`, and the absorbing launch reads them after this slot's own
+  // event.  A lent slot stays busy until whoever joined the absorbing launch calls release_loan().
+  std::atomic<bool> lent{false};
   std::shared_ptr<const MsmTable> tab, tab2;     // keep the tables alive while the kernels run
   // Waits for the slot's last launch (bounded by the context's deadline): then the slot is free and drops its tables.
   // hipErrorNotReady = the deadline passed; the slot stays busy (its kernels may still run).
@@ -1491,10 +1539,16 @@ struct MsmSlot {
     if (!busy) return hipSuccess;
     hipError_t he = eng->event_wait(ev);
     if (he == hipErrorNotReady) return he;
+    if (lent) return he;
     tab.reset();
     tab2.reset();
     busy = false;
     return he;
+  }
+  // the absorbing launch has finished (or was never enqueued); not concurrently with wait() from another thread
+  hipError_t release_loan(const IEngine* eng) {
+    lent = false;
+    return wait(eng);
   }
   ~MsmSlot() {
     if (pinned) (void)hipHostFree(pinned);
@@ -1522,6 +1576,27 @@ struct MsmBatchArg {
 struct MsmPending {
   MsmFoldGeo fold;
   MsmSlot* slot = nullptr;                       // nullptr: nothing was launched (no points), the results are identities
+  int nred = -1;                                 // base vectors [0, nred) were reduced, the others donated (-1: all reduced)
+  MsmGeo geo;
+  const void* donated[2] = {nullptr, nullptr};   // by base vector: its finished bucket array in the slot's workspace
+  hipEvent_t donated_ev = nullptr;               // recorded behind the finalize kernel that finished them
+};
+
+// Sharing of bucket sets between launches (msm_finalize_kernel, "SHARED BUCKET SET") and the second vector's scalar factor.
+// The caller has compared the geometries beforehand (MsmRunner::geometry); the absorbing launch checks them again.
+template <class Fr>
+struct MsmShare {
+  int keep = -1;                      // >= 0: base vectors [keep, vectors) DONATE their buckets: no reduction, no slices, no
+                                      // fold for them; `donated_ev` is recorded behind the finalize kernel
+  hipEvent_t donated_ev = nullptr;
+  bool scale1_on = false;             // the second base vector's scalars times scale1 (forces a sort per vector)
+  Fr scale1;
+  int n_absorb = 0;                   // donated bucket arrays this launch adds to its own before its reduction
+  const MsmPending* from[2] = {nullptr, nullptr};
+  int from_vec[2] = {0, 0};
+  // optional, when the donor is launched by another host thread: raised by that thread once from[i] is filled and its
+  // event recorded (1), or once its launch has failed (-1); the absorbing launch waits for it within the deadline
+  std::atomic<int>* from_flag[2] = {nullptr, nullptr};
 };
 
 // Ordering between the accumulate kernels of concurrent launches (the Groth16 prover runs the G2 accumulate ahead of the
@@ -1559,7 +1634,37 @@ struct MsmTuning {
 template <class FrP, class Fld>
 int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* bases, const void* bases2,
                const void* scalars, size_t npts, const Fp<FrP>* coef_d, size_t part_len, hipStream_t st,
-               MsmPending* out, const MsmBatchArg* batch = nullptr);
+               MsmPending* out, const MsmBatchArg* batch = nullptr, const MsmShare<Fp<FrP>>* share = nullptr);
+// the plan msm_launch would follow now (the registry of fixed-base tables may change between two calls); tab / tab2:
+// the tables it uses, if any
+template <class FrP, class Fld>
+MsmPlan msm_plan_for(const MsmTuning& tune, const void* bases, const void* bases2, size_t npts, size_t batch, bool own_sorts,
+                     std::shared_ptr<const MsmTable>* tab_out = nullptr, std::shared_ptr<const MsmTable>* tab2_out = nullptr,
+                     size_t* toff_out = nullptr) {
+  constexpr bool G2FLD = IsExtField<Fld>::value;
+  const unsigned NB = bases2 ? 2u : 1u;
+  // fixed-base table registered for this base vector (and the same window layout / offset for the second one)?
+  size_t toff = 0, toff2 = 0;
+  std::shared_ptr<const MsmTable> tab = TableRegistry::inst().find(bases, npts, sizeof(Affine<Fld>), FrP::BITS, &toff), tab2;
+  if (tab && NB == 2) {
+    tab2 = TableRegistry::inst().find(bases2, npts, sizeof(Affine<Fld>), FrP::BITS, &toff2);
+    if (!tab2 || tab2->len != tab->len || toff2 != toff || tab2->c != tab->c) tab = nullptr, tab2 = nullptr;
+  }
+  MsmPlanIn in;
+  in.scalar_bits = FrP::BITS, in.scalar_bytes = (int)sizeof(Fp<FrP>), in.coord_bytes = (int)sizeof(Fld), in.g2 = G2FLD;
+  if constexpr (G2FLD) in.acc_waves = SPLIT_WAVES<typename BaseParams<Fld>::type>;
+  else in.acc_waves = ACC_WAVES<Fld>;
+  in.npts = npts, in.batch = batch, in.vectors = (int)NB;      // batch: scalar vectors multiplied against the same base vector(s)
+  if (tab) {
+    in.tab_c = tab->c, in.tab_len = tab->len, in.tab_off = toff;
+    in.tab_no_identity = !tab->any_identity && (NB == 1 || !tab2->any_identity);
+  }
+  in.c_force = tune.c_force, in.bigsort_min = tune.bigsort_min, in.own_sorts = own_sorts;
+  if (tab_out) *tab_out = tab;
+  if (tab2_out) *tab2_out = tab2;
+  if (toff_out) *toff_out = toff;
+  return msm_plan(in);
+}
 // det_pack over extension-field points, quad-split (pack_split.hpp; same translation units: inline 12-limb products).
 // dig: the parties' joint-sparse-form digit columns [n][jlen] (groth16.hpp jsf_digits); G1 instantiations return an error.
 template <class FrP, class Fld>
@@ -1605,6 +1710,8 @@ int msm_fold_batch(IEngine* eng, MsmPending& p, XYZZ<Fld>* results, int nvec) {
     eng->msm_offered[f.g2 ? 1 : 0].fetch_add(f.offered, std::memory_order_relaxed);
   }
   if (nvec > f.nb) nvec = f.nb;
+  if (p.nred >= 0 && nvec > p.nred) nvec = p.nred;          // donated vectors have no slices: their results stay identities
+  if (nvec == 0) return ZK_OK;
   // windows [w_lo, w_hi] of one vector, high to low, doublings only INSIDE the range:
   // sum_w 2^(start_w - start_w_lo) X_w with X_w = sum_j 2^(j + lo_bits) TR_j + sum_j 2^j TC_j
   auto fold_range = [&](const XYZZ<Fld>* h, int w_hi, int w_lo) -> XYZZ<Fld> {
@@ -1764,14 +1871,89 @@ class MsmRunner {
   template <class Fld>
   int launch_t(IEngine* eng, int ws, const void* bases, const void* scalars, size_t npts, const Fr* coef_d,
                size_t part_len, hipStream_t st, MsmPending* pend, const void* bases2 = nullptr, MsmGate gate = MsmGate{},
-               const MsmBatchArg* batch = nullptr) {
+               const MsmBatchArg* batch = nullptr, const MsmShare<Fr>* share = nullptr) {
     if (ws < 0 || ws >= MSM_WS) return eng->fail(ZK_ERR_BAD_INPUT, "bad msm workspace slot");
     if (slots_[ws].busy) return eng->fail(ZK_ERR_GENERIC, "msm workspace slot still in flight");
     MsmTuning tune{bigsort_min, gate, IsExtField<Fld>::value ? c_g2 : c_g1};
     int rc = msm_launch<FrP, Fld>(eng, slots_[ws], tune, bases, bases2, scalars, npts, coef_d, part_len, st, pend,
-                                  batch);
-    if (rc) (void)slots_[ws].wait(eng);
+                                  batch, share);
+    if (rc) (void)slots_[ws].wait(eng);      // (a donor stays busy: whoever owns the absorbing launch releases the loan)
     return rc;
+  }
+  // the bucket geometry a launch over these vectors would have now; false: nothing would be launched (no points)
+  template <class Fld>
+  bool geometry(const void* bases, const void* bases2, size_t npts, MsmGeo* out) const {
+    if (!npts) return false;
+    MsmTuning tune{bigsort_min, MsmGate{}, IsExtField<Fld>::value ? c_g2 : c_g1};
+    const MsmPlan pl = msm_plan_for<FrP, Fld>(tune, bases, bases2, npts, 1, bases2 != nullptr);
+    if (pl.err) return false;
+    *out = pl.geo();
+    return true;
+  }
+  // zk_msm_sum: sum_i MSM(bases[i], scalars[i]) of k <= MSM_SUM_MAX MSMs over one group as ONE point.  The last vector's
+  // launch absorbs the buckets of every earlier one whose geometry equals its own ("SHARED BUCKET SET": one reduction and
+  // one fold for all of them); the others are reduced and folded on their own and added on the host.  Launches are
+  // enqueued back to back on `st`; the donors run on the WS_SUM slots.
+  template <class Fld>
+  int sum_t(IEngine* eng, int k, const void* const* bases, const void* const* scalars, const size_t* lens, hipStream_t st,
+            XYZZ<Fld>* out, int* shared_out) {
+    int rc = eng->check_wedged();
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(standalone_mu_);
+    const int last = k - 1;
+    MsmGeo geo[MSM_SUM_MAX];
+    bool has[MSM_SUM_MAX];
+    for (int i = 0; i < k; i++) has[i] = geometry<Fld>(bases[i], nullptr, lens[i], &geo[i]);
+    MsmPending pend[MSM_SUM_MAX];
+    MsmShare<Fr> ab, don;
+    don.keep = 0;                                // a donor of this call donates its only vector; event: its slot's own
+    int lrc[MSM_SUM_MAX], nshared = 0;
+    bool launched[MSM_SUM_MAX] = {};
+    for (int i = 0; i < k && !rc; i++) {
+      const bool donor = i < last && has[i] && has[last] && geo[i] == geo[last];
+      if (donor) {
+        ab.from[ab.n_absorb] = &pend[i];
+        ab.from_vec[ab.n_absorb++] = 0;
+        nshared++;
+      }
+      launched[i] = true;
+      rc = lrc[i] = launch_t<Fld>(eng, i < last ? WS_SUM + i : WS_STANDALONE, bases[i], scalars[i], lens[i], nullptr, 1, st,
+                                  &pend[i], nullptr, MsmGate{}, nullptr, donor ? &don : (i == last && ab.n_absorb ? &ab : nullptr));
+    }
+    // join: the absorbing launch first, then the loans, then whatever was reduced on its own
+    XYZZ<Fld> total = XYZZ<Fld>::identity();
+    bool expired = false;
+    for (int i = last; i >= 0; i--) {
+      if (!launched[i]) continue;
+      XYZZ<Fld> r = XYZZ<Fld>::identity();
+      const int rf = lrc[i] ? ZK_OK : msm_fold_batch<Fld>(eng, pend[i], &r, 1);      // (a donor: waits, counts its entries)
+      MsmSlot* sl = pend[i].slot;
+      if (sl && sl->lent && !slots_[WS_STANDALONE].busy) (void)sl->release_loan(eng);
+      if (rf && !rc) rc = rf;
+      if (sl && sl->busy) expired = true;
+      total = xyzz_add_ni(total, r);
+    }
+    if (expired) {
+      Status keep = eng->last;
+      return eng->wedge(keep.msg);
+    }
+    if (rc) return rc;
+    *out = total;
+    if (shared_out) *shared_out = nshared;
+    return ZK_OK;
+  }
+  int sum(IEngine* eng, int group, int k, const void* const* bases, const void* const* scalars, const size_t* lens, void* out,
+          int* shared_out, hipStream_t st) {
+    if (k < 1 || k > MSM_SUM_MAX || !bases || !scalars || !lens) return eng->fail(ZK_ERR_BAD_INPUT, "zk_msm_sum: 1 to 3 MSMs");
+    if (!out) return eng->fail(ZK_ERR_BAD_INPUT, "null output");
+    for (int i = 0; i < k; i++)
+      if (lens[i] && (!bases[i] || !scalars[i])) return eng->fail(ZK_ERR_BAD_INPUT, "null pointer");
+    return by_group(eng, group, [&](auto fld) {
+      XYZZ<decltype(fld)> r;
+      int rc = sum_t(eng, k, bases, scalars, lens, st, &r, shared_out);
+      if (!rc) write_jacobian(out, r);
+      return rc;
+    });
   }
   // (Round 4 measured a large lone MSM as TWO window groups on two streams -- the sort of the upper windows under the
   // accumulate of the lower ones: 13.3-13.4 ms with the staged sort kernels, 15.2-15.3 with small-workgroup ones, against

@@ -63,7 +63,7 @@ hipError_t msm_launch_lds(int device, void (*kernel)(P...), dim3 grid, dim3 bloc
 // Stage 1: zero, then the sort (two-level or atomics) of the launch's digits into sorted[] / offsets[] / k0[]
 template <class FrP, class KF>
 int msm_stage_sort(IEngine* eng, const MsmPlan& pl, const MsmViews<Fp<FrP>, KF>& v, const MsmScalars<Fp<FrP>>& sc,
-                   const Fp<FrP>* coef_d, size_t plen, const MsmBaseId& bid, hipStream_t st) {
+                   const Fp<FrP>* coef_d, size_t plen, const MsmBaseId& bid, const MsmScale1<Fp<FrP>>& sc1, hipStream_t st) {
   const size_t npts = pl.npts, ys = pl.ys, nkeys = pl.nkeys;
   const unsigned batch = (unsigned)pl.batch, NS = pl.nsorts;
   const int c = pl.win.c, nwin = pl.win.nwin, wide = pl.win.wide, sort_hi = pl.sort_hi, sort_lo = pl.sort_lo;
@@ -77,7 +77,7 @@ int msm_stage_sort(IEngine* eng, const MsmPlan& pl, const MsmViews<Fp<FrP>, KF>&
       const unsigned tpv = tiles((size_t)BIG_THREADS * pl.hist_ppt);
       MSM_HIP(msm_launch_lds(eng->device, msm_hist_kernel<FrP>, dim3(tpv * batch, NS), dim3(BIG_THREADS), pl.hist_lds, st,
                              sc, coef_d, plen, c, nwin, wide, sort_hi, sort_lo, pl.hist_ppt, tpv, wmask, v.bins, bid, v.canon,
-                             v.tcnt, ys));
+                             v.tcnt, ys, sc1));
     }
     if (pl.large) {
       const unsigned tpv = tiles(pl.tile_pts);
@@ -110,7 +110,7 @@ int msm_stage_sort(IEngine* eng, const MsmPlan& pl, const MsmViews<Fp<FrP>, KF>&
     const dim3 pb(256), pgb((unsigned)((npts * batch + 255) / 256), NS);     // one thread per (scalar vector, point)
     const unsigned ib = (unsigned)pl.iscan_blocks;
     msm_digits_kernel<FrP, 0><<<pgb, pb, 0, st>>>(sc, coef_d, plen, c, nwin, wide, pl.pre_stride, pl.pre_off, v.counts, nullptr,
-                                                 nullptr, bid, v.canon, ys);
+                                                 nullptr, bid, v.canon, ys, sc1);
     MSM_STAGE("digits/count");
     iscan_block_kernel<<<dim3(ib, NS), dim3(ISCAN_THREADS), 0, st>>>(v.counts, nkeys, v.bt, nullptr, nullptr, nullptr, 0, ys);
     iscan_carry_kernel<<<dim3(1, NS), dim3(ISCAN_THREADS), 0, st>>>(v.bt, pl.iscan_blocks, ys);
@@ -119,7 +119,7 @@ int msm_stage_sort(IEngine* eng, const MsmPlan& pl, const MsmViews<Fp<FrP>, KF>&
     msm_lane_start_kernel<<<dim3((pl.nlanes + 255) / 256, NS), dim3(256), 0, st>>>(v.offsets, (uint32_t)nkeys, pl.nlanes, pl.tmin,
                                                                                  pl.cap, v.k0, ys);
     msm_digits_kernel<FrP, 1><<<pgb, pb, 0, st>>>(sc, coef_d, plen, c, nwin, wide, pl.pre_stride, pl.pre_off, nullptr, v.cursor,
-                                                 v.sorted, bid, v.canon, ys);
+                                                 v.sorted, bid, v.canon, ys, sc1);
   }
   return ZK_OK;
 }
@@ -164,11 +164,15 @@ int msm_stage_accumulate(IEngine* eng, const MsmPlan& pl, const MsmViews<Fr, KF>
   return ZK_OK;
 }
 
-// Stage 3: heavy buckets, finalize, reduce A and B (the bit slices land in the pinned buffer)
+// Stage 3: heavy buckets, finalize, reduce A and B (the bit slices land in the pinned buffer).  share (msm.hpp "SHARED
+// BUCKET SET"): donated bucket arrays are added in the finalize kernel, behind their donors' events; base vectors
+// [share->keep, vectors) of this launch donate theirs -- the reduction covers the vectors in front of them, if any.
 template <class Fr, class Fld, class KF>
-int msm_stage_reduce(IEngine* eng, const MsmPlan& pl, const MsmViews<Fr, KF>& v, hipStream_t st) {
+int msm_stage_reduce(IEngine* eng, const MsmPlan& pl, const MsmViews<Fr, KF>& v, hipStream_t st, const MsmShare<Fr>* share,
+                     MsmPending* pend) {
   constexpr bool G2FLD = IsExtField<Fld>::value;
   const unsigned NB = pl.vectors, nsets = (unsigned)pl.nsets;
+  const unsigned NR = share && share->keep >= 0 ? std::min<unsigned>((unsigned)share->keep, NB) : NB;      // vectors reduced here
   const uint32_t nkeys = (uint32_t)pl.nkeys, nlanes = pl.nlanes, tmin = pl.tmin, cap = pl.cap;
   const size_t ys = pl.ys;
   ProfScope ps_(eng->prof, G2FLD ? PROF_MSM_REDUCE_G2 : PROF_MSM_REDUCE, st, (double)pl.nkeys * NB);   // units: buckets
@@ -180,6 +184,21 @@ int msm_stage_reduce(IEngine* eng, const MsmPlan& pl, const MsmViews<Fr, KF>& v,
   msm_heavy_kernel<KF><<<dim3(2048, NB), dim3(64), (size_t)16 * sizeof(XYZZ<Fld>), st>>>(v.edge, nlanes, tmin, cap, v.offsets, nkeys,
                                                                     v.buckets, v.heavy, v.hpart, pl.vcap, ys);
   MSM_STAGE("heavy buckets");
+  MsmAbsorb<KF> ab{{nullptr, nullptr}};
+  for (int i = 0; share && i < share->n_absorb; i++) {
+    if (NB != 1 || i >= 2) return eng->fail(ZK_ERR_GENERIC, "msm launch: a launch over one base vector absorbs at most two bucket arrays");
+    // a donor launched by another host thread: its pending launch is filled and its event recorded once the flag is up
+    std::atomic<int>* fl = share->from_flag[i];
+    if (fl && !eng->spin_until([&] { return fl->load(std::memory_order_acquire) != 0; }))
+      return eng->fail(ZK_ERR_GENERIC, "msm launch: a launch that donates buckets to this one was not enqueued within the deadline");
+    if (fl && fl->load(std::memory_order_acquire) < 0) return eng->fail(ZK_ERR_GENERIC, "msm launch: a launch that donates buckets to this one failed");
+    const MsmPending* d = share->from[i];
+    const void* arr = d ? d->donated[share->from_vec[i] & 1] : nullptr;
+    if (!arr || !d->donated_ev || d->geo != pl.geo())
+      return eng->fail(ZK_ERR_GENERIC, "msm launch: donated buckets of another geometry (the table registry changed between plan and launch?)");
+    MSM_HIP(hipStreamWaitEvent(st, d->donated_ev, 0));
+    ab.d[i] = (const XYZZ<KF>*)arr;
+  }
   {
     // capped grid (grid-stride inside): enough one-wave workgroups to cover the chip a few times over
     const size_t fin_wgs = std::min<size_t>((pl.nkeys + FIN_THREADS / 4 - 1) / (FIN_THREADS / 4), 8192);
@@ -187,16 +206,25 @@ int msm_stage_reduce(IEngine* eng, const MsmPlan& pl, const MsmViews<Fr, KF>& v,
     const unsigned fin_extra = 256;
     msm_finalize_kernel<KF><<<dim3((unsigned)fin_wgs + fin_extra, NB), dim3(FIN_THREADS),
                               (size_t)(FIN_THREADS / 4) * sizeof(XYZZ<Fld>), st>>>(
-        v.edge, nlanes, tmin, cap, v.offsets, nkeys, v.buckets, v.heavy, v.hpart, pl.vcap, (uint32_t)fin_wgs, ys);
+        v.edge, nlanes, tmin, cap, v.offsets, nkeys, v.buckets, v.heavy, v.hpart, pl.vcap, (uint32_t)fin_wgs, ys, ab,
+        // no reduce stage B in a launch that donates every vector: the sorts' entry counts leave from here
+        NR == 0 ? v.stats : nullptr, pl.nsorts);
   }
   MSM_STAGE("finalize");
+  if (NR < NB) {
+    for (unsigned y = NR; y < NB; y++) pend->donated[y] = v.buckets + (size_t)y * nkeys;
+    pend->donated_ev = share->donated_ev;
+    pend->nred = (int)NR;
+    if (share->donated_ev) MSM_HIP(hipEventRecord(share->donated_ev, st));
+    if (NR == 0) return ZK_OK;
+  }
   // quads per group: few groups (one bucket set) -> whole workgroups per group, shortest dependent chain; many groups
   // (one bucket set per window) -> 4 quads per group, waves stay full
   // As many quads per group as keep the whole launch resident at once (a second generation of workgroups doubles a
   // kernel that is one dependent chain): the chip holds 1024 SIMDs x (2 waves of the extension-field kernels, 3 of the
   // base-field ones) x 16 quads.
-  const size_t tot_groups = (size_t)pl.red_groups * NB * nsets;
-  const size_t tot_slices = (size_t)pl.nslices * NB * nsets;
+  const size_t tot_groups = (size_t)pl.red_groups * NR * nsets;
+  const size_t tot_slices = (size_t)pl.nslices * NR * nsets;
   const size_t cap_quads = (size_t)1024 * (G2FLD ? 2 : 3) * 16;
   auto pick_nvl = [&](size_t groups) {
     int n = qvl;
@@ -205,9 +233,9 @@ int msm_stage_reduce(IEngine* eng, const MsmPlan& pl, const MsmViews<Fr, KF>& v,
   };
   const int nvl_a = pick_nvl(tot_groups), nvl_b = pick_nvl(tot_slices);
   const unsigned gpw_a = (unsigned)(qvl / nvl_a), gpw_b = (unsigned)(qvl / nvl_b);
-  msm_reduce_a_kernel<KF><<<dim3((pl.red_groups + gpw_a - 1) / gpw_a, NB * nsets), dim3((unsigned)qt), quad_lds, st>>>(
+  msm_reduce_a_kernel<KF><<<dim3((pl.red_groups + gpw_a - 1) / gpw_a, NR * nsets), dim3((unsigned)qt), quad_lds, st>>>(
       v.buckets, pl.B, pl.lo_bits, nvl_a, v.rc);
-  msm_reduce_b_kernel<KF><<<dim3(((unsigned)pl.nslices + gpw_b - 1) / gpw_b, NB * nsets), dim3((unsigned)qt), quad_lds, st>>>(
+  msm_reduce_b_kernel<KF><<<dim3(((unsigned)pl.nslices + gpw_b - 1) / gpw_b, NR * nsets), dim3((unsigned)qt), quad_lds, st>>>(
       v.rc, pl.B, pl.lo_bits, nvl_b, v.out,
       // mixed additions actually performed = sorted entries (identity bases and zero digits leave none): one count per sort
       v.offsets + nkeys, ys, pl.nsorts, v.stats);
@@ -217,7 +245,7 @@ int msm_stage_reduce(IEngine* eng, const MsmPlan& pl, const MsmViews<Fr, KF>& v,
 template <class FrP, class Fld>
 int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* bases, const void* bases2,
                const void* scalars, size_t npts, const Fp<FrP>* coef_d, size_t part_len, hipStream_t st,
-               MsmPending* pend, const MsmBatchArg* ba) {
+               MsmPending* pend, const MsmBatchArg* ba, const MsmShare<Fp<FrP>>* share) {
   using Fr = Fp<FrP>;
   using KF = typename KernelField<Fld>::type;     // same layout as Fld
   static_assert(sizeof(KF) == sizeof(Fld), "kernel field layout");
@@ -227,29 +255,19 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
   const unsigned NB = bases2 ? 2u : 1u;
   const void* const bases_in = bases;            // the caller's points (the identity test reads them, not the table rows)
   const void* const bases2_in = bases2;
-  // fixed-base table registered for this base vector (and the same window layout / offset for the second one)?
-  size_t toff = 0, toff2 = 0;
-  std::shared_ptr<const MsmTable> tab = TableRegistry::inst().find(bases, npts, sizeof(Affine<Fld>), FrP::BITS, &toff), tab2;
-  if (tab && NB == 2) {
-    tab2 = TableRegistry::inst().find(bases2, npts, sizeof(Affine<Fld>), FrP::BITS, &toff2);
-    if (!tab2 || tab2->len != tab->len || toff2 != toff || tab2->c != tab->c) tab = nullptr;
-    else bases2 = tab2->data;
-  }
+  std::shared_ptr<const MsmTable> tab, tab2;
+  const MsmPlan pl = msm_plan_for<FrP, Fld>(tune, bases, bases2, npts, ba ? (size_t)ba->nb : 1, share && share->scale1_on, &tab, &tab2);
   if (tab) bases = tab->data;
-  MsmPlanIn in;
-  in.scalar_bits = FrP::BITS, in.scalar_bytes = (int)sizeof(Fr), in.coord_bytes = (int)sizeof(Fld), in.g2 = G2FLD;
-  if constexpr (G2FLD) in.acc_waves = SPLIT_WAVES<typename BaseParams<Fld>::type>;
-  else in.acc_waves = ACC_WAVES<Fld>;
-  in.npts = npts, in.batch = ba ? (size_t)ba->nb : 1, in.vectors = (int)NB;      // batch: scalar vectors multiplied against the same base vector(s)
-  if (tab) {
-    in.tab_c = tab->c, in.tab_len = tab->len, in.tab_off = toff;
-    in.tab_no_identity = !tab->any_identity && (NB == 1 || !tab2->any_identity);
-  }
-  in.c_force = tune.c_force, in.bigsort_min = tune.bigsort_min;
-  const MsmPlan pl = msm_plan(in);
+  if (tab2) bases2 = tab2->data;
   if (pl.err) return eng->fail(ZK_ERR_BAD_INPUT, pl.err);
   pend->fold = pl.fold;
-  if (npts == 0) return ZK_OK;
+  pend->geo = pl.geo();
+  if (share && share->scale1_on && pl.nsorts != 2) return eng->fail(ZK_ERR_GENERIC, "msm launch: a scalar factor for the second base vector needs two vectors");
+  if (share && share->keep >= 0 && pl.batch != 1) return eng->fail(ZK_ERR_GENERIC, "msm launch: a batched launch cannot donate buckets");
+  if (npts == 0) {
+    if (share && (share->n_absorb || share->keep >= 0)) return eng->fail(ZK_ERR_GENERIC, "msm launch: an empty launch shares no buckets");
+    return ZK_OK;
+  }
   hipError_t he = slot.ws.ensure(pl.ws_bytes);
   if (he != hipSuccess) return eng->hip_fail(he, "msm workspace");
   he = slot.ensure_pinned(pl.pinned_bytes);
@@ -261,6 +279,7 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
   // From the first enqueue on the slot is busy and holds the tables; every exit records its event (a failed launch may
   // have enqueued work), so that only MsmSlot::wait frees it.
   slot.busy = true;
+  slot.lent = share && share->keep >= 0 && (unsigned)share->keep < NB;
   slot.tab = tab;
   slot.tab2 = tab2;
   pend->slot = &slot;
@@ -285,13 +304,18 @@ int msm_launch(IEngine* eng, MsmSlot& slot, const MsmTuning& tune, const void* b
     bid.b1 = bases2_in;
     bid.elem16 = (uint32_t)(sizeof(Affine<KF>) / 16);
   }
-  int rc = msm_stage_sort<FrP, KF>(eng, pl, v, sc, coef_d, part_len ? part_len : npts, bid, st);
+  MsmScale1<Fr> sc1{};
+  if (share && share->scale1_on) sc1.k = share->scale1, sc1.on = 1u;
+  int rc = msm_stage_sort<FrP, KF>(eng, pl, v, sc, coef_d, part_len ? part_len : npts, bid, sc1, st);
   if (rc) return rc;
   MSM_STAGE("scatter");
   rc = msm_stage_accumulate<Fr, Fld, KF>(eng, pl, v, tune.gate, bases, bases2, st);
   if (rc) return rc;
   MSM_STAGE("accumulate");
-  rc = msm_stage_reduce<Fr, Fld, KF>(eng, pl, v, st);
+  MsmShare<Fr> sh_ = share ? *share : MsmShare<Fr>{};
+  if (sh_.keep >= 0 && !sh_.donated_ev) sh_.donated_ev = slot.ev;      // (then every vector donates: checked below)
+  if (share && share->keep > 0 && !share->donated_ev) return eng->fail(ZK_ERR_GENERIC, "msm launch: a partial donor needs an event");
+  rc = msm_stage_reduce<Fr, Fld, KF>(eng, pl, v, st, share ? &sh_ : nullptr, pend);
   if (rc) return rc;
   MSM_HIP(hipGetLastError());
   MSM_STAGE("reduce");
@@ -364,7 +388,8 @@ int base_mul_few_launch(IEngine* eng, const void* scalars, size_t len, const voi
 
 #define ZK_INSTANTIATE_MSM(FRP, FLD)                                                                              \
   template int msm_launch<FRP, FLD>(IEngine*, MsmSlot&, const MsmTuning&, const void*, const void*, const void*, \
-                                    size_t, const Fp<FRP>*, size_t, hipStream_t, MsmPending*, const MsmBatchArg*);  \
+                                    size_t, const Fp<FRP>*, size_t, hipStream_t, MsmPending*, const MsmBatchArg*, \
+                                    const MsmShare<Fp<FRP>>*);  \
   template int msm_table_launch<FRP, FLD>(IEngine*, const void*, size_t, int, int, int, void*, hipStream_t);     \
   template int pack_points_split_launch<FRP, FLD>(IEngine*, const void*, size_t, int, const uint8_t*, int, const void*, void*, hipStream_t); \
   template int base_mul_split_launch<FRP, FLD>(IEngine*, const void*, size_t, const void*, int, int, void*, hipStream_t); \

@@ -158,6 +158,21 @@ struct MsmFoldGeo {
   bool g2 = false;
 };
 
+// The bucket geometry of a launch: two launches whose geometries are equal fill bucket arrays that can be added bucket by
+// bucket (msm.hpp "SHARED BUCKET SET"): bucket k of either holds the points whose digit in the same window (of the same
+// bit position and width) has the same magnitude.
+struct MsmGeo {
+  bool g2 = false;
+  int c = 0, nwin = 0, kwin = 0, lo_bits = 0;
+  size_t nsets = 0, nkeys = 0;
+  uint32_t B = 0;
+  bool operator==(const MsmGeo& o) const {
+    return g2 == o.g2 && c == o.c && nwin == o.nwin && kwin == o.kwin && lo_bits == o.lo_bits && nsets == o.nsets &&
+           nkeys == o.nkeys && B == o.B;
+  }
+  bool operator!=(const MsmGeo& o) const { return !(*this == o); }
+};
+
 struct MsmPlanIn {
   int scalar_bits = 0, scalar_bytes = 0;     // scalar field: bits of the modulus, bytes of an element
   int coord_bytes = 0;                       // bytes of one coordinate (an Fq2 element for G2)
@@ -170,6 +185,8 @@ struct MsmPlanIn {
   bool tab_no_identity = false;              // ... no registered vector of the launch holds an identity
   int c_force = 0;                           // zk_ctx_set_option "msm_c" / "msm_c_g2" (0: the cost model)
   size_t bigsort_min = 0;                    // two-level sort from this many points on ("msm_bigsort_min")
+  bool own_sorts = false;                    // two base vectors: a sort each even without identities (their scalars are scaled
+                                             // differently: msm.hpp MsmShare::scale1)
 };
 
 // workspace regions, in layout order
@@ -229,6 +246,7 @@ struct MsmPlan {
   size_t out_bytes = 0;          // bit slices of all bucket sets (pinned)
   size_t pinned_bytes = 0;       // + the sorted-entry counts of the launch's sorts (msm statistics)
   MsmFoldGeo fold;
+  MsmGeo geo() const { return MsmGeo{fold.g2, win.c, win.nwin, kwin, lo_bits, nsets, nkeys, B}; }
 };
 
 inline MsmPlan msm_plan(const MsmPlanIn& in) {
@@ -273,7 +291,7 @@ inline MsmPlan msm_plan(const MsmPlanIn& in) {
   // workspace region (ZK_YSHIFT in the kernels).
   // registered vectors know whether they hold an identity at all (zk_msm_precompute): without one there is no mask
   p.no_identity = tab && in.tab_no_identity;
-  const unsigned NS = p.nsorts = (NB == 2 && !p.no_identity) ? 2u : 1u;
+  const unsigned NS = p.nsorts = (NB == 2 && (!p.no_identity || in.own_sorts)) ? 2u : 1u;
 
   constexpr size_t large_min = (size_t)4 << 20;
   const bool large = p.large = npts * batch >= large_min;
