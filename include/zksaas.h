@@ -586,6 +586,66 @@ int zk_groth16_prove_checked(zk_ctx* ctx, const zk_crs_share* crs, const void* q
                              const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
                              int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
                              uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream);
+/* zk_pss_repair_batch_parties: zk_pss_repair_batch for the shares of ONE party list S, shared by all items -- the three words
+ * of a king round when only the listed parties' words arrived (ext_wit.rs:127-170 with the list of unpack_missing_shares,
+ * secret-sharing/src/pss.rs:141-221; gao.rs:11-84 over the points of S per chunk).  Item i is a COMPACT matrix
+ * [nparties][nchunks] at shares_d + i * item_stride elements, row r the shares of parties[r], as zk_pss_repair_parties lays
+ * them out; item_stride >= nparties * nchunks.  parties (HOST) holds ascending ids below n, NULL stands for
+ * 0 .. nparties - 1.  status_d and errpos_d (by party id) are [nitems][nchunks], summary_d is [nitems][3 + n]; each follows
+ * zk_pss_repair_parties' definitions per item, an item changes only where that call would change it, elements between the
+ * items keep their bytes.  With nitems == 1 every output and byte written equals zk_pss_repair_parties', with nparties == n
+ * zk_pss_repair_batch's.  One clear, the two tables of the list (once per call), one scan launch and one decoder launch
+ * serve all items.
+ * Errors (nothing written): a bad list or dimension -> ZK_ERR_BAD_INPUT and nparties <= dimension -> ZK_ERR_PROTOCOL as in
+ * zk_pss_repair_parties; nitems outside 1 .. 48, item_stride < nparties * nchunks, nitems * nchunks >= 2^32, NULL shares_d
+ * or status_d -> ZK_ERR_BAD_INPUT as in zk_pss_repair_batch.  nchunks == 0 is ZK_OK.
+ * No host synchronisation, working memory from the stream's workspace.  Device engine only. */
+int zk_pss_repair_batch_parties(zk_ctx* ctx, void* shares_d /* in place */,
+                                const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */, int nparties,
+                                size_t item_stride /* elements */, int nitems, size_t nchunks, int dimension,
+                                uint8_t* status_d /* [nitems][nchunks] */, uint32_t* errpos_d /* [nitems][nchunks], or NULL */,
+                                uint64_t* summary_d /* [nitems][3 + n], or NULL */, void* stream);
+/* zk_circom_h_checked_parties: zk_circom_h_checked when only the listed parties' words reach the kings
+ * (groth16/src/ext_wit.rs:104-181; the kings dist-primitives/src/dfft/mod.rs:264-304 and utils/deg_red.rs:99-115 with the list
+ * of unpack_missing_shares, pss.rs:141-221) -- a dropout, or a party left out because an earlier report named it.  The list
+ * is read and refused as the checked kings with a list read it, before anything is written: all n parties or n - 1 of them;
+ * a malformed list is ZK_ERR_BAD_INPUT, a shorter one ZK_ERR_PROTOCOL.  With nparties == n this is zk_circom_h_checked.
+ * The inputs and masks keep their [n][m/l] layouts.  The rows of an absent party in qap_*, in the six fft in-masks and in
+ * degred_in have NO INFLUENCE on any output (they are not read).
+ *   items 0..5  the words of the listed parties, compact, repaired by one zk_pss_repair_batch_parties of 3 items per round
+ *               at dimension 2l (cap = (nparties - 2l) / 2 wrong parties per chunk, named by party id); the kings run with
+ *               the list
+ *   item 6      NOT CHECKED with n - 1 parties: at dimension 4l - 1 no redundancy is left.  The word goes to deg_red with
+ *               the list as received; its status_d and errpos_d bytes are written 0 and its summary_d row is ALL ZEROS --
+ *               zero chunks checked, which a clean item (summary [m/l, 0, 0, ..]) never shows
+ * On honest input h_share_d equals zk_circom_h's bit for bit under the same seed and masks (the kings' randomness depends on
+ * the seed only).  With a liar left out h_share_d is the honest h, items 0..5 report clean and no chunk reaches the decoder.
+ * Errors: those of zk_circom_h_checked.  Device engine only. */
+int zk_circom_h_checked_parties(zk_ctx* ctx, const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */,
+                                int nparties, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
+                                const zk_groth16_masks* masks, uint64_t seed, void* h_share_d,
+                                uint8_t* status_d /* [7][m/l] */, uint32_t* errpos_d /* [7][m/l], or NULL */,
+                                uint64_t* summary_d /* [7][3 + n], or NULL */, void* stream);
+/* zk_groth16_prove_checked_parties: zk_groth16_prove_checked with the party list carried through the whole proof
+ * (groth16/src/prove.rs, examples/sha256.rs:32-129; the kings' unpack_missing_shares, pss.rs:141-221, and the d_msm king,
+ * dist-primitives/src/dmsm/mod.rs:73-102, over the surviving parties as mpc-net/src/ser_net.rs:57-94 delivers them).  A
+ * caller who has read a report asks with it for the honest proof from the remaining n - 1 parties.
+ *   h chain     zk_circom_h_checked_parties with the list; the report buffers as there (item 6 NOT CHECKED with n - 1)
+ *   MSM rounds  the five d_msm rounds and the host in-mask terms use the list's king coefficients (those of
+ *               zk_d_msm_parties), zero at the absent party; every launch keeps the shape it has in zk_groth16_prove
+ * CONTRACT: the absent party's rows of qap_*, a_share_d, ax_share_d and of every in-mask have no influence on the proof.
+ * They must still be readable memory, field rows must hold field elements and point rows curve points: the MSM may read
+ * them under a zero coefficient.  The MSM rounds stay UNCHECKED as in zk_groth16_prove_checked: a wrong a_share / ax_share
+ * row of a LISTED party still spoils the proof.  The list is read and refused as zk_circom_h_checked_parties reads it,
+ * before anything is written; with nparties == n this is zk_groth16_prove_checked.  Synchronous; there is no async, batch
+ * or zk_dist_* form, no list for point shares, and the absent party's share is not recovered.
+ * Errors: those of zk_groth16_prove_checked and of the list. */
+int zk_groth16_prove_checked_parties(zk_ctx* ctx, const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */,
+                                     int nparties, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
+                                     const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r,
+                                     const void* s, int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a,
+                                     void* pi_b, void* pi_c, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d,
+                                     void* stream);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

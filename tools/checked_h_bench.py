@@ -3,6 +3,7 @@ prover, on one GPU, same process, same buffers, alternating -- DESIGN.md 4.11.5.
 the batched repair (below).
 
 usage: python tools/checked_h_bench.py [--quick] [--reps R] [--batch B] [--out FILE]      -> ONE JSON line
+       python tools/checked_h_bench.py --parties [...]      the rows of the party-list forms, below
 
 BN254, l = 2.  Rows (the yardstick of each is the unchanged call in the same run):
   circom_h     zk_circom_h against zk_circom_h_checked at log2_m = 15 (the SHA-256 proof's) and 20, all twelve masks: clean
@@ -14,7 +15,15 @@ BN254, l = 2.  Rows (the yardstick of each is the unchanged call in the same run
   prove        zk_groth16_prove against zk_groth16_prove_checked on the SHA-256 instance, all masks, clean
 A figure is the median over R windows of B back-to-back calls with one stream synchronise behind them (host clock / B; the
 prover is synchronous: B = 1 call per window there); the entry points of a row take turns window by window
-(tools/checked_king_bench.py's method)."""
+(tools/checked_king_bench.py's method).
+
+--parties (party BAD absent; profiles/checked_h_parties_bench.json):
+  repair       three zk_pss_repair_parties calls against one zk_pss_repair_batch_parties of three items on the same compact
+               matrices, clean, at 2^14 and 2^19 chunks; the same `batch_not_slower` condition
+  circom_h     at log2_m = 15 and 20: zk_circom_h; zk_circom_h_checked clean; zk_circom_h_checked with one liar in round 1;
+               zk_circom_h_checked_parties with that liar left out (on the liar's input: its rows are not read) -- the four
+               taking turns; ratios against zk_circom_h
+  prove        zk_groth16_prove against zk_groth16_prove_checked_parties with one party absent, SHA-256 instance"""
 import argparse
 import ctypes as C
 import json
@@ -132,6 +141,102 @@ def repair_row(pp, log_chunks, reps, batch):
             "saved_us": us(ts - tb), "yardstick_spread_us": us(spread), "batch_not_slower": bool(tb <= ts + spread)}
 
 
+def parties_repair_row(pp, log_chunks, reps, batch):
+    n, nch, k = pp.n, 1 << log_chunks, 2 * L
+    rng = np.random.default_rng(200 + log_chunks)
+    S = [p for p in range(n) if p != BAD]
+    np_ = len(S)
+    per = np_ * nch
+    ids = (C.c_uint32 * np_)(*S)
+    words = np.concatenate([honest(pp, nch, rng, 20 + i)[S].reshape(per, 4) for i in range(3)])
+    sh = zk.DeviceBuffer.from_numpy(pp, words)
+    one = [(zk.DeviceBuffer(pp, nch), zk.DeviceBuffer(pp, 4 * nch), zk.DeviceBuffer(pp, 8 * (3 + n))) for _ in range(3)]
+    st, ep, sm = zk.DeviceBuffer(pp, 3 * nch), zk.DeviceBuffer(pp, 12 * nch), zk.DeviceBuffer(pp, 24 * (3 + n))
+
+    def singles():
+        for i in range(3):
+            pp._check(pp.lib.zk_pss_repair_parties(pp.h, sh.ptr + i * per * 32, ids, np_, nch, k, one[i][0].ptr, one[i][1].ptr,
+                                                   one[i][2].ptr, None))
+
+    def batched():
+        pp._check(pp.lib.zk_pss_repair_batch_parties(pp.h, sh.ptr, ids, np_, per, 3, nch, k, st.ptr, ep.ptr, sm.ptr, None))
+
+    (ts, tb), (spread, _) = windows(pp, [singles, batched], reps, batch, spread=True)
+    flat = [int(v) for v in sm.to_numpy(np.uint64)]
+    assert [flat[i * (3 + n):i * (3 + n) + 3] for i in range(3)] == [[nch, 0, 0]] * 3
+    assert all([int(v) for v in o[2].to_numpy(np.uint64)][:3] == [nch, 0, 0] for o in one)
+    return {"log2_chunks": log_chunks, "absent": BAD, "three_singles_us": us(ts), "batch_of_three_us": us(tb),
+            "ratio": round(tb / ts, 3), "saved_us": us(ts - tb), "yardstick_spread_us": us(spread),
+            "batch_not_slower": bool(tb <= ts + spread)}
+
+
+def parties_circom_h_row(pp, log_m, reps, batch):
+    n, nch = pp.n, (1 << log_m) // L
+    rng = np.random.default_rng(300 + log_m)
+    rows = [honest(pp, nch, rng, 1 + k) for k in range(3)]
+    masks = zg.ProofMasks(pp, log_m, 5)
+    mk = C.byref(masks.ct)
+    hu, hc, hl, hp = (pp.alloc_fr(n * nch) for _ in range(4))
+    rc, rl, rp = (api.h_report(pp, log_m) for _ in range(3))
+    S = [p for p in range(n) if p != BAD]
+    ids = (C.c_uint32 * len(S))(*S)
+    q = [zk.DeviceBuffer.from_numpy(pp, r) for r in rows]
+    bad = [r.copy() for r in rows]
+    for r in bad:
+        r[BAD] = raw(rng, nch)
+    qb = [zk.DeviceBuffer.from_numpy(pp, r) for r in bad]
+
+    def unchecked():
+        pp._check(pp.lib.zk_circom_h(pp.h, q[0].ptr, q[1].ptr, q[2].ptr, log_m, mk, 7, hu.ptr, None))
+
+    def checked(src, h, rep):
+        return lambda: pp._check(pp.lib.zk_circom_h_checked(pp.h, src[0].ptr, src[1].ptr, src[2].ptr, log_m, mk, 7, h.ptr,
+                                                            rep.status.ptr, rep.errpos.ptr, rep.summary_d.ptr, None))
+
+    def listed():
+        pp._check(pp.lib.zk_circom_h_checked_parties(pp.h, ids, len(S), qb[0].ptr, qb[1].ptr, qb[2].ptr, log_m, mk, 7, hp.ptr,
+                                                     rp.status.ptr, rp.errpos.ptr, rp.summary_d.ptr, None))
+
+    tu, tc, tl, tp = windows(pp, [unchecked, checked(q, hc, rc), checked(qb, hl, rl), listed], reps, batch)
+    want = pp.unpack(hu, nch).to_numpy().copy()
+    for h in (hc, hl, hp):
+        assert np.array_equal(pp.unpack(h, nch).to_numpy(), want)                       # the honest h
+    assert [x[:3] for x in summaries(pp, rc)] == [[nch, 0, 0]] * 7
+    assert [x[:3] for x in summaries(pp, rl)] == [[0, nch, 0]] * 3 + [[nch, 0, 0]] * 4
+    assert [x[:3] for x in summaries(pp, rp)] == [[nch, 0, 0]] * 6 + [[0, 0, 0]]       # no chunk reaches stage 2
+    return {"log2_m": log_m, "chunks": nch, "absent": BAD, "unchecked_us": us(tu), "checked_clean_us": us(tc),
+            "checked_one_liar_us": us(tl), "checked_parties_liar_out_us": us(tp), "ratio_clean": round(tc / tu, 3),
+            "ratio_one_liar": round(tl / tu, 3), "ratio_parties": round(tp / tu, 3),
+            "parties_over_clean": round(tp / tc, 3), "parties_over_one_liar": round(tp / tl, 3)}
+
+
+def parties_prove_row(pp, reps):
+    from zksaas_amd import sha256_circuit as sc
+    from zksaas_amd.fields import FR
+    p = FR["bn254"]
+    r1, w = sc.build(1, 2, p, pad_wires=sc.REFERENCE_WIRES)
+    rng = np.random.default_rng(42)
+    td = [int.from_bytes(rng.bytes(32), "little") % p for _ in range(5)]
+    crs = zg.Crs(pp, zg.SetupScalars("bn254", r1, *td))
+    wit = zg.Witness(pp, "bn254", r1, w, seed=43)
+    r, s = (int.from_bytes(rng.bytes(32), "little") % p for _ in range(2))
+    masks = zg.ProofMasks(pp, wit.log_m, seed=77)
+    S = [q for q in range(pp.n) if q != BAD]
+    last = {}
+
+    def unchecked():
+        last["u"] = zg.prove(pp, crs, wit, r, s, masks=masks, seed=9)
+
+    def listed():
+        last["p"] = zg.prove(pp, crs, wit, r, s, masks=masks, seed=9, check=True, parties=S)
+
+    tu, tp = windows(pp, [unchecked, listed], reps, 1)
+    nch = (1 << wit.log_m) // L
+    assert [x[:3] for x in summaries(pp, last["p"][1])] == [[nch, 0, 0]] * 6 + [[0, 0, 0]]
+    return {"log2_m": wit.log_m, "absent": BAD, "unchecked_ms": round(tu * 1e3, 3), "checked_parties_ms": round(tp * 1e3, 3),
+            "ratio": round(tp / tu, 3), "overhead_us": us(tp - tu)}
+
+
 def prove_row(pp, reps):
     from zksaas_amd import sha256_circuit as sc
     from zksaas_amd.fields import FR
@@ -165,19 +270,31 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--batch", type=int, default=20)
     ap.add_argument("--no-prove", action="store_true")
+    ap.add_argument("--parties", action="store_true", help="the rows of the party-list forms (DESIGN.md 4.11.6)")
     ap.add_argument("--out")
     a = ap.parse_args()
     pp = zk.PackedSharingParams("bn254", L)
     out = {"tool": "checked_h_bench", "curve": "bn254", "l": L, "reps": a.reps, "batch": a.batch}
+    if a.parties:
+        out["mode"] = "parties"
+        out["repair"] = [parties_repair_row(pp, lg, a.reps, a.batch) for lg in ([14] if a.quick else [14, 19])]
+        out["circom_h"] = [parties_circom_h_row(pp, lg, a.reps, a.batch) for lg in ([15] if a.quick else [15, 20])]
+        if not a.no_prove:
+            out["prove"] = parties_prove_row(pp, a.reps)
+        return emit(out, a.out)
     out["repair"] = [repair_row(pp, lg, a.reps, a.batch) for lg in ([14] if a.quick else [14, 19])]
     out["circom_h"] = [circom_h_row(pp, lg, a.reps, a.batch) for lg in ([15] if a.quick else [15, 20])]
     if not a.no_prove:
         out["prove"] = prove_row(pp, a.reps)
+    emit(out, a.out)
+
+
+def emit(out, path):
     line = json.dumps(out)
     print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
             f.write(line + "\n")
 
 

@@ -38,6 +38,7 @@ SYMBOLS = [
     "zk_pss_unpack_points_robust", "zk_pss_repair_points", "zk_d_msm_checked",
     "zk_pss_repair_batch", "zk_circom_h_checked", "zk_groth16_prove_checked",
     "zk_msm_sum",
+    "zk_pss_repair_batch_parties", "zk_circom_h_checked_parties", "zk_groth16_prove_checked_parties",
 ]
 
 _lib = None
@@ -243,6 +244,10 @@ def load():
     lib.zk_pss_repair_batch.argtypes = [vp, vp, sz, i32, sz, i32, vp, vp, vp, vp]
     lib.zk_circom_h_checked.argtypes = [vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp]
     lib.zk_groth16_prove_checked.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+    lib.zk_pss_repair_batch_parties.argtypes = [vp, vp, ids, i32, sz, i32, sz, i32, vp, vp, vp, vp]
+    lib.zk_circom_h_checked_parties.argtypes = [vp, ids, i32, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp]
+    lib.zk_groth16_prove_checked_parties.argtypes = [vp, ids, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp,
+                                                     vp, vp]
     lib.zk_points_subgroup_check.argtypes = [vp, i32, vp, sz, vp, vp]
     lib.zk_points_decompress_checked.argtypes = [vp, i32, vp, sz, vp, vp, vp]
     lib.zk_groth16_verify_bytes.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]

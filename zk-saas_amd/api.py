@@ -225,17 +225,26 @@ class PackedSharingParams(Context):
                                                        _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
-    def repair_batch(self, shares_d, nitems, nchunks, dimension=None, item_stride=None, stream=None):
+    def repair_batch(self, shares_d, nitems, nchunks, dimension=None, item_stride=None, stream=None, parties=None):
         """zk_pss_repair_batch: repair of nitems share matrices [n][nchunks], item i at element i * item_stride of shares_d
         (default n * nchunks: back to back), with one scan and one decoder launch for all of them.  Returns ONE RobustUnpack
         with an item axis: status and errpos are [nitems][nchunks] (`nchunks` of the report counts all of them), `summaries`
-        holds one summary per item, `nitems` is set and `out` is shares_d."""
+        holds one summary per item, `nitems` is set and `out` is shares_d.
+        With `parties` (ascending ids, one list for all items) every item is a compact matrix [len(parties)][nchunks] as
+        repair(parties=...) takes it (default stride len(parties) * nchunks) and the call is zk_pss_repair_batch_parties."""
         k = 2 * self.l if dimension is None else int(dimension)
-        stride = self.n * nchunks if item_stride is None else int(item_stride)
-        r = self._report(max(0, nitems) * nchunks, k, words=max(1, nitems))
+        rows = self.n if parties is None else len(parties)
+        stride = rows * nchunks if item_stride is None else int(item_stride)
+        r = self._report(max(0, nitems) * nchunks, k, parties, words=max(1, nitems))
         r.out, r.nitems = shares_d, nitems
-        self._check(self.lib.zk_pss_repair_batch(self.h, _ptr(shares_d), stride, nitems, nchunks, k, _ptr(r.status),
-                                                 _ptr(r.errpos), _ptr(r.summary_d), stream))
+        if parties is None:
+            self._check(self.lib.zk_pss_repair_batch(self.h, _ptr(shares_d), stride, nitems, nchunks, k, _ptr(r.status),
+                                                     _ptr(r.errpos), _ptr(r.summary_d), stream))
+        else:
+            arr = (C.c_uint32 * len(r.parties))(*r.parties)
+            self._check(self.lib.zk_pss_repair_batch_parties(self.h, _ptr(shares_d), arr, len(r.parties), stride, nitems,
+                                                             nchunks, k, _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d),
+                                                             stream))
         return r
 
     def unpack_points_robust(self, group, shares_d, nchunks, dimension=None, want_out=True, stream=None):
@@ -409,10 +418,15 @@ def h_report(pp, log2_m):
     return r
 
 
-def circom_h(pp, wit_or_bufs, masks=None, seed=0, check=False, log2_m=None, stream=None):
+def circom_h(pp, wit_or_bufs, masks=None, seed=0, check=False, log2_m=None, stream=None, parties=None):
     """zk_circom_h (ext_wit.rs:104-181) on the QAP share vectors of a Witness (`.qap`, `.log_m`) or on three device buffers
     [n][m/l] with log2_m given.  masks: a zk_groth16_masks structure, an object that holds one as `.ct`, or None.
-    Returns h [n][m/l]; with check=True zk_circom_h_checked and (h, report), the report as h_report's."""
+    Returns h [n][m/l]; with check=True zk_circom_h_checked and (h, report), the report as h_report's.
+    parties (with check=True only; ascending ids, all n or n - 1 of them): zk_circom_h_checked_parties -- only the listed
+    parties' words reach the kings, the rows of the absent party in every input and in-mask are not read; with n - 1
+    parties item 6 is not checked and its summary is all zeros."""
+    if parties is not None and not check:
+        raise ValueError("a party list needs check=True (the unchecked chain takes all n parties)")
     if hasattr(wit_or_bufs, "qap"):
         qap, log2_m = wit_or_bufs.qap, wit_or_bufs.log_m
     else:
@@ -427,8 +441,15 @@ def circom_h(pp, wit_or_bufs, masks=None, seed=0, check=False, log2_m=None, stre
         return h
     rep = h_report(pp, log2_m)
     rep.out = h
-    pp._check(pp.lib.zk_circom_h_checked(pp.h, _ptr(qap[0]), _ptr(qap[1]), _ptr(qap[2]), log2_m, mk, seed, h.ptr,
-                                         _ptr(rep.status), _ptr(rep.errpos), _ptr(rep.summary_d), stream))
+    if parties is None:
+        pp._check(pp.lib.zk_circom_h_checked(pp.h, _ptr(qap[0]), _ptr(qap[1]), _ptr(qap[2]), log2_m, mk, seed, h.ptr,
+                                             _ptr(rep.status), _ptr(rep.errpos), _ptr(rep.summary_d), stream))
+    else:
+        rep.parties = list(parties)
+        arr = (C.c_uint32 * len(rep.parties))(*rep.parties)
+        pp._check(pp.lib.zk_circom_h_checked_parties(pp.h, arr, len(rep.parties), _ptr(qap[0]), _ptr(qap[1]), _ptr(qap[2]),
+                                                     log2_m, mk, seed, h.ptr, _ptr(rep.status), _ptr(rep.errpos),
+                                                     _ptr(rep.summary_d), stream))
     return h, rep
 
 

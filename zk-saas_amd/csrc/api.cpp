@@ -937,6 +937,20 @@ int zk_circom_h_checked(zk_ctx* ctx, const void* qap_a_d, const void* qap_b_d, c
   return e->circom_h_checked(qap_a_d, qap_b_d, qap_c_d, log2_m, masks, seed, h_share_d, status_d, errpos_d, summary_d,
                              S(stream));
 }
+int zk_pss_repair_batch_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, size_t item_stride,
+                                int nitems, size_t nchunks, int dimension, uint8_t* status_d, uint32_t* errpos_d,
+                                uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_repair_batch_parties(shares_d, parties, nparties, item_stride, nitems, nchunks, dimension, status_d, errpos_d,
+                                     summary_d, S(stream));
+}
+int zk_circom_h_checked_parties(zk_ctx* ctx, const uint32_t* parties, int nparties, const void* qap_a_d, const void* qap_b_d,
+                                const void* qap_c_d, int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* h_share_d,
+                                uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->circom_h_checked_parties(parties, nparties, qap_a_d, qap_b_d, qap_c_d, log2_m, masks, seed, h_share_d, status_d,
+                                     errpos_d, summary_d, S(stream));
+}
 int zk_groth16_prove_checked(zk_ctx* ctx, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
                              const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
                              int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
@@ -944,6 +958,15 @@ int zk_groth16_prove_checked(zk_ctx* ctx, const zk_crs_share* crs, const void* q
   CTX_OR_FAIL();
   return e->groth16_prove_checked(crs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m, masks, seed, pi_a,
                                   pi_b, pi_c, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_groth16_prove_checked_parties(zk_ctx* ctx, const uint32_t* parties, int nparties, const zk_crs_share* crs,
+                                     const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, const void* a_share_d,
+                                     const void* ax_share_d, const void* r, const void* s, int log2_m,
+                                     const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                                     uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->groth16_prove_checked_parties(parties, nparties, crs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m,
+                                          masks, seed, pi_a, pi_b, pi_c, status_d, errpos_d, summary_d, S(stream));
 }
 
 // ---- the verifier (pairing.hpp): the kernels are compiled per curve in pairing_<curve>.hip ----

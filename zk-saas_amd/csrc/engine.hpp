@@ -436,6 +436,14 @@ class IEngine {
   // zk_pss_repair_batch: pss_repair of nitems matrices, item_stride elements apart, with one scan and one decoder launch
   virtual int pss_repair_batch(void* shares, size_t item_stride, int nitems, size_t nchunks, int dimension, uint8_t* status,
                                uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  // zk_pss_repair_batch_parties: pss_repair_parties of nitems compact matrices [nparties][nchunks] of one party list
+  virtual int pss_repair_batch_parties(void* shares, const uint32_t* parties, int nparties, size_t item_stride, int nitems,
+                                       size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                                       hipStream_t st) = 0;
+  // circom_h_checked when only the listed parties' words reach the kings (engine_groth16.inc.hpp)
+  virtual int circom_h_checked_parties(const uint32_t* parties, int nparties, const void* qa, const void* qb, const void* qc,
+                                       int log_m, const zk_groth16_masks* masks, uint64_t seed, void* h, uint8_t* status,
+                                       uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
   virtual int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* masks,
                        uint64_t seed, void* h, hipStream_t st) = 0;
   // circom_h with its seven king words repaired first; status / errpos [7][m/l], summary [7][3 + n] (engine_gao.inc.hpp)
@@ -447,6 +455,12 @@ class IEngine {
                                     const void* a_share, const void* ax_share, const void* r, const void* s, int log_m,
                                     const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
                                     uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  // groth16_prove_checked from the words and MSM contributions of a party list (all n parties or n - 1 of them)
+  virtual int groth16_prove_checked_parties(const uint32_t* parties, int nparties, const zk_crs_share* crs, const void* qa,
+                                            const void* qb, const void* qc, const void* a_share, const void* ax_share,
+                                            const void* r, const void* s, int log_m, const zk_groth16_masks* masks,
+                                            uint64_t seed, void* pi_a, void* pi_b, void* pi_c, uint8_t* status,
+                                            uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
   virtual int groth16_prove(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
                             const void* a_share, const void* ax_share, const void* r, const void* s, int log_m,
                             const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,

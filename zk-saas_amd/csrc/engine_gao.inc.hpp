@@ -53,6 +53,54 @@
                                      st);
   }
 
+  // ---------------------------------------------------------------- zk_pss_repair_batch_parties
+  // nitems compact matrices [nparties][nchunks] of ONE party list, item i at shares + i * item_stride: pss_repair_parties of
+  // each with the launches of pss_repair_batch and the two tables of the list, put into working memory once per call.  The
+  // refusals are pss_repair_parties' (list, dimension, too few shares) and pss_repair_batch's; a refusal writes nothing.
+  int repair_list_check(const uint32_t* parties, int np, int dimension, uint32_t* ids) {
+    if (np <= 0 || np > n) return fail(ZK_ERR_BAD_INPUT, "bad party count");
+    for (int i = 0; i < np; i++) {
+      ids[i] = parties ? parties[i] : (uint32_t)i;
+      if (ids[i] >= (uint32_t)n || (i > 0 && ids[i] <= ids[i - 1]))
+        return fail(ZK_ERR_BAD_INPUT, "party ids must be ascending and < n");
+    }
+    if (dimension < 1 || dimension > n - 1) return fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
+    if (np <= dimension) return fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
+    return ZK_OK;
+  }
+  int pss_repair_batch_parties(void* shares, const uint32_t* parties, int np, size_t item_stride, int nitems, size_t nchunks,
+                               int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    uint32_t ids[GAO_MAX_N];
+    int rc = repair_list_check(parties, np, dimension, ids);
+    if (rc) return rc;
+    if (np == n) return pss_repair_batch(shares, item_stride, nitems, nchunks, dimension, status, errpos, summary, st);
+    if (nitems < 1 || nitems > KING_BATCH) return fail(ZK_ERR_BAD_INPUT, "bad repair batch");
+    if (nchunks == 0) return ZK_OK;
+    if (!shares || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (!gao_batch_fits((uint64_t)nitems, nchunks)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
+    if (item_stride < (size_t)np * nchunks) return fail(ZK_ERR_BAD_INPUT, "item stride below nparties * nchunks");
+    DevBuf& wk = ws(st)->hwork;
+    ZK_HIP(wk.ensure(gao_batch_parties_work<Fr>(n, nitems, nchunks).bytes));
+    return gao_repair_batch_parties_run<FrP>(this, wk.p, l, shares, ids, np, item_stride, nitems, nchunks, dimension, status,
+                                             errpos, summary, st);
+  }
+  // the in-mask rows of a list for up to three compact words [np][width], item_stride apart, in one launch: row r of item y
+  // becomes x * k (with `scale`) + row ids[r] of masks[y]; a null mask skips the item (vec_add_list_rows_kernel, ntt.hpp)
+  int add_list_rows(Fr* x, size_t item_stride, const Fr* const* masks, int items, const uint32_t* ids, int np, bool scale,
+                    const Fr& k, size_t width, hipStream_t st) {
+    ListMasks<Fr> lm{};
+    bool any = false;
+    for (int y = 0; y < items && y < 3; y++) any = (lm.mask[y] = masks[y]) || any;
+    if (!any || !width) return ZK_OK;
+    uint32_t listed = 0;
+    for (int i = 0; i < np; i++) listed |= 1u << ids[i];
+    const size_t cnt = width * (size_t)np;
+    vec_add_list_rows_kernel<Fr><<<dim3((unsigned)((cnt + 255) / 256), (unsigned)items), dim3(256), 0, st>>>(
+        x, item_stride, lm, listed, scale ? 1 : 0, k, width, (size_t)np);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+  }
+
   // ---------------------------------------------------------------- checked king rounds (all n parties)
   // Each repairs the word the king receives, then runs the unchecked king launch on the repaired matrix.  A failed chunk is
   // no error return: its shares go to the king as received and the caller reads summary[2].

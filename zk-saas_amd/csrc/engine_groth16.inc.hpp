@@ -70,6 +70,8 @@
     uint8_t* status;        // [7][m/l]
     uint32_t* errpos;       // [7][m/l] or null
     uint64_t* summary;      // [7][3 + n] or null
+    const uint32_t* ids = nullptr;      // zk_*_checked_parties: the party list (checked_list has passed it), np < n of them;
+    int np = 0;                         // 0: all n parties
   };
   // the words of a round in place: W + k * per is fft1 of vector k; masked[k]: item k has an in-mask
   int h_round_words(Fr* W, const zk_groth16_masks* mk, int first, int log_m, int inverse, size_t per, bool* masked,
@@ -151,6 +153,121 @@
     if (mk && mk->degred_in && (rc = vec_add(W1, mk->degred_in, per, st))) return rc;
     if ((rc = repair(W1, 6, 1, 4 * l - 1))) return rc;
     return deg_red_np(W1, nullptr, nullptr, n, Lc, seed + 6, (Fr*)h, mk ? (const Fr*)mk->degred_out : nullptr, st);
+  }
+
+  // ---------------------------------------------------------------- the checked h chain with a party list
+  // (zk_circom_h_checked_parties) circom_h_checked when only the words of the listed parties reach the kings: all n parties
+  // (the chain above) or n - 1 of them (checked_list).  A round's three words are COMPACT, [np][m/l] at W + k * per: the
+  // first NTT pass reads one pointer per listed row, the in-mask rows of the list come from one add_list_rows launch, one
+  // pss_repair_batch_parties of 3 items runs at dimension 2l, and the kings take the list (umat_for(ids, np)).  The batched
+  // king reads np rows at the row pitch m/l from in + k * stride and writes n rows at out + k * stride, so the compact layout
+  // at the stride of the full one goes through ONE batched launch, under the same condition as king3_checked.
+  // At l <= 4 a round's 3 np row pointers go into one NttSrc as 3 n - 1 <= 47 vectors: vector k n + r is listed row r of
+  // word k, and the one row of an item beyond its np -- never read by the repair or the king -- transforms listed row 0 once
+  // more, so the three words of a round stay one set of NTT launches.  At l = 8 (93 pointers) one word per call.
+  // Item 6: with n - 1 parties the dimension 4l - 1 leaves no redundancy -- NOT CHECKED: the compact word goes to deg_red with
+  // the list unrepaired, its status and errpos bytes are 0 and its summary row is all zeros (no chunk checked; a clean
+  // item reads [m/l, 0, 0, ..]).
+  int h_list_words(Fr* W, const Fr* const* src, int log_m, int inverse, size_t per, const uint32_t* ids, int np,
+                   hipStream_t st) {
+    const size_t Lc = ((size_t)1 << log_m) / l;
+    int rc;
+    if (3 * n - 1 <= NTT_SRC_MAX) {
+      NttSrc<Fr> s{};
+      s.per = 1;
+      for (int k = 0; k < 3; k++)
+        for (int r = 0; r < n && k * n + r < 3 * n - 1; r++) s.p[k * n + r] = src[k] + (size_t)ids[r < np ? r : 0] * Lc;
+      return fft1_src(W, log_m, inverse, (size_t)(3 * n - 1), nullptr, st, s);
+    }
+    static_assert(GAO_MAX_N <= NTT_SRC_MAX, "one pointer per listed row");
+    for (int k = 0; k < 3; k++) {
+      NttSrc<Fr> s{};
+      s.per = 1;
+      for (int r = 0; r < np; r++) s.p[r] = src[k] + (size_t)ids[r] * Lc;
+      if ((rc = fft1_src(W + k * per, log_m, inverse, (size_t)np, nullptr, st, s))) return rc;
+    }
+    return ZK_OK;
+  }
+  int king3_list(const Fr* in, const zk_groth16_masks* mk, int first, int log_m, int inverse, const void* g, int rearrange,
+                 uint64_t seed, Fr* out, size_t per, const bool* masked, const uint32_t* ids, int np, hipStream_t st) {
+    const Fr* U = nullptr;
+    int rc = umat_for(ids, np, &U);
+    if (rc) return rc;
+    KingBatch<Fr> kb{};
+    kb.stride = per;
+    for (int k = 0; k < 3; k++) kb.out_mask[k] = mk ? (const Fr*)mk->fft_out[first + k] : nullptr;
+    if (!inverse || (masked[0] == masked[1] && masked[1] == masked[2]))
+      return king_dispatch_batch(in, kb, 3, np, log_m, inverse, U, g, inverse && !masked[0] ? 1 : 0, rearrange, seed, out, false,
+                                 st);
+    for (int k = 0; k < 3; k++) {
+      rc = king_dispatch(in + k * per, nullptr, np, log_m, inverse, U, g, masked[k] ? 0 : 1, rearrange, seed + k, out + k * per,
+                         kb.out_mask[k], false, st);
+      if (rc) return rc;
+    }
+    return ZK_OK;
+  }
+  int circom_h_checked_parties(const uint32_t* parties, int np, const void* qa, const void* qb, const void* qc, int log_m,
+                               const zk_groth16_masks* mk, uint64_t seed, void* h, uint8_t* status, uint32_t* errpos,
+                               uint64_t* summary, hipStream_t st) override {
+    return circom_h_checked_parties_ws(parties, np, qa, qb, qc, log_m, mk, seed, h, HReport{status, errpos, summary},
+                                       ws(st)->hwork, st);
+  }
+  int circom_h_checked_parties_ws(const uint32_t* parties, int np, const void* qa, const void* qb, const void* qc, int log_m,
+                                  const zk_groth16_masks* mk, uint64_t seed, void* h, const HReport& rep, DevBuf& hwork,
+                                  hipStream_t st) {
+    uint32_t ids[GAO_MAX_N];
+    int rc = checked_list(parties, np, 2 * l, ids);
+    if (rc) return rc;
+    if (np == n) return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, h, rep, hwork, st);
+    int log_l = ilog2(l);
+    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
+    if (!qa || !qb || !qc || !h || !rep.status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
+    if (!gao_batch_fits(3, Lc)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
+    const size_t vec_bytes = 6 * per * sizeof(Fr);
+    ZK_HIP(hwork.ensure(vec_bytes + gao_batch_parties_work<Fr>(n, 3, Lc).bytes));
+    Fr* W0 = (Fr*)hwork.p;
+    Fr* W1 = W0 + 3 * per;
+    void* gwk = (char*)hwork.p + vec_bytes;
+    const Fr minv = Fr::from_u64((uint64_t)1 << log_m).inverse();
+    // the words of a round in W0: the transform of the listed rows of src[0..2], the list's in-mask rows, the repair
+    auto round = [&](const Fr* const* src, int first, int inverse, bool* masked) {
+      int r = h_list_words(W0, src, log_m, inverse, per, ids, np, st);
+      if (r) return r;
+      const Fr* masks[3];
+      for (int k = 0; k < 3; k++) masked[k] = (masks[k] = mk ? (const Fr*)mk->fft_in[first + k] : nullptr) != nullptr;
+      if ((r = add_list_rows(W0, per, masks, 3, ids, np, inverse != 0, minv, Lc, st))) return r;
+      return gao_repair_batch_parties_run<FrP>(this, gwk, l, W0, ids, np, per, 3, Lc, 2 * l, rep.status + first * Lc,
+                                               rep.errpos ? rep.errpos + first * Lc : nullptr,
+                                               rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr, st);
+    };
+    Fr w2m = root_of_unity(log_m + 1);
+    bool masked[3];
+    // round 1: 3 x d_ifft(rearrange = true, g = w_2m)   (ext_wit.rs:127-159)
+    const Fr* q3[3] = {(const Fr*)qa, (const Fr*)qb, (const Fr*)qc};
+    if ((rc = round(q3, 0, 1, masked))) return rc;
+    if ((rc = king3_list(W0, mk, 0, log_m, 1, &w2m, 1, seed, W1, per, masked, ids, np, st))) return rc;
+    // round 2: 3 x d_fft(rearrange = false)             (ext_wit.rs:161-170): out of place, W1's listed rows into W0
+    const Fr* w3[3] = {W1, W1 + per, W1 + 2 * per};
+    if ((rc = round(w3, 3, 0, masked))) return rc;
+    if ((rc = king3_list(W0, mk, 3, log_m, 0, nullptr, 0, seed + 3, W1, per, masked, ids, np, st))) return rc;
+    // a*b - c + in_mask over the listed rows, compact in W0, then deg_red with the list   (ext_wit.rs:173-179): the one
+    // absent party e splits the rows into those below it and those above, which move up by one
+    const uint32_t e = ids[np - 1] == (uint32_t)np - 1 ? (uint32_t)np : [&] {
+      uint32_t r = 0;
+      while (ids[r] == r) r++;
+      return r;
+    }();
+    if ((rc = vec_mul_sub(W0, W1, W1 + per, W1 + 2 * per, e * Lc, st))) return rc;
+    const size_t up = (size_t)(e + 1) * Lc;
+    if ((rc = vec_mul_sub(W0 + e * Lc, W1 + up, W1 + per + up, W1 + 2 * per + up, ((size_t)np - e) * Lc, st))) return rc;
+    const Fr* dmask[1] = {mk ? (const Fr*)mk->degred_in : nullptr};
+    if ((rc = add_list_rows(W0, per, dmask, 1, ids, np, false, minv, Lc, st))) return rc;
+    ZK_HIP(hipMemsetAsync(rep.status + 6 * Lc, 0, Lc, st));
+    if (rep.errpos) ZK_HIP(hipMemsetAsync(rep.errpos + 6 * Lc, 0, Lc * 4, st));
+    if (rep.summary) ZK_HIP(hipMemsetAsync(rep.summary + (size_t)6 * (3 + n), 0, (size_t)(3 + n) * 8, st));
+    return deg_red_np(W0, nullptr, ids, np, Lc, seed + 6, (Fr*)h, mk ? (const Fr*)mk->degred_out : nullptr, st);
   }
 
   // circom_h of `nb` proofs as ONE launch chain (zk_groth16_prove_batch): the 3 nb vectors go through every NTT pass,
@@ -254,9 +371,13 @@
     P1 in1[5], s_in0, r_in1;                        // in-mask sums (index 2 unused) and their multiples
     P2 in2;
     std::vector<P1> s_om0, r_om1;                   // per party: s * out_mask_A[p], r * out_mask_B1[p]
+    std::vector<Fr> coef;                           // a proof from a party list: the king's coefficients of the five MSM
+                                                    // rounds by party id, [n], zero at an absent party (coefs_for); empty:
+                                                    // all n parties, the MSM's own tables
     Status err;                                     // first failure reported by a task (tasks must not touch `last`)
     std::mutex emu;
     const zk_groth16_masks* masks() const { return has_mk ? &mk : nullptr; }
+    const Fr* coefs() const { return coef.empty() ? nullptr : coef.data(); }
     MsmSums sums() const {
       return {xyzz_add_ni(S, in1[0]), r_zero ? P1::identity() : xyzz_add_ni(H, in1[1]), xyzz_add_ni(W, in1[3]),
               xyzz_add_ni(U, in1[4]), xyzz_add_ni(V0, in2)};
@@ -289,6 +410,7 @@
     ProveJob() : JobCore(false) {}
     ProofTerms pt;
     bool gate_sorts = false, sharded = false;
+    DevBuf coef_d;                      // the device copy of pt.coef while the proof of a party list is in flight
     std::atomic<int> sorted_cnt{0};     // witness MSMs of this proof whose sort has been enqueued and recorded (MsmGate)
     int k = 0;
     uint32_t cmask3 = 0;
@@ -470,6 +592,7 @@
     j.first = first;
     j.count = count;
     j.err = Status{};
+    j.coef.clear();
     j.S = j.H = j.W = j.U = j.sS = j.rH = j.s_in0 = j.r_in1 = P1::identity();
     j.V0 = j.in2 = P2::identity();
     for (int k = 0; k < 5; k++) j.in1[k] = P1::identity();
@@ -597,6 +720,21 @@
     // size (550-555 vs 571-596), S and H as two MSMs with their own sorts (391 vs 464), raised issue priority or shorter
     // lane ranges for the U-MSM (541-544 vs 591-594).
     const Fr* cf = msm_.coef_d_ + first;
+    const Fr* cu = msm_.coef_d_;
+    // a party list (zk_groth16_prove_checked_parties): the five MSM rounds and the host in-mask terms take the list's
+    // coefficients, zero at the absent party -- a per-job vector in place of the tables; every launch keeps its shape, and
+    // the bucket-sharing coefficients r * coef_p follow from it (MsmShare::scale1 multiplies what the launch is given)
+    const bool listed = report && report->np > 0 && report->np < n;
+    if (listed) {
+      if (!full || first != 0 || count != n) return fail(ZK_ERR_BAD_INPUT, "a party list needs the full proof");
+      std::vector<Fr> c;
+      if ((rc = coefs_for(report->ids, report->np, c))) return rc;
+      j.pt.coef.assign(n, Fr::zero());
+      for (int i = 0; i < report->np; i++) j.pt.coef[report->ids[i]] = c[i];
+      ZK_HIP(j.coef_d.ensure((size_t)n * sizeof(Fr)));
+      ZK_HIP(hipMemcpy(j.coef_d.p, j.pt.coef.data(), (size_t)n * sizeof(Fr), hipMemcpyHostToDevice));
+      cf = cu = (const Fr*)j.coef_d.p;
+    }
     MsmGate gate{};
     // Large domains (2^h_first_log_m_ and up; 2^20 by default): circom_h and the SORT of the U-MSM that consumes it go
     // first, and the accumulate kernels of the witness MSMs wait for them (they still sort beside circom_h).  A proof of
@@ -624,6 +762,9 @@
     // report (zk_groth16_prove_checked): the checked h chain on the same stream with the same work buffers, its report into
     // the caller's buffers -- complete once the job's join has waited for the U chain; nothing else of the proof differs
     auto h_chain = [&](hipStream_t hs) {
+      if (listed)
+        return circom_h_checked_parties_ws(report->ids, report->np, qa, qb, qc, log_m, mk, seed, J->hshare.p, *report, J->hwork,
+                                           hs);
       if (report) return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, *report, J->hwork, hs);
       return circom_h_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, J->hwork, hs);
     };
@@ -662,7 +803,7 @@
       rc = h_chain(streams_[5]);
       if (rc) return rc;
       rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
-                                      msm_.coef_d_, crs->len_u, streams_[5], &j.msm[ROLE_U], nullptr, u_gate(j));
+                                      cu, crs->len_u, streams_[5], &j.msm[ROLE_U], nullptr, u_gate(j));
       if (rc) return rc;
       hu_done = true;
     }
@@ -692,7 +833,7 @@
       if (rc) return rc;
       host_span(PROF_HOST_H);
       rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
-                                      msm_.coef_d_, crs->len_u, hs, &j.msm[ROLE_U], nullptr, MsmGate{}, nullptr,
+                                      cu, crs->len_u, hs, &j.msm[ROLE_U], nullptr, MsmGate{}, nullptr,
                                       sh_u.n_absorb ? &sh_u : nullptr);
       if (rc) return rc;
       submit_host_terms(&j.pt, j.fut);
@@ -728,9 +869,9 @@
         const void* im = mk->msm_in[k];
         fut.push_back(pool_->submit([this, J, k, im, first, count]() {
           if (k == 2) {
-            J->in2 = msm_.template mask_term<Fq2_>(im, first, count);
+            J->in2 = msm_.template mask_term<Fq2_>(im, first, count, J->coefs());
           } else {
-            J->in1[k] = msm_.template mask_term<Fq_>(im, first, count);
+            J->in1[k] = msm_.template mask_term<Fq_>(im, first, count, J->coefs());
             if (k == 0 && J->full) J->s_in0 = host_scalar_mul<FrP, Fq_>(J->in1[0], J->s);
             if (k == 1 && J->full) J->r_in1 = host_scalar_mul<FrP, Fq_>(J->in1[1], J->r);
           }
@@ -868,6 +1009,26 @@
     const HReport report{status, errpos, summary};
     int h = -1;
     int rc = prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, &h, &report);
+    if (rc) return rc;
+    return groth16_wait(h, pi_a, pi_b, pi_c);
+  }
+  // zk_groth16_prove_checked_parties: the checked proof from the words and MSM contributions of a party list -- the h chain
+  // of circom_h_checked_parties, the list's coefficients in the five MSM rounds and the host in-mask terms (prove_begin_impl)
+  int groth16_prove_checked_parties(const uint32_t* parties, int np, const zk_crs_share* crs, const void* qa, const void* qb,
+                                    const void* qc, const void* a_share, const void* ax_share, const void* r_, const void* s_,
+                                    int log_m, const zk_groth16_masks* mk, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                                    uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    uint32_t ids[GAO_MAX_N];
+    int rc = checked_list(parties, np, 2 * l, ids);
+    if (rc) return rc;
+    if (np == n)
+      return groth16_prove_checked(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, pi_a, pi_b, pi_c, status, errpos,
+                                   summary, st);
+    if (!pi_a || !pi_b || !pi_c || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    HReport report{status, errpos, summary};
+    report.ids = ids, report.np = np;
+    int h = -1;
+    rc = prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, &h, &report);
     if (rc) return rc;
     return groth16_wait(h, pi_a, pi_b, pi_c);
   }

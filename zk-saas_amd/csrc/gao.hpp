@@ -515,9 +515,37 @@ constexpr size_t gao_batch_work_bytes(int n, int nitems, size_t nchunks) {
   return gao_batch_head(n, nitems) + (size_t)nitems * nchunks * 4;
 }
 
+// ---------------------------------------------------------------- a batch of words of one party list (zk_pss_repair_batch_parties)
+// Item i is a compact matrix [nparties][nchunks] at shares + i * item_stride, row r the shares of parties[r]; the list, and so
+// the two tables of zk_pss_repair_parties (GaoAbsent, GaoInvLambda), are the same for every item.  Working memory: the head of
+// a batch (the count, the items' summary words), the two tables, then the one list of (item, chunk) entries.  Byte offsets.
+struct GaoBatchPartiesWork {
+  size_t tab, inv, list, bytes;
+};
+ZK_HD GaoBatchPartiesWork gao_batch_parties_work(int n, int nitems, size_t nchunks, size_t tab_size, size_t inv_size) {
+  GaoBatchPartiesWork w;
+  w.tab = gao_batch_head(n, nitems);
+  w.inv = w.tab + (tab_size + 31) / 32 * 32;
+  w.list = w.inv + (inv_size + 31) / 32 * 32;
+  w.bytes = w.list + (size_t)nitems * nchunks * 4;
+  return w;
+}
+template <class F>
+ZK_HD GaoBatchPartiesWork gao_batch_parties_work(int n, int nitems, size_t nchunks) {
+  return gao_batch_parties_work(n, nitems, nchunks, sizeof(GaoAbsent<F>), sizeof(GaoInvLambda<F>));
+}
+
 #if defined(__HIPCC__)
 class IEngine;
 struct DevBuf;
+// zk_pss_repair_batch_parties: nitems compact matrices [nparties][nchunks] of the party list ids[0 .. np - 1] (ascending, below
+// 4 l, dimension < np < 4 l), item_stride elements apart, in place; status and errpos [nitems][nchunks], summary
+// [nitems][3 + n] or null.  wk: working memory of gao_batch_parties_work<Fr>(4 l, nitems, nchunks).bytes bytes that the caller
+// holds; the argument checks, and the all-parties case, are the caller's (engine_gao.inc.hpp).
+template <class FrP>
+int gao_repair_batch_parties_run(IEngine* e, void* wk, int l, void* shares, const uint32_t* ids, int np, size_t item_stride,
+                                 int nitems, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos,
+                                 uint64_t* summary, hipStream_t st);
 // zk_pss_repair_batch: nitems share matrices [n][nchunks], item_stride elements apart, in place; status and errpos
 // [nitems][nchunks], summary [nitems][3 + n] or null.  wk: working memory of gao_batch_work_bytes(4 l, nitems, nchunks) bytes
 // that the caller holds (behind the words of a chain, for instance); the argument checks are the caller's (engine_gao.inc.hpp).

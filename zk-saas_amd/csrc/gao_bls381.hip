@@ -1,4 +1,4 @@
-// zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair, zk_pss_repair_parties and zk_pss_repair_batch over the scalar field of this curve (gao_impl.hpp).
+// zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair, zk_pss_repair_parties, zk_pss_repair_batch and zk_pss_repair_batch_parties over the scalar field of this curve (gao_impl.hpp).
 #include "curves.hpp"
 #include "gao_impl.hpp"
 
@@ -12,4 +12,6 @@ template int gao_repair_parties_run<Bls381Fr>(IEngine*, DevBuf&, int, void*, con
                                         uint64_t*, hipStream_t);
 template int gao_repair_batch_run<Bls381Fr>(IEngine*, void*, int, void*, size_t, int, size_t, int, uint8_t*, uint32_t*, uint64_t*,
                                       hipStream_t);
+template int gao_repair_batch_parties_run<Bls381Fr>(IEngine*, void*, int, void*, const uint32_t*, int, size_t, int, size_t, int, uint8_t*,
+                                              uint32_t*, uint64_t*, hipStream_t);
 }  // namespace zk

@@ -1,4 +1,5 @@
-// Kernels and host drivers of zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair, zk_pss_repair_parties and zk_pss_repair_batch (gao.hpp says what they compute).  Included
+// Kernels and host drivers of zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair, zk_pss_repair_parties,
+// zk_pss_repair_batch and zk_pss_repair_batch_parties (gao.hpp says what they compute).  Included
 // by gao_<curve>.hip only.  Each stage is one body with two kernels: the all-parties one, and the one for a party list (ER).
 //   stage 1  one lane per chunk (two at l = 8): the n shares are loaded once, transformed in registers, coefficients k .. n - 1 tested; a
 //            clean chunk gets its secrets (and message) and status 0, a dirty one is appended to a compact list
@@ -195,6 +196,18 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_scan_batch_kernel(const GaoCo
                                      errpos ? errpos + item * nchunks : nullptr, wk, nullptr, 0, nullptr, 0,
                                      gao_batch_entry(item, 0, (uint32_t)nchunks));
 }
+// zk_pss_repair_batch_parties: the scan of item blockIdx.y of a batch of compact matrices of one party list -- the load of
+// gao_scan_parties_kernel (the row of party p is the popcount of `listed` below p), the item offsets and entry0 of the batch
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_scan_batch_parties_kernel(
+    const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab, const Fp<P>* __restrict__ shares, size_t item_stride, size_t nchunks,
+    int k, int rho, uint32_t listed, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
+  const uint32_t item = blockIdx.y;
+  wk.summary += (size_t)item * (3 + 4 * L);
+  gao_stage1_body<P, L, true, true>(c, shares + item * item_stride, nchunks, k, nullptr, nullptr, status + item * nchunks,
+                                    errpos ? errpos + item * nchunks : nullptr, wk, &ab, rho, nullptr, listed,
+                                    gao_batch_entry(item, 0, (uint32_t)nchunks));
+}
 // k: the caller's dimension
 template <class P, int L>
 __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
@@ -212,7 +225,8 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
 // the inverses, read at a run-time index by a lane that stores
 // BATCH (zk_pss_repair_batch): a list entry names (item, chunk) and is the chunk's index in status and errpos; the item's matrix
 // is at shares + item * item_stride and its summary words at wk.summary + item * (3 + n), added to chunk by chunk -- the
-// entries of a lane's walk belong to any items in any order
+// entries of a lane's walk belong to any items in any order.  With ER (zk_pss_repair_batch_parties) the item's matrix is the
+// compact one of the party list: the load and the store address row `row` of it, the table is the same for every item
 template <class P, bool REPAIR>
 using GaoSharesPtr = std::conditional_t<REPAIR, Fp<P>*, const Fp<P>* __restrict__>;
 template <class P>
@@ -229,7 +243,7 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
                                                 const GaoAbsent<Fp<P>>* __restrict__ tab,
                                                 const Fp<P>* __restrict__ ilam = nullptr, size_t item_stride = 0) {
   using F = Fp<P>;
-  static_assert(!BATCH || (REPAIR && !ER), "the batch is the all-parties repair");
+  static_assert(!BATCH || REPAIR, "a batch is a repair");
   const uint32_t cnt = *wk.count;
   const uint32_t gpb = GAO_THREADS / n, stride = gridDim.x * gpb;
   if (blockIdx.x * gpb >= cnt) return;
@@ -261,7 +275,8 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
       }
     }();
     F y;
-    if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * nchunks + j) * lam : F::zero();
+    if constexpr (ER && BATCH) y = live && row >= 0 ? load_elem(it.sh + (size_t)row * nchunks + it.chunk) * lam : F::zero();
+    else if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * nchunks + j) * lam : F::zero();
     else if constexpr (BATCH) y = live ? load_elem(it.sh + (size_t)p * nchunks + it.chunk) : F::zero();
     else y = live ? load_elem(shares + (size_t)p * nchunks + j) : F::zero();
     GaoResult<F, GaoDevGroup, REPAIR> r = gao_chunk<F, GaoDevGroup, REPAIR>(g, c, n, kd, live, y, xp, xinv, sp);
@@ -270,7 +285,10 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
     if constexpr (REPAIR && ER) {
       gao_repair_word_parties<F, GaoDevGroup>(
           g, r, [&](int) { return row; }, [&](int lane) { return load_elem(ilam + lane); },
-          [&](int, int at, const F& v) { store_elem(shares + (size_t)at * nchunks + j, v); });
+          [&](int, int at, const F& v) {
+            if constexpr (BATCH) store_elem(it.sh + (size_t)at * nchunks + it.chunk, v);
+            else store_elem(shares + (size_t)at * nchunks + j, v);
+          });
     } else if constexpr (BATCH) {
       gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(it.sh + (size_t)lane * nchunks + it.chunk, v); });
     } else if constexpr (REPAIR) {
@@ -338,6 +356,13 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_repair_parties_kernel(const G
                                                                         uint8_t* __restrict__ status,
                                                                         uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage2_body<P, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, tab, ilam);
+}
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_repair_batch_parties_kernel(
+    const GaoConsts<Fp<P>> c, const GaoAbsent<Fp<P>>* __restrict__ tab, const Fp<P>* __restrict__ ilam, int n, int l,
+    Fp<P>* shares, size_t item_stride, size_t nchunks, int k, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos,
+    GaoWork wk) {
+  gao_stage2_body<P, true, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, tab, ilam, item_stride);
 }
 // the table of a call, from the launch's arguments to working memory: one word per lane
 template <class F>
@@ -448,6 +473,48 @@ int gao_repair_batch_run(IEngine* e, void* wkp, int l, void* shares, size_t item
   const size_t gpb = GAO_THREADS / n, total = (size_t)nitems * nchunks;
   const dim3 grid2((unsigned)std::min<size_t>((total + gpb - 1) / gpb, GAO_STAGE2_GRID));
   gao_repair_batch_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, item_stride, nchunks, dimension, status, errpos, wk);
+  GAO_HIP(hipGetLastError());
+  return ZK_OK;
+}
+// zk_pss_repair_batch_parties: the launches of the batch above with the two tables of the party list put into working memory
+// ahead of them, once per call: one clear, GaoAbsent, GaoInvLambda, one scan with the item on grid.y, one repair launch over
+// the one list.  ids: np ascending party ids below n, dimension < np < n (the caller's checks; np == n is the batch above).
+template <class FrP>
+int gao_repair_batch_parties_run(IEngine* e, void* wkp, int l, void* shares, const uint32_t* ids, int np, size_t item_stride,
+                                 int nitems, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos,
+                                 uint64_t* summary, hipStream_t st) {
+  using Fr = Fp<FrP>;
+  using Tab = GaoAbsent<Fr>;
+  const int n = 4 * l;
+  static_assert(sizeof(Tab) + 80 <= 4096, "the table travels as a kernel argument");
+  const GaoBatchPartiesWork lay = gao_batch_parties_work<Fr>(n, nitems, nchunks);
+  GaoWork wk;
+  wk.count = (uint32_t*)wkp;
+  wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkp + 32);
+  wk.list = (uint32_t*)((char*)wkp + lay.list);
+  Tab* tab = (Tab*)((char*)wkp + lay.tab);
+  GaoInvLambda<Fr>* inv = (GaoInvLambda<Fr>*)((char*)wkp + lay.inv);
+  GAO_HIP(hipMemsetAsync(wkp, 0, lay.tab, st));
+  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)nitems * (3 + n) * 8, st));
+  const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
+  const Tab a = gao_make_absent<FrP>(c, l, ids, np, dimension);
+  const dim3 blk(GAO_THREADS);
+  gao_absent_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(a, tab);
+  gao_inv_lambda_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(gao_make_inv_lambda<FrP>(a), inv);
+  const size_t per_wg = GAO_THREADS / gao_split(l);
+  const dim3 grid1((unsigned)((nchunks + per_wg - 1) / per_wg), (unsigned)nitems);
+  Fr* sh = (Fr*)shares;
+  const int k = dimension, rho = a.rho;
+  switch (l) {
+    case 1: gao_scan_batch_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
+    case 2: gao_scan_batch_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
+    case 4: gao_scan_batch_parties_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
+    case 8: gao_scan_batch_parties_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
+    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
+  }
+  const size_t gpb = GAO_THREADS / n, total = (size_t)nitems * nchunks;
+  const dim3 grid2((unsigned)std::min<size_t>((total + gpb - 1) / gpb, GAO_STAGE2_GRID));
+  gao_repair_batch_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, inv->v, n, l, sh, item_stride, nchunks, k, status, errpos, wk);
   GAO_HIP(hipGetLastError());
   return ZK_OK;
 }

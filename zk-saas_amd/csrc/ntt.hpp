@@ -357,6 +357,33 @@ __global__ void vec_add2d_kernel(F* __restrict__ x, size_t xpitch, const F* __re
   store_elem(x + r * xpitch + c, load_elem(x + r * xpitch + c) + load_elem(y + r * ypitch + c));
 }
 
+// The in-mask rows of a party list, for up to three king words in one launch (the checked rounds with a list,
+// engine_gao.inc.hpp): item blockIdx.y is a compact word [nparties][width] at x + item * item_stride, and row r of it becomes
+// x[r] * k + mask[item][party of row r], the mask a full matrix [n][width].  listed: bit p -- party p is listed; the party of
+// row r is the r-th set bit.  A null mask skips the item; scale == 0 leaves the factor k out (the forward round).
+template <class F>
+struct ListMasks {
+  const F* mask[3];
+};
+template <class F>
+__global__ void vec_add_list_rows_kernel(F* __restrict__ x, size_t item_stride, ListMasks<F> lm, uint32_t listed, int scale, F k,
+                                         size_t width, size_t rows) {
+  __builtin_amdgcn_s_setprio(3);
+  const F* __restrict__ mask = lm.mask[blockIdx.y];
+  if (!mask) return;
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= width * rows) return;
+  const uint32_t r = (uint32_t)(i / width);
+  const size_t c = i % width;
+  uint32_t m = listed;                               // the r-th set bit: r < popcount(listed) <= 32
+  for (uint32_t t = 0; t < r; t++) m &= m - 1;
+  const uint32_t party = (uint32_t)__builtin_ctz(m);
+  F* at = x + blockIdx.y * item_stride + (size_t)r * width + c;
+  F v = load_elem(at);
+  if (scale) v = v * k;
+  store_elem(at, v + load_elem(mask + (size_t)party * width + c));
+}
+
 template <class F>
 __global__ void vec_scale_kernel(F* __restrict__ x, F k, size_t len) {
   __builtin_amdgcn_s_setprio(3);

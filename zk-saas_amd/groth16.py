@@ -531,10 +531,15 @@ def verify_all_bytes(pp, pvk, proof_bytes, input_bytes, seed=None, stream=None, 
     return (bool(ok.value), pp.fq.decode(gt.reshape(12, nl))) if want_gt else bool(ok.value)
 
 
-def prove(pp, crs, wit, r, s, masks=None, seed=0, stream=None, check=False):
+def prove(pp, crs, wit, r, s, masks=None, seed=0, stream=None, check=False, parties=None):
     """dsha256 (sha256.rs:32-129) for all parties. Returns (pi_a [n][3nl], pi_b [n][6nl], pi_c [n][3nl]) Jacobian.
     check=True: zk_groth16_prove_checked -- the seven king words of circom_h are repaired before the kings read them (the
-    five d_msm rounds are not checked); returns (proof, report), the report as api.h_report's."""
+    five d_msm rounds are not checked); returns (proof, report), the report as api.h_report's.
+    parties (with check=True only; ascending ids, all n or n - 1 of them): zk_groth16_prove_checked_parties -- the proof
+    from the listed parties alone: the h chain of api.circom_h(parties=...) and the list's coefficients in the five MSM
+    rounds; the absent party's rows of every input and in-mask have no influence on the proof."""
+    if parties is not None and not check:
+        raise ValueError("a party list needs check=True (the unchecked prover takes all n parties)")
     nl = pp.fq.nl
     pa = np.zeros((pp.n, 3 * nl), dtype=np.uint64)
     pb = np.zeros((pp.n, 6 * nl), dtype=np.uint64)
@@ -543,6 +548,17 @@ def prove(pp, crs, wit, r, s, masks=None, seed=0, stream=None, check=False):
     assert crs.len_a == wit.len_a and crs.len_w == wit.len_w
     if isinstance(masks, ProofMasks):
         masks = masks.ct
+    if check and parties is not None:
+        rep = api.h_report(pp, wit.log_m)
+        rep.parties = list(parties)
+        arr = (C.c_uint32 * len(rep.parties))(*rep.parties)
+        pp._check(pp.lib.zk_groth16_prove_checked_parties(pp.h, arr, len(rep.parties), C.byref(crs.ct), wit.qap[0].ptr,
+                                                          wit.qap[1].ptr, wit.qap[2].ptr, wit.a_share.ptr, wit.ax_share.ptr,
+                                                          rr.ctypes.data, ss.ctypes.data, wit.log_m,
+                                                          None if masks is None else C.byref(masks), seed, pa.ctypes.data,
+                                                          pb.ctypes.data, pc.ctypes.data, rep.status.ptr, rep.errpos.ptr,
+                                                          rep.summary_d.ptr, stream))
+        return (pa, pb, pc), rep
     if check:
         rep = api.h_report(pp, wit.log_m)
         pp._check(pp.lib.zk_groth16_prove_checked(pp.h, C.byref(crs.ct), wit.qap[0].ptr, wit.qap[1].ptr, wit.qap[2].ptr,
