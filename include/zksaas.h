@@ -455,6 +455,20 @@ int zk_pss_repair_parties(zk_ctx* ctx, void* shares_d /* [nparties][nchunks], in
                           size_t nchunks, int dimension, uint8_t* status_d /* [nchunks] */,
                           uint32_t* errpos_d /* [nchunks], or NULL */, uint64_t* summary_d /* [3 + n], or NULL */,
                           void* stream);
+/* zk_pss_repair_range: parity access to the RANGE form of zk_pss_repair_parties, which the checked rounds on the net run
+ * where every rank is king of a range of chunks (zk_dist_*_checked with the option king_alltoall; like zk_fq_selftest, for
+ * tests).  The word of len chunks is not contiguous: shares_d is a block [nparties][stride] of which columns 0 .. cnt - 1
+ * are valid, and column c is chunk (base + c + len - shift) mod len of the word -- the layout in which the king of a range
+ * receives it (dist-primitives/src/dfft/mod.rs:264-304 reads the whole word; here a rank holds its range).  Shares are read
+ * and rewritten at row * stride + c for c < cnt only: columns cnt .. stride - 1 are neither read nor written.  status_d and
+ * errpos_d are [len] and written at the mapped chunks only; summary_d counts the cnt chunks (cnt == 0: all zeros).
+ * With stride == cnt == len, base == 0 and shift == 0 every output and every byte written is zk_pss_repair_parties'.
+ * Errors: those of zk_pss_repair_parties; cnt > stride, cnt > len, base >= len or shift > len is ZK_ERR_BAD_INPUT. */
+int zk_pss_repair_range(zk_ctx* ctx, void* shares_d /* [nparties][stride], in place */,
+                        const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */, int nparties, size_t stride,
+                        uint32_t cnt, uint32_t len, uint32_t base, uint32_t shift, int dimension,
+                        uint8_t* status_d /* [len] */, uint32_t* errpos_d /* [len], or NULL */,
+                        uint64_t* summary_d /* [3 + n], or NULL */, void* stream);
 /* Checked king rounds with a party list: the calls above for the case that only the listed parties' shares reached the king
  * (dist-primitives/src/dfft/mod.rs:264-304 with the list of unpack_missing_shares, pss.rs:141-221) -- a dropout, or a party
  * left out because an earlier report named it.  Each runs zk_pss_repair_parties at dimension 2l on the word the king
@@ -823,6 +837,42 @@ int zk_dist_groth16_prove(zk_ctx* ctx, zk_net* net, const zk_crs_share* crs, con
                           const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
                           int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
                           void* stream);
+
+/* ---- checked king rounds on the net: the per-rank calls above with the word the king RECEIVES from the other ranks checked
+ * before the king reads it -- the place where a lying party is another process (client_send_or_king_receive in
+ * dist-primitives/src/dfft/mod.rs:264-304 and dist-primitives/src/utils/deg_red.rs:99-115).  Each takes the unchecked
+ * call's arguments, then status_d [len], errpos_d [len] (or NULL) and summary_d [3 + n] (or NULL), all DEVICE pointers, the
+ * same (NULL or not) on every rank.  The list is the parties of the ranks zk_net_enter admitted; it is refused as
+ * zk_*_checked_parties refuse a list (all n parties or n - 1 of them, else ZK_ERR_PROTOCOL), before anything is written and
+ * on every rank alike.
+ *   WHERE THE REPORT LANDS  every present rank zeroes status_d / errpos_d on entry and then writes exactly the chunks it
+ *   was king of: rank 0 all of them under the star king, each rank its range under the all-to-all king (option
+ *   king_alltoall) -- the OR over the ranks is the single-device report.  summary_d is complete and IDENTICAL on every
+ *   present rank and equals the summary of zk_*_checked[_parties] on the same word; it crosses the net on the round's own
+ *   channel after the king.  A failed chunk is no error return: its shares go to the king as received.
+ * With the LOCAL transport the results are zk_d_fft_checked's / zk_d_ifft_checked's / zk_deg_red_checked's.  With a
+ * general party_to_rank map the all-to-all king does not apply and the checked calls use the star, as the unchecked do. */
+/* d_fft(pd_shares, rearrange, &FftMask, pp, &net, sid), dfft/mod.rs:99-134, king :264-304: the word fft1(x) + in_mask at
+ * dimension 2l, up to (nparties - 2l) / 2 wrong shares per chunk corrected */
+int zk_dist_d_fft_checked(zk_ctx* ctx, zk_net* net, int sid, void* shares_d, const void* in_mask_d, const void* out_mask_d,
+                          int rearrange, int log2_m, uint64_t seed, uint8_t* status_d, uint32_t* errpos_d,
+                          uint64_t* summary_d, void* stream);
+/* d_ifft(pd_shares, rearrange, &FftMask, dom, g, pp, &net, sid), dfft/mod.rs:137-175, king :264-304 */
+int zk_dist_d_ifft_checked(zk_ctx* ctx, zk_net* net, int sid, void* shares_d, const void* in_mask_d, const void* out_mask_d,
+                           int rearrange, int log2_m, const void* g, uint64_t seed, uint8_t* status_d, uint32_t* errpos_d,
+                           uint64_t* summary_d, void* stream);
+/* deg_red(px, pp, &DegRedMask, &net, sid), utils/deg_red.rs:80-126, king :99-115: dimension 4l - 1, DETECTION ONLY (a status is
+ * 0 or 2, nothing is rewritten).  With a rank absent the n - 1 words leave no redundancy: NOT CHECKED -- status and errpos
+ * bytes 0 and an all-zero summary, as item 6 of zk_circom_h_checked_parties. */
+int zk_dist_deg_red_checked(zk_ctx* ctx, zk_net* net, int sid, void* x_d, const void* in_mask_d, const void* out_mask_d,
+                            size_t len, uint64_t seed, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d,
+                            void* stream);
+/* circom_h(qap_share, pp, masks.., &net), groth16/src/ext_wit.rs:104-181: zk_dist_circom_h with its six transform rounds
+ * (:127-170) and the deg_red round (:173-179) checked.  status_d / errpos_d [7][m/l], summary_d [7][3 + n], the items in the
+ * order of zk_circom_h_checked; the three channels of a phase stay in flight together. */
+int zk_dist_circom_h_checked(zk_ctx* ctx, zk_net* net, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d,
+                             int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* h_d, uint8_t* status_d,
+                             uint32_t* errpos_d, uint64_t* summary_d, void* stream);
 
 /* The sharded prover in two halves (the reference's parties are concurrent tasks, mpc-net/src/multi.rs:317-327, and
  * prove.rs:209-227 joins the W and U d_msm): zk_dist_groth16_prove_async admits the proof, starts this rank's four witness

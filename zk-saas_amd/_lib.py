@@ -39,6 +39,8 @@ SYMBOLS = [
     "zk_pss_repair_batch", "zk_circom_h_checked", "zk_groth16_prove_checked",
     "zk_msm_sum",
     "zk_pss_repair_batch_parties", "zk_circom_h_checked_parties", "zk_groth16_prove_checked_parties",
+    "zk_pss_repair_range", "zk_dist_d_fft_checked", "zk_dist_d_ifft_checked", "zk_dist_deg_red_checked",
+    "zk_dist_circom_h_checked",
 ]
 
 _lib = None
@@ -248,6 +250,12 @@ def load():
     lib.zk_circom_h_checked_parties.argtypes = [vp, ids, i32, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp]
     lib.zk_groth16_prove_checked_parties.argtypes = [vp, ids, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp,
                                                      vp, vp]
+    u32 = C.c_uint32
+    lib.zk_pss_repair_range.argtypes = [vp, vp, ids, i32, sz, u32, u32, u32, u32, i32, vp, vp, vp, vp]
+    lib.zk_dist_d_fft_checked.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, u64, vp, vp, vp, vp]
+    lib.zk_dist_d_ifft_checked.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, u64, vp, vp, vp, vp]
+    lib.zk_dist_deg_red_checked.argtypes = [vp, vp, i32, vp, vp, vp, sz, u64, vp, vp, vp, vp]
+    lib.zk_dist_circom_h_checked.argtypes = [vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp]
     lib.zk_points_subgroup_check.argtypes = [vp, i32, vp, sz, vp, vp]
     lib.zk_points_decompress_checked.argtypes = [vp, i32, vp, sz, vp, vp, vp]
     lib.zk_groth16_verify_bytes.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp]

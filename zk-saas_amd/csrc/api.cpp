@@ -699,6 +699,35 @@ int zk_dist_circom_h(zk_ctx* ctx, zk_net* net, const void* qap_a_d, const void* 
   NET_OR_FAIL();
   return e->dist_finish(&net->net, e->dist_circom_h(&net->net, qap_a_d, qap_b_d, qap_c_d, log2_m, masks, seed, h_d, S(stream)));
 }
+int zk_dist_d_fft_checked(zk_ctx* ctx, zk_net* net, int sid, void* shares_d, const void* in_mask_d, const void* out_mask_d,
+                          int rearrange, int log2_m, uint64_t seed, uint8_t* status_d, uint32_t* errpos_d,
+                          uint64_t* summary_d, void* stream) {
+  NET_OR_FAIL();
+  return e->dist_finish(&net->net, e->dist_d_fft_checked(&net->net, sid, shares_d, in_mask_d, out_mask_d, rearrange, log2_m, 0,
+                                                         nullptr, seed, status_d, errpos_d, summary_d, S(stream)));
+}
+int zk_dist_d_ifft_checked(zk_ctx* ctx, zk_net* net, int sid, void* shares_d, const void* in_mask_d, const void* out_mask_d,
+                           int rearrange, int log2_m, const void* g, uint64_t seed, uint8_t* status_d, uint32_t* errpos_d,
+                           uint64_t* summary_d, void* stream) {
+  NET_OR_FAIL();
+  return e->dist_finish(&net->net, e->dist_d_fft_checked(&net->net, sid, shares_d, in_mask_d, out_mask_d, rearrange, log2_m, 1,
+                                                         g, seed, status_d, errpos_d, summary_d, S(stream)));
+}
+int zk_dist_deg_red_checked(zk_ctx* ctx, zk_net* net, int sid, void* x_d, const void* in_mask_d, const void* out_mask_d,
+                            size_t len, uint64_t seed, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d,
+                            void* stream) {
+  NET_OR_FAIL();
+  return e->dist_finish(&net->net, e->dist_deg_red_checked(&net->net, sid, x_d, in_mask_d, out_mask_d, len, seed, status_d,
+                                                           errpos_d, summary_d, S(stream)));
+}
+int zk_dist_circom_h_checked(zk_ctx* ctx, zk_net* net, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d,
+                             int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* h_d, uint8_t* status_d,
+                             uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  const int sid = 0;
+  NET_OR_FAIL();
+  return e->dist_finish(&net->net, e->dist_circom_h_checked(&net->net, qap_a_d, qap_b_d, qap_c_d, log2_m, masks, seed, h_d,
+                                                            status_d, errpos_d, summary_d, S(stream)));
+}
 int zk_dist_groth16_prove(zk_ctx* ctx, zk_net* net, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
                           const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
                           int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
@@ -880,6 +909,13 @@ int zk_pss_repair_parties(zk_ctx* ctx, void* shares_d, const uint32_t* parties, 
                           uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
   CTX_OR_FAIL();
   return e->pss_repair_parties(shares_d, parties, nparties, nchunks, dimension, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_pss_repair_range(zk_ctx* ctx, void* shares_d, const uint32_t* parties, int nparties, size_t stride, uint32_t cnt,
+                        uint32_t len, uint32_t base, uint32_t shift, int dimension, uint8_t* status_d, uint32_t* errpos_d,
+                        uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_repair_range(shares_d, parties, nparties, stride, cnt, len, base, shift, dimension, status_d, errpos_d,
+                             summary_d, S(stream));
 }
 int zk_fft2_king_checked_parties(zk_ctx* ctx, void* in_d, const uint32_t* parties, int nparties, int log2_m, int inverse,
                                  const void* g, int scale_size_inv, int rearrange, uint64_t seed, void* out_d,

@@ -414,6 +414,21 @@ class IEngine {
   // zk_pss_repair_parties: the verdicts of pss_unpack_robust_parties, written back into the shares [nparties][nchunks]
   virtual int pss_repair_parties(void* shares, const uint32_t* parties, int nparties, size_t nchunks, int dimension,
                                  uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  // the range form of pss_repair_parties: cnt valid columns of a block [nparties][stride], column c being chunk
+  // (base + c + len - shift) mod len of a word of len chunks (king_range.hpp; status and errpos are [len])
+  virtual int pss_repair_range(void* shares, const uint32_t* parties, int nparties, size_t stride, uint32_t cnt, uint32_t len,
+                               uint32_t base, uint32_t shift, int dimension, uint8_t* status, uint32_t* errpos,
+                               uint64_t* summary, hipStream_t st) = 0;
+  // the checked king rounds on the net (engine_dist.inc.hpp): the unchecked call's arguments, then the report -- status and
+  // errpos [len] hold the chunks this rank was king of, summary [3 + n] is complete on every rank
+  virtual int dist_d_fft_checked(Net* net, int sid, void* shares, const void* in_mask, const void* out_mask, int rearrange,
+                                 int log_m, int inverse, const void* g, uint64_t seed, uint8_t* status, uint32_t* errpos,
+                                 uint64_t* summary, hipStream_t st) = 0;
+  virtual int dist_deg_red_checked(Net* net, int sid, void* x, const void* in_mask, const void* out_mask, size_t len,
+                                   uint64_t seed, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  virtual int dist_circom_h_checked(Net* net, const void* qa, const void* qb, const void* qc, int log_m,
+                                    const zk_groth16_masks* masks, uint64_t seed, void* h, uint8_t* status, uint32_t* errpos,
+                                    uint64_t* summary, hipStream_t st) = 0;
   // the king rounds with the word of a party list repaired first (engine_gao.inc.hpp)
   virtual int fft2_king_checked_parties(void* in, const uint32_t* parties, int np, int log_m, int inverse, const void* g,
                                         int scale_size_inv, int rearrange, uint64_t seed, void* out, const void* out_mask,

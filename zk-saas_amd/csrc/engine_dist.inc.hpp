@@ -130,14 +130,11 @@
         if (r == net->rank) pl->me = pl->map.npresent;
         pl->map.idx_of_rank[r] = pl->map.npresent++;
       }
-    const size_t np_r = (size_t)pl->map.npresent;
-    if (pl->me < 0 || np_r < 2 || len / gran < np_r || len % gran) return false;
-    const size_t seg = ((len / gran + np_r - 1) / np_r) * gran;
-    if (seg > 0xffffffffull) return false;
-    pl->seg = (uint32_t)seg;
-    const size_t rs0 = (size_t)pl->me * seg;
-    pl->rs = (uint32_t)(rs0 < len ? rs0 : len);
-    pl->cnt = (uint32_t)(rs0 >= len ? 0 : (len - rs0 < seg ? len - rs0 : seg));
+    KingSpan sp;
+    if (pl->me < 0 || !king_span(len, gran, (size_t)pl->map.npresent, (size_t)pl->me, &sp)) return false;      // king_range.hpp
+    pl->seg = sp.seg;
+    pl->rs = sp.rs;
+    pl->cnt = sp.cnt;
     return true;
   }
   static constexpr int A2A_NOT_APPLICABLE = -1000;
@@ -174,8 +171,107 @@
     return unpack(back, pl, s);
   }
 
+  // ---------------------------------------------------------------- checked king rounds on the net (zk_dist_*_checked)
+  // The word a king RECEIVES from the other ranks is repaired before the unchanged king reads it (dfft/mod.rs:264-304 and
+  // utils/deg_red.rs:99-115, behind client_send_or_king_receive).  Star: rank 0 runs pss_repair_parties on the gathered
+  // [np][len] with the list the round admitted.  All-to-all: every present rank runs the range form (pss_repair_range) on its
+  // [np][seg] block.  status / errpos: zeroed on entry by every rank, then written at the chunks this rank is king of.
+  // summary: the repair writes this rank's counts into row 0 of dist_sum_; after the king they cross on the round's own
+  // channel -- one row per party scattered from rank 0, or the ranks' rows exchanged and added -- so that every present rank
+  // holds the summary of the whole word.  With the LOCAL transport the repair writes the caller's buffers directly.
+  struct DistCheck {
+    uint8_t* status = nullptr;        // [len]
+    uint32_t* errpos = nullptr;       // [len] or null
+    uint64_t* summary = nullptr;      // [3 + n] or null
+    int dimension = 0;                // 2l, or 4l - 1: detection only
+    bool skip = false;                // NOT CHECKED (deg_red with a rank absent): zero bytes and an all-zero summary
+  };
+  DevBuf dist_sum_[NET_NSID];         // rows of 3 + n counts: 0 this rank's, 1 .. 32 the rows sent, 33 .. 64 the rows received
+  uint64_t* dist_sum_row(int sid, int row) { return (uint64_t*)dist_sum_[sid].p + (size_t)row * (3 + n); }
+  int dist_sum_ensure(int sid) {
+    static_assert(GAO_MAX_N <= 32 && NET_MAXR <= 32, "rows of dist_sum_");
+    ZK_HIP(dist_sum_[sid].ensure((size_t)65 * (3 + n) * sizeof(uint64_t)));
+    return ZK_OK;
+  }
+  int dist_check_star(Net* net, int sid, Fr* in, const uint32_t* ps, int np, size_t len, const DistCheck& chk, hipStream_t ks) {
+    if (chk.skip) return ZK_OK;
+    uint64_t* sum = chk.summary;
+    if (sum && net->transport != ZK_NET_LOCAL) {
+      int rc = dist_sum_ensure(sid);
+      if (rc) return rc;
+      sum = dist_sum_row(sid, 0);
+    }
+    return pss_repair_parties(in, ps, np, len, chk.dimension, chk.status, chk.errpos, sum, ks);
+  }
+  int dist_check_range(int sid, Fr* in, const uint32_t* ps, int np, const A2aPlan& pl, size_t len, uint32_t shift,
+                       const DistCheck& chk, hipStream_t ks) {
+    if (chk.skip) return ZK_OK;
+    uint64_t* sum = nullptr;
+    if (chk.summary) {
+      int rc = dist_sum_ensure(sid);
+      if (rc) return rc;
+      sum = dist_sum_row(sid, 0);
+    }
+    return pss_repair_range(in, ps, np, pl.seg, pl.cnt, (uint32_t)len, pl.cnt ? pl.rs : 0u, shift, chk.dimension, chk.status,
+                            chk.errpos, sum, ks);
+  }
+  // after the king, on the round's channel: the whole word's summary on every present rank
+  int dist_summary(Net* net, int sid, uint32_t mask, bool a2a, const DistCheck& chk, hipStream_t s) {
+    if (!chk.summary) return ZK_OK;
+    const int S = 3 + n;
+    const size_t bytes = (size_t)S * sizeof(uint64_t);
+    if (chk.skip) {
+      ZK_HIP(hipMemsetAsync(chk.summary, 0, bytes, s));
+      return ZK_OK;
+    }
+    if (net->transport == ZK_NET_LOCAL) return ZK_OK;
+    int rc = dist_sum_ensure(sid);
+    if (rc) return rc;
+    using W = unsigned long long;
+    if (!a2a) {
+      // one copy per party, so that the block of a rank is k rows under either party map (net.hpp scatter)
+      if (net->rank == 0) {
+        rows_sum_kernel<W><<<dim3(1), dim3(64), 0, s>>>((const W*)dist_sum_row(sid, 0), 1, S, (W*)dist_sum_row(sid, 1), n);
+        ZK_HIP(hipGetLastError());
+      }
+      rc = net_err(net, net->scatter(sid, mask, net->rank == 0 ? dist_sum_row(sid, 1) : nullptr,
+                                     (size_t)net->parties_per_rank() * bytes, dist_sum_row(sid, 33)));
+      if (rc) return rc;
+      ZK_HIP(hipMemcpyAsync(chk.summary, dist_sum_row(sid, 33), bytes, hipMemcpyDeviceToDevice, s));
+      return ZK_OK;
+    }
+    rows_sum_kernel<W><<<dim3(1), dim3(64), 0, s>>>((const W*)dist_sum_row(sid, 0), 1, S, (W*)dist_sum_row(sid, 1), net->world);
+    ZK_HIP(hipGetLastError());
+    rc = net_err(net, net->alltoall(sid, mask, dist_sum_row(sid, 1), bytes, dist_sum_row(sid, 33)));
+    if (rc) return rc;
+    rows_sum_kernel<W><<<dim3(1), dim3(64), 0, s>>>((const W*)dist_sum_row(sid, 33), __builtin_popcount(mask), S,
+                                                    (W*)chk.summary, 1);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+  }
+  // the list a round admitted, refused as the checked kings with a list refuse it (checked_list: all n parties or n - 1 of
+  // them) -- before anything is written, and alike on every rank, since every rank holds the same mask
+  int dist_checked_list(Net* net, uint32_t mask, int* np) {
+    const std::vector<uint32_t> ps = parties_of(net, mask);
+    uint32_t ids[GAO_MAX_N];
+    *np = (int)ps.size();
+    return checked_list(ps.data(), *np, 2 * l, ids);
+  }
+  // NOT CHECKED: at dimension 4l - 1 a list of n - 1 parties has no redundancy left (deg_red with a rank absent)
+  bool dist_not_checked(int dimension, int np) const { return dimension == 4 * l - 1 && np < n; }
+  // item `item` of an h report as the check of one round ([7][m/l] / [7][3 + n], engine_groth16.inc.hpp HReport)
+  DistCheck dist_check_item(Net* net, uint32_t mask, const HReport& rep, int item, size_t Lc, int dimension) {
+    DistCheck ck;
+    ck.status = rep.status + (size_t)item * Lc;
+    ck.errpos = rep.errpos ? rep.errpos + (size_t)item * Lc : nullptr;
+    ck.summary = rep.summary ? rep.summary + (size_t)item * (3 + n) : nullptr;
+    ck.dimension = dimension;
+    ck.skip = dist_not_checked(dimension, __builtin_popcount(mask) * net->parties_per_rank());
+    return ck;
+  }
+
   int dist_d_fft_on(Net* net, int sid, uint32_t mask, Fr* shares, const Fr* in_mask, const Fr* out_mask, int rearrange,
-                    int log_m, int inverse, const void* g, uint64_t seed, bool do_fft1) {
+                    int log_m, int inverse, const void* g, uint64_t seed, bool do_fft1, const DistCheck* chk = nullptr) {
     const int k = net->parties_per_rank();
     const size_t Lc = ((size_t)1 << log_m) / l;
     hipStream_t s = net_stream(net, sid, nullptr);
@@ -219,6 +315,7 @@
               const Fr* U = nullptr;
               int r2 = umat_for(ps, np, &U);
               if (r2) return r2;
+              if (chk && (r2 = dist_check_range(sid, (Fr*)in, ps, np, pl, Lc, 1u, *chk, ks))) return r2;
               KingRange rg{pl.rs, pl.seg, pl.cnt};
               return king_dispatch(in, nullptr, np, log_m, inverse, U, g, scale, rearrange, seed, out, nullptr, false, ks, &rg);
             },
@@ -230,14 +327,17 @@
               return (int)ZK_OK;
             });
     }
+    const bool a2a_ran = rc != A2A_NOT_APPLICABLE;
     if (rc == A2A_NOT_APPLICABLE)
     rc = king_round(net, sid, mask, shares, Lc, [&](const Fr* in, const uint32_t* ps, int np, Fr* out, const Fr* om, hipStream_t ks) {
       const Fr* U = nullptr;
       int r2 = umat_for(ps, np, &U);
       if (r2) return r2;
+      if (chk && (r2 = dist_check_star(net, sid, (Fr*)in, ps, np, Lc, *chk, ks))) return r2;
       return king_dispatch(in, nullptr, np, log_m, inverse, U, g, scale, rearrange, seed, out, om, false, ks);
     }, out_mask, king_in);
     else if (!rc && out_mask) rc = vec_add(shares, out_mask, (size_t)k * Lc, s);       // after the all-to-all king
+    if (!rc && chk) rc = dist_summary(net, sid, mask, a2a_ran, *chk, s);
     return rc;
   }
   int dist_d_fft(Net* net, int sid, void* shares, const void* in_mask, const void* out_mask, int rearrange, int log_m,
@@ -256,7 +356,7 @@
   }
 
   int dist_deg_red_on(Net* net, int sid, uint32_t mask, Fr* x, const Fr* in_mask, const Fr* out_mask, size_t len,
-                      uint64_t seed) {
+                      uint64_t seed, const DistCheck* chk = nullptr) {
     const int k = net->parties_per_rank();
     hipStream_t s = net_stream(net, sid, nullptr);
     int rc;
@@ -269,6 +369,8 @@
       rc = king_round_a2a(
           net, sid, mask, x, len, 1, 0u,
           [&](const Fr* in, const uint32_t* ps, int np, Fr* out, const A2aPlan& pl, hipStream_t ks) {
+            int r2;
+            if (chk && (r2 = dist_check_range(sid, (Fr*)in, ps, np, pl, len, 0u, *chk, ks))) return r2;
             return deg_red_np(in, nullptr, ps, np, pl.cnt, seed, out, nullptr, ks, pl.seg, pl.rs);
           },
           [&](const Fr* back, const A2aPlan& pl, hipStream_t ks) {
@@ -278,12 +380,18 @@
             ZK_HIP(hipGetLastError());
             return (int)ZK_OK;
           });
-    if (rc == A2A_NOT_APPLICABLE)
-      return king_round(net, sid, mask, x, len, [&](const Fr* in, const uint32_t* ps, int np, Fr* out, const Fr* om, hipStream_t ks) {
+    if (rc == A2A_NOT_APPLICABLE) {
+      rc = king_round(net, sid, mask, x, len, [&](const Fr* in, const uint32_t* ps, int np, Fr* out, const Fr* om, hipStream_t ks) {
+        int r2;
+        if (chk && (r2 = dist_check_star(net, sid, (Fr*)in, ps, np, len, *chk, ks))) return r2;
         return deg_red_np(in, nullptr, ps, np, len, seed, out, om, ks);
       }, out_mask, nullptr, true);
+      if (!rc && chk) rc = dist_summary(net, sid, mask, false, *chk, s);
+      return rc;
+    }
     if (rc) return rc;
-    if (out_mask) return vec_add(x, out_mask, (size_t)k * len, s);        // after the all-to-all king
+    if (out_mask && (rc = vec_add(x, out_mask, (size_t)k * len, s))) return rc;        // after the all-to-all king
+    if (chk) return dist_summary(net, sid, mask, true, *chk, s);
     return ZK_OK;
   }
   int dist_deg_red(Net* net, int sid, void* x, const void* in_mask, const void* out_mask, size_t len, uint64_t seed,
@@ -296,6 +404,56 @@
     rc = net_err(net, net->begin(sid, st));
     if (rc) return rc;
     rc = dist_deg_red_on(net, sid, mask, (Fr*)x, (const Fr*)in_mask, (const Fr*)out_mask, len, seed);
+    if (rc) return rc;
+    return net_err(net, net->end(sid, st));
+  }
+
+  // zk_dist_d_fft_checked / zk_dist_d_ifft_checked / zk_dist_deg_red_checked: the round above with the king's word checked
+  int dist_d_fft_checked(Net* net, int sid, void* shares, const void* in_mask, const void* out_mask, int rearrange, int log_m,
+                         int inverse, const void* g, uint64_t seed, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                         hipStream_t st) override {
+    if (!shares || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (log_m < ilog2(l) || log_m > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    const size_t Lc = ((size_t)1 << log_m) / l;
+    if (Lc >= ((size_t)1 << 32)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
+    uint32_t mask = 0;
+    int np = 0;
+    int rc = net_err(net, net->enter(sid, &mask));
+    if (rc) return rc;
+    if ((rc = dist_checked_list(net, mask, &np))) return rc;
+    rc = net_err(net, net->begin(sid, st));
+    if (rc) return rc;
+    hipStream_t s = net_stream(net, sid, nullptr);
+    ZK_HIP(hipMemsetAsync(status, 0, Lc, s));
+    if (errpos) ZK_HIP(hipMemsetAsync(errpos, 0, Lc * sizeof(uint32_t), s));
+    DistCheck ck;
+    ck.status = status, ck.errpos = errpos, ck.summary = summary, ck.dimension = 2 * l;
+    rc = dist_d_fft_on(net, sid, mask, (Fr*)shares, (const Fr*)in_mask, (const Fr*)out_mask, rearrange, log_m, inverse, g,
+                       seed, true, &ck);
+    if (rc) return rc;
+    return net_err(net, net->end(sid, st));
+  }
+  // dimension 4l - 1: detection only; with a rank absent the n - 1 words leave no redundancy -- NOT CHECKED, the convention
+  // of circom_h_checked_parties for its item 6
+  int dist_deg_red_checked(Net* net, int sid, void* x, const void* in_mask, const void* out_mask, size_t len, uint64_t seed,
+                           uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    if (!len) return ZK_OK;
+    if (!x || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (len >= ((size_t)1 << 32)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
+    uint32_t mask = 0;
+    int np = 0;
+    int rc = net_err(net, net->enter(sid, &mask));
+    if (rc) return rc;
+    if ((rc = dist_checked_list(net, mask, &np))) return rc;
+    rc = net_err(net, net->begin(sid, st));
+    if (rc) return rc;
+    hipStream_t s = net_stream(net, sid, nullptr);
+    ZK_HIP(hipMemsetAsync(status, 0, len, s));
+    if (errpos) ZK_HIP(hipMemsetAsync(errpos, 0, len * sizeof(uint32_t), s));
+    DistCheck ck;
+    ck.status = status, ck.errpos = errpos, ck.summary = summary, ck.dimension = 4 * l - 1;
+    ck.skip = dist_not_checked(ck.dimension, np);
+    rc = dist_deg_red_on(net, sid, mask, (Fr*)x, (const Fr*)in_mask, (const Fr*)out_mask, len, seed, &ck);
     if (rc) return rc;
     return net_err(net, net->end(sid, st));
   }
@@ -412,7 +570,8 @@
   // circom_h (ext_wit.rs:104-181): the three d_ifft, then the three d_fft, each triple in flight together on channels
   // 0..2 (ext_wit.rs:158-170 joins them); then a*b - c and deg_red on channel 0.  masks: LOCAL rows.
   int dist_circom_h_on(Net* net, const uint32_t* cmask, const void* qa, const void* qb, const void* qc, int log_m,
-                       const zk_groth16_masks* mk, uint64_t seed, void* h, hipStream_t st, DevBuf* wb = nullptr) {
+                       const zk_groth16_masks* mk, uint64_t seed, void* h, hipStream_t st, DevBuf* wb = nullptr,
+                       const HReport* rep = nullptr) {
     const int k = net->parties_per_rank();
     const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)k * Lc;
     if (!wb) wb = &dist_w0_;
@@ -440,9 +599,11 @@
       for (int j = 0; j < 3; j++) {
         const int mi = phase * 3 + j;
         if ((mk && mk->fft_in[mi] != nullptr) != has_in) return fail(ZK_ERR_BAD_INPUT, "mixed in-masks in circom_h");
+        DistCheck ck;      // item mi of the report: a word of dimension 2l
+        if (rep) ck = dist_check_item(net, cmask[j], *rep, mi, Lc, 2 * l);
         rc = dist_d_fft_on(net, j, cmask[j], W + j * per, mk ? (const Fr*)mk->fft_in[mi] : nullptr,
                            mk ? (const Fr*)mk->fft_out[mi] : nullptr, phase == 0 ? 1 : 0, log_m, inverse,
-                           phase == 0 ? (const void*)&w2m : nullptr, seed + mi, false);
+                           phase == 0 ? (const void*)&w2m : nullptr, seed + mi, false, rep ? &ck : nullptr);
         if (rc) return rc;
       }
       for (int j = 0; j < 3; j++) {
@@ -454,8 +615,10 @@
     if (rc) return rc;
     rc = net_err(net, net->begin(0, st));
     if (rc) return rc;
+    DistCheck ck6;       // item 6: dimension 4l - 1, detection only; NOT CHECKED with a rank absent
+    if (rep) ck6 = dist_check_item(net, cmask[0], *rep, 6, Lc, 4 * l - 1);
     rc = dist_deg_red_on(net, 0, cmask[0], (Fr*)h, mk ? (const Fr*)mk->degred_in : nullptr,
-                         mk ? (const Fr*)mk->degred_out : nullptr, Lc, seed + 6);
+                         mk ? (const Fr*)mk->degred_out : nullptr, Lc, seed + 6, rep ? &ck6 : nullptr);
     if (rc) return rc;
     return net_err(net, net->end(0, st));
   }
@@ -719,6 +882,32 @@
     if (cmask[1] != cmask[0] || cmask[2] != cmask[0])
       return fail(ZK_ERR_PROTOCOL, "the three channels of circom_h saw different parties", -1);
     return dist_circom_h_on(net, cmask, qa, qb, qc, log_m, mk, seed, h, st);
+  }
+
+  // zk_dist_circom_h_checked: dist_circom_h_on with its six transform rounds and the deg_red round checked; the report has
+  // the layouts and the item order of circom_h_checked (HReport).  The three channels of a phase stay in flight together,
+  // each repairing on its own stream with that stream's working memory.
+  int dist_circom_h_checked(Net* net, const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* mk,
+                            uint64_t seed, void* h, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                            hipStream_t st) override {
+    if (log_m < ilog2(l) || log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    if (!qa || !qb || !qc || !h || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    const size_t Lc = ((size_t)1 << log_m) / l;
+    if (Lc >= ((size_t)1 << 32)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
+    uint32_t cmask[3];
+    for (int j = 0; j < 3; j++) {
+      int rc = net_err(net, net->enter(j, &cmask[j]));
+      if (rc) return rc;
+    }
+    if (cmask[1] != cmask[0] || cmask[2] != cmask[0])
+      return fail(ZK_ERR_PROTOCOL, "the three channels of circom_h saw different parties", -1);
+    int np = 0;
+    int rc = dist_checked_list(net, cmask[0], &np);
+    if (rc) return rc;
+    ZK_HIP(hipMemsetAsync(status, 0, 7 * Lc, st));
+    if (errpos) ZK_HIP(hipMemsetAsync(errpos, 0, 7 * Lc * sizeof(uint32_t), st));
+    const HReport rep{status, errpos, summary};
+    return dist_circom_h_on(net, cmask, qa, qb, qc, log_m, mk, seed, h, st, nullptr, &rep);
   }
 
   // dsha256 per rank (sha256.rs:32-129): all shares and masks are this rank's k parties' rows; pi_*: k Jacobian points.

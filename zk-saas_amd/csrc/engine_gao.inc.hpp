@@ -170,6 +170,18 @@
                                        summary, st);
   }
 
+  // ---------------------------------------------------------------- the range form of zk_pss_repair_parties
+  // The word of an all-to-all king (engine_dist.inc.hpp): rg.cnt valid columns of a block [nparties][rg.stride], column c
+  // being chunk rg.chunk(c) of a word of rg.len chunks (king_range.hpp).  Only those columns are read and rewritten, status
+  // and errpos [rg.len] are written at the mapped chunks only, the summary counts the rg.cnt chunks.
+  int pss_repair_range(void* shares, const uint32_t* parties, int nparties, size_t stride, uint32_t cnt, uint32_t len,
+                       uint32_t base, uint32_t shift, int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                       hipStream_t st) override {
+    const GaoRange rg{stride, cnt, base, shift, len};
+    return gao_repair_range_run<FrP>(this, ws(st)->hwork, l, shares, parties, nparties, rg, dimension, status, errpos, summary,
+                                     st);
+  }
+
   // ---------------------------------------------------------------- checked king rounds with a party list
   // Only the listed parties' words reached the king: repair with the list at dimension 2l, cap = (np - 2l) / 2, then the
   // unchecked king with the same list (umat_for).  The refusals are pss_repair_parties' and the unchecked king's (checked_list).

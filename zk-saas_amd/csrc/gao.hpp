@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "field.hpp"
+#include "king_range.hpp"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #endif
@@ -569,6 +570,13 @@ int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wk, int l, const void* sha
 template <class FrP>
 int gao_repair_parties_run(IEngine* e, DevBuf& wk, int l, void* shares, const uint32_t* parties, int nparties, size_t nchunks,
                            int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
+// the range form of zk_pss_repair_parties: a word whose rg.cnt valid columns lie in a block with padding, rows rg.stride
+// elements apart (king_range.hpp GaoRange); the shares are read and rewritten at row * rg.stride + c for c < rg.cnt only,
+// status and errpos [rg.len] are written at rg.chunk(c) and nowhere else, the summary counts the rg.cnt chunks.  With
+// stride == cnt == len, base == 0 and shift == 0 every output and byte written is gao_repair_parties_run's.
+template <class FrP>
+int gao_repair_range_run(IEngine* e, DevBuf& wk, int l, void* shares, const uint32_t* parties, int nparties, const GaoRange& rg,
+                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
 #endif
 
 }  // namespace zk

@@ -73,15 +73,19 @@ struct GaoWork {
 // and no message: 1 / 5 / 17 products per chunk at l = 1, 2, 4; at l = 8 the two lanes' 17 each and the 15 of the split.
 // SCAN with ER (zk_pss_repair_parties): listed -- bit p: party p is listed; its row is the number of listed parties below it.
 // entry0: the list entry of this item's chunk 0 (gao_batch_entry; zk_pss_repair_batch), 0 for a single word.
-template <class P, int L, bool ER, bool SCAN = false>
+// RANGE (with SCAN): the word lies in a block with padding (king_range.hpp GaoRange) -- nchunks is the count of valid columns,
+// the rows are rg.stride apart, status and errpos are written at rg.chunk(column), the list holds columns.
+template <class P, int L, bool ER, bool SCAN = false, bool RANGE = false>
 __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const Fp<P>* __restrict__ shares, size_t nchunks,
                                                 int k, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
                                                 uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, const GaoWork& wk,
                                                 const GaoAbsentLoad<Fp<P>>* ab, int rho,
                                                 const GaoAbsent<Fp<P>>* __restrict__ tab, uint32_t listed = 0,
-                                                uint32_t entry0 = 0) {
+                                                uint32_t entry0 = 0, [[maybe_unused]] const GaoRangeDev rg = GaoRangeDev{}) {
   using F = Fp<P>;
+  static_assert(!RANGE || SCAN, "the range form is a repair");
   constexpr int N = 4 * L, SP = gao_split(L), M = N / SP;
+  const size_t pitch = RANGE ? (size_t)rg.stride : nchunks;       // elements between two rows
   const int kd = ER ? k + rho : k;       // the dimension the word is tested and evaluated at
   __shared__ uint32_t wg_dirty, wg_base;
   if (threadIdx.x == 0) wg_dirty = 0;
@@ -97,20 +101,21 @@ __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const
         if constexpr (SCAN) {      // the row from the list's bit mask, two scalar operations: 32 row numbers held in scalar
                                    // registers beside the constants made the l = 8 scan spill some
           const int row = __builtin_popcount(listed & ((1u << p) - 1));
-          return (listed >> p) & 1 ? load_elem(shares + (size_t)row * nchunks + j) * ab->lam[p] : F::zero();
+          return (listed >> p) & 1 ? load_elem(shares + (size_t)row * pitch + j) * ab->lam[p] : F::zero();
         }
         const int row = ab->row[p];
-        return row < 0 ? F::zero() : load_elem(shares + (size_t)row * nchunks + j) * ab->lam[p];
+        return row < 0 ? F::zero() : load_elem(shares + (size_t)row * pitch + j) * ab->lam[p];
       }, x);
     else
-      gao_load<M, SP>(c, q, [&](int p) { return load_elem(shares + (size_t)p * nchunks + j); }, x);
+      gao_load<M, SP>(c, q, [&](int p) { return load_elem(shares + (size_t)p * pitch + j); }, x);
     gao_ifft<M, SP>(c, x);
     dirty = !gao_is_clean<M, SP>(x, kd, q);
     if (SP == 2) dirty = __shfl_xor((int)dirty, 1, 64) || dirty;
     if (!dirty) {
       if (q == 0) {
-        status[j] = 0;
-        if (errpos) errpos[j] = 0;
+        const size_t sj = RANGE ? (size_t)rg.chunk((uint32_t)j) : j;
+        status[sj] = 0;
+        if (errpos) errpos[sj] = 0;
       }
       if constexpr (!SCAN) {
         auto put_message = [&](int i, const F& v) { store_elem(message + (size_t)i * nchunks + j, v); };
@@ -183,6 +188,21 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_scan_parties_kernel(const Gao
                                                                       uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage1_body<P, L, true, true>(c, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, &ab, rho, nullptr, listed);
 }
+// the range forms of the two scans above (engine_dist.inc.hpp: a rank's [np][seg] block under the all-to-all king)
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_scan_range_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
+                                                                    GaoRangeDev rg, int k, uint8_t* __restrict__ status,
+                                                                    uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage1_body<P, L, false, true, true>(c, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, nullptr, 0, nullptr, 0, 0,
+                                           rg);
+}
+template <class P, int L>
+__global__ __launch_bounds__(GAO_THREADS) void gao_scan_parties_range_kernel(
+    const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab, const Fp<P>* __restrict__ shares, GaoRangeDev rg, int k, int rho,
+    uint32_t listed, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage1_body<P, L, true, true, true>(c, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, &ab, rho, nullptr, listed,
+                                          0, rg);
+}
 // zk_pss_repair_batch: the scan of item blockIdx.y -- its matrix, its rows of status and errpos, its summary words; the count
 // and the list are the batch's
 template <class P, int L>
@@ -235,15 +255,20 @@ struct GaoBatchItem {
   size_t chunk;
   unsigned long long* sum;
 };
-template <class P, bool ER, bool REPAIR = false, bool BATCH = false>
+// RANGE (a repair, no batch): as in stage 1 -- a list entry is a column, the rows are rg.stride apart, status and errpos are
+// written at rg.chunk(column)
+template <class P, bool ER, bool REPAIR = false, bool BATCH = false, bool RANGE = false>
 __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n, int l, GaoSharesPtr<P, REPAIR> shares,
                                                 size_t nchunks, int k, Fp<P>* __restrict__ secrets,
                                                 Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
                                                 uint32_t* __restrict__ errpos, const GaoWork& wk,
                                                 const GaoAbsent<Fp<P>>* __restrict__ tab,
-                                                const Fp<P>* __restrict__ ilam = nullptr, size_t item_stride = 0) {
+                                                const Fp<P>* __restrict__ ilam = nullptr, size_t item_stride = 0,
+                                                [[maybe_unused]] const GaoRangeDev rg = GaoRangeDev{}) {
   using F = Fp<P>;
   static_assert(!BATCH || REPAIR, "a batch is a repair");
+  static_assert(!RANGE || (REPAIR && !BATCH), "the range form is a repair of one word");
+  const size_t pitch = RANGE ? (size_t)rg.stride : nchunks;       // elements between two rows of a single word
   const uint32_t cnt = *wk.count;
   const uint32_t gpb = GAO_THREADS / n, stride = gridDim.x * gpb;
   if (blockIdx.x * gpb >= cnt) return;
@@ -276,9 +301,9 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
     }();
     F y;
     if constexpr (ER && BATCH) y = live && row >= 0 ? load_elem(it.sh + (size_t)row * nchunks + it.chunk) * lam : F::zero();
-    else if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * nchunks + j) * lam : F::zero();
+    else if constexpr (ER) y = live && row >= 0 ? load_elem(shares + (size_t)row * pitch + j) * lam : F::zero();
     else if constexpr (BATCH) y = live ? load_elem(it.sh + (size_t)p * nchunks + it.chunk) : F::zero();
-    else y = live ? load_elem(shares + (size_t)p * nchunks + j) : F::zero();
+    else y = live ? load_elem(shares + (size_t)p * pitch + j) : F::zero();
     GaoResult<F, GaoDevGroup, REPAIR> r = gao_chunk<F, GaoDevGroup, REPAIR>(g, c, n, kd, live, y, xp, xinv, sp);
     if constexpr (ER) gao_absent_finish<F, GaoDevGroup, REPAIR>(g, k, rho, listed, message != nullptr, slam, lamc, r);
     if (!live) continue;
@@ -287,12 +312,12 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
           g, r, [&](int) { return row; }, [&](int lane) { return load_elem(ilam + lane); },
           [&](int, int at, const F& v) {
             if constexpr (BATCH) store_elem(it.sh + (size_t)at * nchunks + it.chunk, v);
-            else store_elem(shares + (size_t)at * nchunks + j, v);
+            else store_elem(shares + (size_t)at * pitch + j, v);
           });
     } else if constexpr (BATCH) {
       gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(it.sh + (size_t)lane * nchunks + it.chunk, v); });
     } else if constexpr (REPAIR) {
-      gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(shares + (size_t)lane * nchunks + j, v); });
+      gao_repair_word<F, GaoDevGroup>(g, r, [&](int lane, const F& v) { store_elem(shares + (size_t)lane * pitch + j, v); });
     } else {
       if (message && p < k) store_elem(message + (size_t)p * nchunks + j, r.h);
       if (secrets && p < l) store_elem(secrets + j * l + p, r.sec);
@@ -307,8 +332,9 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
       continue;
     }
     if (p == 0) {
-      status[j] = (uint8_t)r.status;
-      if (errpos) errpos[j] = r.errpos;
+      const size_t sj = RANGE ? (size_t)rg.chunk((uint32_t)j) : j;
+      status[sj] = (uint8_t)r.status;
+      if (errpos) errpos[sj] = r.errpos;
       if (r.status == 1) n_status1++;
       else n_status2++;
     }
@@ -339,6 +365,20 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_repair_batch_kernel(const Gao
                                                                       uint32_t* __restrict__ errpos, GaoWork wk) {
   gao_stage2_body<P, false, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr, nullptr,
                                         item_stride);
+}
+// the range forms of gao_repair_kernel and gao_repair_parties_kernel
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_repair_range_kernel(const GaoConsts<Fp<P>> c, int n, int l, Fp<P>* shares,
+                                                                      GaoRangeDev rg, int k, uint8_t* __restrict__ status,
+                                                                      uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage2_body<P, false, true, false, true>(c, n, l, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, nullptr, nullptr,
+                                               0, rg);
+}
+template <class P>
+__global__ __launch_bounds__(GAO_THREADS) void gao_repair_parties_range_kernel(
+    const GaoConsts<Fp<P>> c, const GaoAbsent<Fp<P>>* __restrict__ tab, const Fp<P>* __restrict__ ilam, int n, int l,
+    Fp<P>* shares, GaoRangeDev rg, int k, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
+  gao_stage2_body<P, true, true, false, true>(c, n, l, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, tab, ilam, 0, rg);
 }
 // k: the caller's dimension
 template <class P>
@@ -393,10 +433,11 @@ __global__ __launch_bounds__(GAO_THREADS) void gao_inv_lambda_table_kernel(const
 template <class FrP, bool REPAIR>
 int gao_all_parties_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPAIR, void*, const void*> shares, size_t nchunks,
                         int dimension, void* secrets, void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary,
-                        hipStream_t st) {
+                        hipStream_t st, const GaoRange* rg = nullptr) {
   using Fr = Fp<FrP>;
   const int n = 4 * l;
   if (dimension < 1 || dimension > n - 1) return e->fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
+  if (rg && !REPAIR) return e->fail(ZK_ERR_BAD_INPUT, "the range form is a repair");
   if (nchunks == 0) return ZK_OK;
   if (!shares || !status) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
   if (nchunks >= ((size_t)1 << 32)) return e->fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
@@ -415,6 +456,23 @@ int gao_all_parties_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REP
   std::conditional_t<REPAIR, Fr*, const Fr*> sh = (decltype(sh))shares;
   Fr* sec = (Fr*)secrets;
   Fr* msg = (Fr*)message;
+  if constexpr (REPAIR) {
+    if (rg) {      // the word in a block with padding: nchunks is rg->cnt (gao_repair_range_run)
+      const GaoRangeDev rd = gao_range_dev(*rg);
+      switch (l) {
+        case 1: gao_scan_range_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
+        case 2: gao_scan_range_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
+        case 4: gao_scan_range_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
+        case 8: gao_scan_range_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
+        default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
+      }
+      const size_t gpb_r = GAO_THREADS / n;
+      const dim3 grid_r((unsigned)std::min<size_t>((nchunks + gpb_r - 1) / gpb_r, GAO_STAGE2_GRID));
+      gao_repair_range_kernel<FrP><<<grid_r, blk, 0, st>>>(c, n, l, sh, rd, dimension, status, errpos, wk);
+      GAO_HIP(hipGetLastError());
+      return ZK_OK;
+    }
+  }
   if constexpr (REPAIR) switch (l) {
     case 1: gao_scan_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
     case 2: gao_scan_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
@@ -525,11 +583,12 @@ int gao_repair_batch_parties_run(IEngine* e, void* wkp, int l, void* shares, con
 template <class FrP, bool REPAIR>
 int gao_party_list_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPAIR, void*, const void*> shares,
                        const uint32_t* parties, int np, size_t nchunks, int dimension, void* secrets, void* message,
-                       uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+                       uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st, const GaoRange* rg = nullptr) {
   using Fr = Fp<FrP>;
   const int n = 4 * l;
   if (l != 1 && l != 2 && l != 4 && l != 8) return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
   if (np <= 0 || np > n) return e->fail(ZK_ERR_BAD_INPUT, "bad party count");
+  if (rg && !REPAIR) return e->fail(ZK_ERR_BAD_INPUT, "the range form is a repair");
   uint32_t ids[GAO_MAX_N];
   for (int i = 0; i < np; i++) {
     ids[i] = parties ? parties[i] : (uint32_t)i;
@@ -540,7 +599,7 @@ int gao_party_list_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPA
   if (np <= dimension) return e->fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
   if (np == n)
     return gao_all_parties_run<FrP, REPAIR>(e, wkbuf, l, shares, nchunks, dimension, secrets, message, status, errpos, summary,
-                                            st);
+                                            st, rg);
   if (nchunks == 0) return ZK_OK;
   if (!shares || !status) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
   if (nchunks >= ((size_t)1 << 32)) return e->fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
@@ -569,6 +628,22 @@ int gao_party_list_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPA
   Fr* sec = (Fr*)secrets;
   Fr* msg = (Fr*)message;
   const int k = dimension, rho = a.rho;
+  if constexpr (REPAIR) {
+    if (rg) {      // the word in a block with padding: nchunks is rg->cnt (gao_repair_range_run)
+      const GaoRangeDev rd = gao_range_dev(*rg);
+      switch (l) {
+        case 1: gao_scan_parties_range_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
+        case 2: gao_scan_parties_range_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
+        case 4: gao_scan_parties_range_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
+        default: gao_scan_parties_range_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
+      }
+      const size_t gpb_r = GAO_THREADS / n;
+      const dim3 grid_r((unsigned)std::min<size_t>((nchunks + gpb_r - 1) / gpb_r, GAO_STAGE2_GRID));
+      gao_repair_parties_range_kernel<FrP><<<grid_r, blk, 0, st>>>(c, tab, inv->v, n, l, sh, rd, k, status, errpos, wk);
+      GAO_HIP(hipGetLastError());
+      return ZK_OK;
+    }
+  }
   if constexpr (REPAIR) switch (l) {
     case 1: gao_scan_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
     case 2: gao_scan_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
@@ -600,6 +675,21 @@ int gao_repair_parties_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, const
                            int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
   return gao_party_list_run<FrP, true>(e, wkbuf, l, shares, parties, np, nchunks, dimension, nullptr, nullptr, status, errpos,
                                        summary, st);
+}
+// The range form of zk_pss_repair_parties (gao.hpp): the word's rg.cnt valid columns lie in rows rg.stride elements apart,
+// column c is chunk rg.chunk(c) of a word of rg.len chunks -- status and errpos [rg.len] are written there.  The list,
+// dimension and summary are gao_repair_parties_run's; with no valid column only the summary is cleared.
+template <class FrP>
+int gao_repair_range_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, const uint32_t* parties, int np, const GaoRange& rg,
+                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+  if (rg.cnt > rg.stride || rg.cnt > rg.len || rg.base >= (rg.len ? rg.len : 1) || rg.shift > rg.len ||
+      rg.stride > 0xffffffffull)
+    return e->fail(ZK_ERR_BAD_INPUT, "bad range: cnt <= stride < 2^32, cnt <= len, base < len, shift <= len");
+  int rc = gao_party_list_run<FrP, true>(e, wkbuf, l, shares, parties, np, rg.cnt, dimension, nullptr, nullptr, status, errpos,
+                                         summary, st, &rg);
+  if (rc || rg.cnt) return rc;
+  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)(3 + 4 * l) * 8, st));
+  return ZK_OK;
 }
 #undef GAO_HIP
 

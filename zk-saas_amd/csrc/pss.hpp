@@ -444,6 +444,18 @@ __global__ void a2a_unpack_rows_kernel(const F* __restrict__ recv, int k, size_t
   store_elem(local + (size_t)p * len + g, load_elem(recv + t));
 }
 
+// The summary of a checked round on the net (engine_dist.inc.hpp): every row of out [rows_out][width] becomes the sum of the
+// rows of in [rows_in][width] -- one row copied for every party before the king's scatter (rows_in = 1), or the ranks' counts
+// added after the all-to-all (rows_out = 1).  A few dozen words: one workgroup.
+template <class W>
+__global__ void rows_sum_kernel(const W* __restrict__ in, int rows_in, int width, W* __restrict__ out, int rows_out) {
+  for (int w = (int)threadIdx.x; w < width; w += (int)blockDim.x) {
+    W acc = 0;
+    for (int r = 0; r < rows_in; r++) acc += in[(size_t)r * width + w];
+    for (int r = 0; r < rows_out; r++) out[(size_t)r * width + w] = acc;
+  }
+}
+
 // King closure of deg_red (deg_red.rs:103-111): unpack_missing_shares then pack, per chunk.
 // Batched form (blockIdx.y = item, the proofs of zk_groth16_prove_batch): item y reads in / mul_b / sub_c at
 // + y * in_step, writes out at + y * out_step, uses masks[y] and the randomness stream seed + y * seed_step.

@@ -161,6 +161,56 @@ def dist_circom_h(pp, net, qap_local, log2_m, masks=None, seed=0, out=None, stre
     return out
 
 
+# ---- checked king rounds on the net (zk_dist_*_checked).  Each returns the result together with the report object of the
+# single-device checked calls (api.py RobustUnpack): status / errpos hold the chunks THIS rank was king of (rank 0 all of them
+# under the star king, each rank its range under the all-to-all king; zeros elsewhere), the summary is the whole word's on
+# every rank.  The list is the parties of the ranks the round admitted.
+def dist_d_fft_checked(pp, net, sid, shares_local, fft_mask, rearrange, log2_m, seed=0, stream=None):
+    """zk_dist_d_fft_checked: dist_d_fft with the king's word repaired first (dimension 2l).  Returns (shares_local, report)."""
+    im, om = _mask_ptrs(fft_mask)
+    r = pp._report((1 << log2_m) // pp.l, 2 * pp.l)
+    r.out = shares_local
+    pp._check(pp.lib.zk_dist_d_fft_checked(pp.h, net.h, sid, _ptr(shares_local), im, om, int(rearrange), log2_m, seed,
+                                           _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+    return shares_local, r
+
+
+def dist_d_ifft_checked(pp, net, sid, shares_local, fft_mask, rearrange, log2_m, g=None, seed=0, stream=None):
+    """zk_dist_d_ifft_checked, as dist_d_fft_checked."""
+    im, om = _mask_ptrs(fft_mask)
+    garr = None if g is None else pp.fr.encode_one(g)
+    r = pp._report((1 << log2_m) // pp.l, 2 * pp.l)
+    r.out = shares_local
+    pp._check(pp.lib.zk_dist_d_ifft_checked(pp.h, net.h, sid, _ptr(shares_local), im, om, int(rearrange), log2_m,
+                                            None if garr is None else garr.ctypes.data, seed, _ptr(r.status), _ptr(r.errpos),
+                                            _ptr(r.summary_d), stream))
+    return shares_local, r
+
+
+def dist_deg_red_checked(pp, net, sid, x_local, mask, length, seed=0, stream=None):
+    """zk_dist_deg_red_checked: detection only (dimension 4l - 1); with a rank absent the word is not checked and the report
+    is all zeros.  Returns (x_local, report)."""
+    im, om = _mask_ptrs(mask)
+    r = pp._report(length, 4 * pp.l - 1)
+    r.out = x_local
+    pp._check(pp.lib.zk_dist_deg_red_checked(pp.h, net.h, sid, _ptr(x_local), im, om, length, seed, _ptr(r.status),
+                                             _ptr(r.errpos), _ptr(r.summary_d), stream))
+    return x_local, r
+
+
+def dist_circom_h_checked(pp, net, qap_local, log2_m, masks=None, seed=0, out=None, stream=None):
+    """zk_dist_circom_h_checked: dist_circom_h with its seven king words checked.  Returns (h_local, report), the report as
+    api.h_report's: status and errpos [7][m/l], one summary per item."""
+    from .api import h_report
+    out = out or pp.alloc_fr(net.k * ((1 << log2_m) // pp.l))
+    rep = h_report(pp, log2_m)
+    rep.out = out
+    pp._check(pp.lib.zk_dist_circom_h_checked(pp.h, net.h, _ptr(qap_local[0]), _ptr(qap_local[1]), _ptr(qap_local[2]), log2_m,
+                                              None if masks is None else C.byref(masks), seed, out.ptr, _ptr(rep.status),
+                                              _ptr(rep.errpos), _ptr(rep.summary_d), stream))
+    return out, rep
+
+
 def dist_deg_red_points(pp, net, sid, group, x_local, in_mask_local, out_mask_local, length, gen_affine, seed=0, out=None,
                         stream=None):
     """zk_dist_deg_red_points (deg_red.rs:80-126 with T = G): this rank's rows [k][length] of affine points."""
