@@ -902,6 +902,75 @@ int zk_dist_groth16_prove_batch(zk_ctx* ctx, zk_net* net, const zk_crs_share* cr
                                 int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b,
                                 void* pi_c, void* stream);
 
+/* ---- per-party entry points: ONE CALLER PER PARTY, as the reference calls its primitives ------------------------------
+ * simulate_network_round (mpc-net/src/multi.rs:301-328) runs one task per party; each task calls d_fft / d_msm / dsha256
+ * with its OWN share vector and its own net handle (dist-primitives/src/dfft/mod.rs:99-111, dmsm/mod.rs:59-66,
+ * groth16/examples/sha256.rs:316-360).  A zk_party is that net handle: party `party_id` of the k = n / world parties this
+ * rank drives.  Each zk_party_* call below is the rank call of the same name (zk_dist_d_fft ... zk_dist_groth16_prove)
+ * issued ONCE per round with the k parties' rows, once all k parties of the rank are inside it: it returns what the rank
+ * call returns, and each party's output is its row of the rank call's output.  The rank calls stay, and stay the fast path.
+ *   EXECUTOR  the calls BLOCK in a rendezvous until the rank's other parties have arrived, so a host needs one thread per
+ *             party that can be inside a call at once: k threads, times the channels it keeps open at once.  In an async
+ *             runtime that means spawn_blocking, or at least that many worker threads.
+ *   ROUNDS    per (net, sid) the k callers of a round must pass equal scalar arguments (log2_m, len, rearrange, seed, group,
+ *             the bytes of g, r and s, the CRS lengths, and which pointers are NULL); otherwise all k get ZK_ERR_BAD_INPUT,
+ *             zk_party_last_error names the lowest party that differs from the rank's first party, nothing has entered
+ *             the net round and the net stays usable.  A party that does not arrive within the net's timeout
+ *             (zk_net_set_timeout_ms) fails the round for the waiting parties with ZK_ERR_PROTOCOL and its id; the channel
+ *             then refuses every later call at once, the rank has not entered the net round (the other ranks see a late
+ *             rank), and the net must be rebuilt as after any PROTOCOL result.  Two threads inside the same (party, sid) at
+ *             once: ZK_ERR_BAD_INPUT for the second.  Channels 0..2 may be in flight at once, each with its own rendezvous;
+ *             zk_party_circom_h and zk_party_groth16_prove meet on channel 0 and use the channels their rank calls use.
+ *   STREAMS   a caller's `stream` is its own.  The library records an event on it on arrival; an internal per-(net, sid)
+ *             stream waits for the k events and carries the rank call; every caller's stream then waits for its completion
+ *             event.  As with the rank calls, a call returns with its device work ENQUEUED; the only host waits are the
+ *             rendezvous and whatever the rank call already waits for.
+ *   ROWS      if the k pointers of an operand are the rows of one block (p[i] == p[0] + i * row_bytes, ascending party
+ *             order) the rank call gets the first pointer and nothing is copied; registered fixed-base tables apply.
+ *             Otherwise the operand is staged through a per-(net, sid) buffer (one gather launch, one scatter launch for
+ *             in-place outputs); staged MSM bases never use a registered table.  A row that is not 16-byte aligned is
+ *             ZK_ERR_BAD_INPUT.  k is at most 32.
+ * zk_net_party: party_id not driven by this rank (or k > 32) -> ZK_ERR_BAD_INPUT.  Handles are released before their net is
+ * destroyed.  A party may be driven through any number of handles, one after another (a handle per task is fine): the order
+ * of its calls on a channel belongs to the party, not to a handle.  zk_party_last_error: per handle, so that k threads do not share one string.  zk_party_stats: rounds issued,
+ * of them zero-copy, of them staged, bytes staged (both directions), since the net's first zk_net_party. */
+typedef struct zk_party zk_party;
+int zk_net_party(zk_net* net, int party_id, zk_party** out);
+void zk_party_release(zk_party* p);
+int zk_party_id(const zk_party* p);
+const char* zk_party_last_error(zk_party* p, int* party);
+int zk_party_stats(zk_net* net, uint64_t stats[4]);
+/* d_fft(pd_shares, rearrange, &FftMask, pp, &net, sid), dist-primitives/src/dfft/mod.rs:99-134: share_d [m/l] in place,
+ * masks [m/l] or NULL */
+int zk_party_d_fft(zk_ctx* ctx, zk_party* p, int sid, void* share_d, const void* in_mask_d, const void* out_mask_d,
+                   int rearrange, int log2_m, uint64_t seed, void* stream);
+/* d_ifft(pd_shares, rearrange, &FftMask, dom, g, pp, &net, sid), dfft/mod.rs:137-175 */
+int zk_party_d_ifft(zk_ctx* ctx, zk_party* p, int sid, void* share_d, const void* in_mask_d, const void* out_mask_d,
+                    int rearrange, int log2_m, const void* g, uint64_t seed, void* stream);
+/* deg_red(px, pp, &DegRedMask, &net, sid), dist-primitives/src/utils/deg_red.rs:80-126: x_d [len] in place */
+int zk_party_deg_red(zk_ctx* ctx, zk_party* p, int sid, void* x_d, const void* in_mask_d, const void* out_mask_d, size_t len,
+                     uint64_t seed, void* stream);
+/* d_pp(num, den, &DegRedMask, pp, &net, sid), dist-primitives/src/dpp/mod.rs:15-87: num_d, den_d, out_d [len] */
+int zk_party_d_pp(zk_ctx* ctx, zk_party* p, int sid, const void* num_d, const void* den_d, const void* in_mask_d,
+                  const void* out_mask_d, size_t len, uint64_t seed, void* out_d, void* stream);
+/* d_msm(bases, scalars, &MsmMask, pp, &net, sid), dist-primitives/src/dmsm/mod.rs:59-102: bases_d, scalars_d [len];
+ * in_mask / out_mask: ONE Jacobian point each (host) or NULL; out: one Jacobian point (host) */
+int zk_party_d_msm(zk_ctx* ctx, zk_party* p, int sid, int group, const void* bases_d, const void* scalars_d, size_t len,
+                   const void* in_mask, const void* out_mask, void* out, void* stream);
+/* circom_h(qap_share, pp, masks.., &net), groth16/src/ext_wit.rs:104-181: qap_*_d, h_d [m/l]; the Fr-vector members of
+ * `masks` are THIS PARTY's rows (the MSM members are not read) */
+int zk_party_circom_h(zk_ctx* ctx, zk_party* p, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
+                      const zk_groth16_masks* masks, uint64_t seed, void* h_d, void* stream);
+/* dsha256(pp, crs_share, qap_share, a_share, ax_share, .., &net), groth16/examples/sha256.rs:32-129: the five share vectors of
+ * `crs` (s_d .. u_d, [len] each), the QAP and witness shares and every member of `masks` are THIS PARTY's rows (MSM masks:
+ * one Jacobian point each, host); pi_a / pi_c: one Jacobian G1, pi_b: one Jacobian G2 (host).  The members of `crs` that are
+ * not party rows (a_query0, b_g1_query0, delta_g1, alpha_g1, beta_g1, b_g2_query0, delta_g2, beta_g2) are taken from the
+ * RANK'S FIRST PARTY; the lengths must agree across the round. */
+int zk_party_groth16_prove(zk_ctx* ctx, zk_party* p, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
+                           const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
+                           int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                           void* stream);
+
 /* ---- host-pointer forms of the primitives (the reference's own signatures take and return host vectors: dfft/mod.rs:99,
  * dmsm/mod.rs:59): the call stages its operands through device scratch (H2D, compute, D2H) and returns when the result is
  * in host memory.  zk_d_fft_host: shares [n][m/l] in place, masks host [n][m/l] or NULL, inverse != 0 = d_ifft with the

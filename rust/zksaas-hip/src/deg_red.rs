@@ -18,7 +18,7 @@ use mpc_net::{MpcNetError, MultiplexedStreamID};
 use secret_sharing::pss::PackedSharingParams;
 use zksaas_hip_sys as sys;
 
-use crate::{check, group_of, pack_affine, same_slice, same_vec, unpack_affine, Context, DeviceBuf, HipNet};
+use crate::{check, group_of, pack_affine, same_slice, same_vec, unpack_affine, Backend, Context, DeviceBuf, HipNet, PartyNet};
 
 /// `deg_red.rs:80-126`: mask add -> gather -> king `unpack2` then `pack` per chunk -> scatter -> unmask.
 pub async fn deg_red<
@@ -33,7 +33,23 @@ pub async fn deg_red<
     net: &Net,
     sid: MultiplexedStreamID,
 ) -> Result<Vec<T>, MpcNetError> {
-    let hip = HipNet::of(net)?;
+    let hip = match HipNet::backend(net)? {
+        Backend::Rank(h) => h,
+        Backend::Party(pn) => {
+            // one party's vector through `zk_party_deg_red` (field elements; the group form has no per-party call yet)
+            pn.ctx().expect_field::<F>(pp.l)?;
+            if in_mask.len() != x_share.len() || out_mask.len() != x_share.len() {
+                return Err(MpcNetError::BadInput { err: "DegRedMask length differs from the share vector" });
+            }
+            if TypeId::of::<T>() != TypeId::of::<F>() {
+                return Err(MpcNetError::BadInput { err: "PartyNet: deg_red over group elements is per rank only" });
+            }
+            let x = same_vec::<T, F>(x_share).map_err(|_| MpcNetError::BadInput { err: "unreachable" })?;
+            let (im, om) = (same_slice::<T, F>(in_mask).unwrap(), same_slice::<T, F>(out_mask).unwrap());
+            let out = deg_red_party(pn, x, im, om, sid)?;
+            return same_vec::<F, T>(out).map_err(|_| MpcNetError::BadInput { err: "unreachable" });
+        }
+    };
     hip.ctx().expect_field::<F>(pp.l)?;
     let len = x_share.len();
     if in_mask.len() != len || out_mask.len() != len {
@@ -65,6 +81,19 @@ fn deg_red_field<F: FftField>(hip: &HipNet, x_share: Vec<F>, in_mask: &[F], out_
                              ptr::null_mut())
     })?;
     check(ctx, unsafe { sys::zk_net_sync(hip.raw_net(), sid as i32) })?;
+    x.to_vec(len)
+}
+
+fn deg_red_party<F: FftField>(pn: &PartyNet, x_share: Vec<F>, in_mask: &[F], out_mask: &[F], sid: MultiplexedStreamID)
+                              -> Result<Vec<F>, MpcNetError> {
+    let (ctx, len) = (pn.ctx(), x_share.len());
+    let x = DeviceBuf::from_slice(ctx, &x_share)?;
+    let im = DeviceBuf::from_slice(ctx, in_mask)?;
+    let om = DeviceBuf::from_slice(ctx, out_mask)?;
+    pn.check(unsafe {
+        sys::zk_party_deg_red(ctx.raw(), pn.raw_party(), sid as i32, x.ptr(), im.ptr(), om.ptr(), len, 0, ptr::null_mut())
+    })?;
+    check(ctx, unsafe { sys::zk_net_sync(pn.hip().raw_net(), sid as i32) })?;
     x.to_vec(len)
 }
 

@@ -17,7 +17,7 @@ use mpc_net::{MpcNetError, MultiplexedStreamID};
 use secret_sharing::pss::PackedSharingParams;
 use zksaas_hip_sys as sys;
 
-use crate::{check, Context, DeviceBuf, HipNet};
+use crate::{check, Backend, Context, DeviceBuf, HipNet, PartyNet};
 
 fn masks_dev<F: PrimeField>(ctx: &Context, in_mask: &[F], out_mask: &[F], len: usize)
                             -> Result<(Option<DeviceBuf>, Option<DeviceBuf>), MpcNetError> {
@@ -37,6 +37,34 @@ fn p(b: &Option<DeviceBuf>) -> *const c_void {
     b.as_ref().map(|b| b.ptr() as *const c_void).unwrap_or(ptr::null())
 }
 
+/// One party's `d_fft` / `d_ifft` through `zk_party_d_fft` / `zk_party_d_ifft`: `share` is that party's `[m/l]` vector.  The
+/// masks are always uploaded: whether a mask pointer is NULL must agree across the parties of a rank, and whether ONE
+/// party's mask happens to be all zero is not something the others know.
+fn party_fft<F: FftField + PrimeField>(pn: &PartyNet, share: Vec<F>, in_mask: &[F], out_mask: &[F], rearrange: bool,
+                                       log2_m: i32, g: Option<F>, l: usize, sid: MultiplexedStreamID)
+                                       -> Result<Vec<F>, MpcNetError> {
+    let ctx = pn.ctx();
+    ctx.expect_field::<F>(l)?;
+    if in_mask.len() != share.len() || out_mask.len() != share.len() {
+        return Err(MpcNetError::BadInput { err: "FftMask length differs from the share vector" });
+    }
+    let sh = DeviceBuf::from_slice(ctx, &share)?;
+    let (im, om) = (DeviceBuf::from_slice(ctx, in_mask)?, DeviceBuf::from_slice(ctx, out_mask)?);
+    pn.check(unsafe {
+        match g {
+            None => sys::zk_party_d_fft(ctx.raw(), pn.raw_party(), sid as i32, sh.ptr(), im.ptr(), om.ptr(), rearrange as i32,
+                                        log2_m, 0, ptr::null_mut()),
+            Some(g) => {
+                let gl = [g];
+                sys::zk_party_d_ifft(ctx.raw(), pn.raw_party(), sid as i32, sh.ptr(), im.ptr(), om.ptr(), rearrange as i32,
+                                     log2_m, crate::fr_ptr(&gl), 0, ptr::null_mut())
+            }
+        }
+    })?;
+    check(ctx, unsafe { sys::zk_net_sync(pn.hip().raw_net(), sid as i32) })?;
+    sh.to_vec(share.len())
+}
+
 /// `dist-primitives/src/dfft/mod.rs:99-134`.  `pcoeff_share`: this rank's `k` parties' vectors, `[k][m/l]` flattened
 /// (`k = 1` in the reference's one-process-per-party deployment, where it is exactly the reference's argument).
 pub async fn d_fft<
@@ -53,7 +81,15 @@ pub async fn d_fft<
     net: &Net,
     sid: MultiplexedStreamID,
 ) -> Result<Vec<F>, MpcNetError> {
-    let hip = HipNet::of(net)?;
+    let hip = match HipNet::backend(net)? {
+        Backend::Rank(h) => h,
+        Backend::Party(pn) => {
+            if pcoeff_share.len() * pp.l != dom.size() {
+                return Err(MpcNetError::BadInput { err: "Mismatch of size in FFT" });
+            }
+            return party_fft(pn, pcoeff_share, in_mask, out_mask, rearrange, dom.log_size_of_group() as i32, None, pp.l, sid);
+        }
+    };
     let k = hip.parties_per_rank();
     if pcoeff_share.len() * pp.l != dom.size() * k {
         // the reference debug_asserts (`:112-118`); here the mismatch is an error in every build
@@ -88,7 +124,15 @@ pub async fn d_ifft<
     net: &Net,
     sid: MultiplexedStreamID,
 ) -> Result<Vec<F>, MpcNetError> {
-    let hip = HipNet::of(net)?;
+    let hip = match HipNet::backend(net)? {
+        Backend::Rank(h) => h,
+        Backend::Party(pn) => {
+            if peval_share.len() * pp.l != dom.size() {
+                return Err(MpcNetError::BadInput { err: "Mismatch of size in IFFT" });
+            }
+            return party_fft(pn, peval_share, in_mask, out_mask, rearrange, dom.log_size_of_group() as i32, Some(g), pp.l, sid);
+        }
+    };
     let k = hip.parties_per_rank();
     if peval_share.len() * pp.l != dom.size() * k {
         return Err(MpcNetError::BadInput { err: "Mismatch of size in IFFT" });

@@ -13,7 +13,7 @@ use mpc_net::{MpcNetError, MultiplexedStreamID};
 use secret_sharing::pss::PackedSharingParams;
 use zksaas_hip_sys as sys;
 
-use crate::{check, group_of, pack_affine, pack_jacobian, same_slice, same_value, unpack_jacobian, DeviceBuf, HipNet};
+use crate::{check, group_of, pack_affine, pack_jacobian, same_slice, same_value, unpack_jacobian, Backend, DeviceBuf, HipNet, PartyNet};
 
 /// `dist-primitives/src/dmsm/mod.rs:59-102`.  A length mismatch is the `Generic(min_len.to_string())` the reference
 /// gets from `G::msm` (`:73`).  One party per rank (`d_msm_rows` carries `k` parties).
@@ -26,7 +26,21 @@ pub async fn d_msm<G: CurveGroup, Net: MpcSerNet>(
     net: &Net,
     sid: MultiplexedStreamID,
 ) -> Result<G, MpcNetError> {
-    let hip = HipNet::of(net)?;
+    let hip = match HipNet::backend(net)? {
+        Backend::Rank(h) => h,
+        Backend::Party(pn) => {
+            // one party of a rank that drives k of them: this signature IS one party's vectors (`zk_party_d_msm`)
+            pn.ctx().expect_field::<G::ScalarField>(pp.l)?;
+            return crate::sw_dispatch!(G, C => {
+                let b = same_slice::<G::Affine, Affine<C>>(bases).expect("G::Affine is Affine<C>");
+                let s = same_slice::<G::ScalarField, <C as ark_ec::CurveConfig>::ScalarField>(scalars).expect("same scalar field");
+                let im = same_value::<G, Projective<C>>(*in_mask).expect("G is Projective<C>");
+                let om = same_value::<G, Projective<C>>(*out_mask).expect("G is Projective<C>");
+                let out = d_msm_party::<C>(b, s, im, om, pn, sid)?;
+                Ok(same_value::<Projective<C>, G>(out).expect("G is Projective<C>"))
+            });
+        }
+    };
     hip.ctx().expect_field::<G::ScalarField>(pp.l)?;
     if hip.parties_per_rank() != 1 {
         return Err(MpcNetError::BadInput { err: "d_msm: this signature carries one party's vectors (see d_msm_rows)" });
@@ -40,6 +54,26 @@ pub async fn d_msm<G: CurveGroup, Net: MpcSerNet>(
         let out = d_msm_rows::<C>(b, s, b.len().min(s.len()), &[im], &[om], hip, sid, b.len() != s.len())?;
         Ok(same_value::<Projective<C>, G>(out[0]).expect("G is Projective<C>"))
     })
+}
+
+/// `zk_party_d_msm`: one party's bases, scalars and masks; its output share.
+pub fn d_msm_party<C: SWCurveConfig>(bases: &[Affine<C>], scalars: &[C::ScalarField], in_mask: Projective<C>,
+                                     out_mask: Projective<C>, pn: &PartyNet, sid: MultiplexedStreamID)
+                                     -> Result<Projective<C>, MpcNetError> {
+    if bases.len() != scalars.len() {
+        return Err(MpcNetError::Generic(bases.len().min(scalars.len()).to_string()));      // `dmsm/mod.rs:73`
+    }
+    let ctx = pn.ctx();
+    let b = DeviceBuf::from_slice(ctx, &pack_affine(bases))?;
+    let s = DeviceBuf::from_slice(ctx, scalars)?;
+    let (im, om) = (pack_jacobian(&[in_mask]), pack_jacobian(&[out_mask]));
+    let mut out = vec![0u64; im.len()];
+    pn.check(unsafe {
+        sys::zk_party_d_msm(ctx.raw(), pn.raw_party(), sid as i32, group_of::<C>(), b.ptr(), s.ptr(), bases.len(),
+                            im.as_ptr() as *const c_void, om.as_ptr() as *const c_void, out.as_mut_ptr() as *mut c_void,
+                            ptr::null_mut())
+    })?;
+    Ok(unpack_jacobian::<C>(&out, 1)[0])
 }
 
 /// The same for a rank that drives `k` parties: rows `[k][len]`, `k` masks, `k` results.

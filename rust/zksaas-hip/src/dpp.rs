@@ -13,7 +13,7 @@ use mpc_net::{MpcNetError, MultiplexedStreamID};
 use secret_sharing::pss::PackedSharingParams;
 use zksaas_hip_sys as sys;
 
-use crate::{check, DeviceBuf, HipNet};
+use crate::{check, Backend, DeviceBuf, HipNet};
 
 /// `dist-primitives/src/dpp/mod.rs:15-87`.
 pub async fn d_pp<F: FftField + PrimeField + Field, Net: MpcSerNet>(
@@ -25,11 +25,29 @@ pub async fn d_pp<F: FftField + PrimeField + Field, Net: MpcSerNet>(
     net: &Net,
     sid: MultiplexedStreamID,
 ) -> Result<Vec<F>, MpcNetError> {
-    let hip = HipNet::of(net)?;
     let len = num.len();
     if den.len() != len || in_mask.len() != len || out_mask.len() != len {
         return Err(MpcNetError::BadInput { err: "d_pp: num, den and the DegRedMask must have one length" });
     }
+    let hip = match HipNet::backend(net)? {
+        Backend::Rank(h) => h,
+        Backend::Party(pn) => {
+            // one party's vectors through `zk_party_d_pp`
+            let ctx = pn.ctx();
+            ctx.expect_field::<F>(pp.l)?;
+            let n_d = DeviceBuf::from_slice(ctx, &num)?;
+            let d_d = DeviceBuf::from_slice(ctx, &den)?;
+            let im = DeviceBuf::from_slice(ctx, in_mask)?;
+            let om = DeviceBuf::from_slice(ctx, out_mask)?;
+            let out = DeviceBuf::alloc(ctx, n_d.bytes)?;
+            pn.check(unsafe {
+                sys::zk_party_d_pp(ctx.raw(), pn.raw_party(), sid as i32, n_d.ptr(), d_d.ptr(), im.ptr(), om.ptr(), len, 0,
+                                   out.ptr(), ptr::null_mut())
+            })?;
+            check(ctx, unsafe { sys::zk_net_sync(pn.hip().raw_net(), sid as i32) })?;
+            return out.to_vec(len);
+        }
+    };
     let ctx = hip.ctx();
     ctx.expect_field::<F>(pp.l)?;
     let k = hip.parties_per_rank();

@@ -41,7 +41,7 @@ use mpc_net::MpcNetError;
 use zksaas_hip_sys as sys;
 
 pub use error::check;
-pub use net::{HipNet, Transport};
+pub use net::{Backend, HipNet, PartyNet, Transport};
 
 /// `Some(v)` seen as a slice of `B` iff `A` and `B` are the same type (`TypeId`): the monomorphised dispatch from a
 /// generic parameter to the concrete type a branch is written for.  Not a transmute between different types.

@@ -11,6 +11,8 @@ use core::any::Any;
 use core::ffi::c_void;
 use core::ptr;
 use std::collections::HashMap;
+use std::ffi::CStr;
+use std::sync::Arc;
 use std::time::Duration;
 
 use async_trait::async_trait;
@@ -87,6 +89,28 @@ impl HipNet {
     /// Waits for a channel's transfers with the timeout as a deadline (a hung collective becomes `Protocol`).
     pub fn sync(&self, sid: MultiplexedStreamID) -> Result<(), MpcNetError> {
         check(&self.ctx, unsafe { sys::zk_net_sync(self.raw, sid as i32) })
+    }
+    /// The net handle of ONE of this rank's parties (`zk_net_party`): what a per-party task of the reference holds
+    /// (`mpc-net/src/multi.rs:301-328` runs one task per party).  `party_id()` of the result is `p`; `d_fft`, `d_ifft`,
+    /// `d_msm`, `deg_red` and `d_pp` of this crate take it and call the `zk_party_*` form with that party's own vectors,
+    /// at any `k = n / world`.  Those calls BLOCK until the rank's other parties are inside the same call: give every
+    /// party a thread of its own (`tokio::task::spawn_blocking`, or at least `k` worker threads, times the channels kept
+    /// open at once).  The byte collectives keep their `k == 1` condition.
+    pub fn party(self: &Arc<Self>, p: usize) -> Result<PartyNet, MpcNetError> {
+        let mut raw: *mut sys::ZkParty = ptr::null_mut();
+        let rc = unsafe { sys::zk_net_party(self.raw, p as i32, &mut raw) };
+        if rc != sys::ZK_OK {
+            return Err(MpcNetError::BadInput { err: "HipNet::party: not a party of this rank (or more than 32 parties per rank)" });
+        }
+        Ok(PartyNet { net: self.clone(), raw, id: p })
+    }
+    /// Which of the two handles a `Net: MpcNet` is: the rank's (`HipNet`) or one party's (`PartyNet`).
+    pub fn backend<Net: MpcNet + ?Sized>(net: &Net) -> Result<Backend<'_>, MpcNetError> {
+        let any = net.hip_backend().ok_or(MpcNetError::NotConnected)?;
+        if let Some(h) = any.downcast_ref::<HipNet>() {
+            return Ok(Backend::Rank(h));
+        }
+        any.downcast_ref::<PartyNet>().map(Backend::Party).ok_or(MpcNetError::NotConnected)
     }
     fn byte_collectives_need_one_party_per_rank(&self) -> Result<(), MpcNetError> {
         if self.k != 1 {
@@ -190,5 +214,78 @@ impl MpcNet for HipNet {
         check(&self.ctx, unsafe { sys::zk_net_scatter(self.raw, sid as i32, mask, full.ptr(), m, local.ptr()) })?;
         self.sync(sid)?;
         Ok(Bytes::from(local.to_vec::<u8>(m)?))
+    }
+}
+
+/// What `HipNet::backend` finds behind a `Net: MpcNet`.
+pub enum Backend<'a> {
+    Rank(&'a HipNet),
+    Party(&'a PartyNet),
+}
+
+/// One party of a rank (`zk_party`): an `MpcNet` whose `party_id()` is that party's.  Nothing under `rust/` can be compiled
+/// in the build image of this repository; `tests/test_rust_ffi.py` keeps the declarations it calls honest.
+pub struct PartyNet {
+    net: Arc<HipNet>,
+    raw: *mut sys::ZkParty,
+    id: usize,
+}
+unsafe impl Send for PartyNet {}
+unsafe impl Sync for PartyNet {}
+
+impl PartyNet {
+    pub fn hip(&self) -> &HipNet {
+        &self.net
+    }
+    pub fn ctx(&self) -> &Context {
+        self.net.ctx()
+    }
+    pub fn raw_party(&self) -> *mut sys::ZkParty {
+        self.raw
+    }
+    /// `error::check` with this handle's own message (`zk_party_last_error`: the k threads of a rank do not share one).
+    pub fn check(&self, rc: i32) -> Result<(), MpcNetError> {
+        if rc == sys::ZK_OK {
+            return Ok(());
+        }
+        let mut party = -1i32;
+        let err = unsafe { CStr::from_ptr(sys::zk_party_last_error(self.raw, &mut party)) }.to_string_lossy().into_owned();
+        match rc {
+            sys::ZK_ERR_PROTOCOL => Err(MpcNetError::Protocol { err, party: party.max(0) as u32 }),
+            sys::ZK_ERR_NOT_CONNECTED => Err(MpcNetError::NotConnected),
+            sys::ZK_ERR_BAD_INPUT => {
+                eprintln!("zksaas-hip: bad input: {err}");
+                Err(MpcNetError::BadInput { err: "zksaas-hip: bad input (see log)" })
+            }
+            _ => Err(MpcNetError::Generic(err)),
+        }
+    }
+}
+impl Drop for PartyNet {
+    fn drop(&mut self) {
+        unsafe { sys::zk_party_release(self.raw) }
+    }
+}
+
+#[async_trait]
+impl MpcNet for PartyNet {
+    fn n_parties(&self) -> usize {
+        self.net.n_parties()
+    }
+    fn party_id(&self) -> u32 {
+        self.id as u32
+    }
+    fn is_init(&self) -> bool {
+        !self.raw.is_null()
+    }
+    fn hip_backend(&self) -> Option<&(dyn Any + Send + Sync)> {
+        Some(self)
+    }
+    /// Byte-level messages address parties; they exist at `k == 1` only, on the rank's handle.
+    async fn recv_from(&self, _id: u32, _sid: MultiplexedStreamID) -> Result<Bytes, MpcNetError> {
+        Err(MpcNetError::BadInput { err: "PartyNet: byte-level messages are not carried for k > 1; use the primitives" })
+    }
+    async fn send_to(&self, _id: u32, _bytes: Bytes, _sid: MultiplexedStreamID) -> Result<(), MpcNetError> {
+        Err(MpcNetError::BadInput { err: "PartyNet: byte-level messages are not carried for k > 1; use the primitives" })
     }
 }

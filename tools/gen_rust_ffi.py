@@ -20,7 +20,7 @@ OUT = os.path.join(ROOT, "rust", "zksaas-hip-sys", "src", "lib.rs")
 
 SCALARS = {"int": "c_int", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "long long": "c_longlong",
            "long": "c_long", "double": "f64", "char": "c_char", "void": "c_void"}
-STRUCTS = {"zk_ctx": "ZkCtx", "zk_net": "ZkNet", "zk_vk": "ZkVk", "zk_crs_share": "ZkCrsShare", "zk_groth16_masks": "ZkGroth16Masks"}
+STRUCTS = {"zk_ctx": "ZkCtx", "zk_net": "ZkNet", "zk_vk": "ZkVk", "zk_party": "ZkParty", "zk_crs_share": "ZkCrsShare", "zk_groth16_masks": "ZkGroth16Masks"}
 
 
 def strip_comments(text):
@@ -151,7 +151,7 @@ def emit(consts, enums, structs, funcs, cites):
         for k, v in vals:
             o.append("pub const %s: c_int = %d;" % (k, v))
     o.append("")
-    for opaque in ("zk_ctx", "zk_net", "zk_vk"):
+    for opaque in ("zk_ctx", "zk_net", "zk_vk", "zk_party"):
         o.append("/// opaque `%s`" % opaque)
         o.append("#[repr(C)]")
         o.append("pub struct %s {" % STRUCTS[opaque])

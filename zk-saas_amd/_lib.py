@@ -41,6 +41,8 @@ SYMBOLS = [
     "zk_pss_repair_batch_parties", "zk_circom_h_checked_parties", "zk_groth16_prove_checked_parties",
     "zk_pss_repair_range", "zk_dist_d_fft_checked", "zk_dist_d_ifft_checked", "zk_dist_deg_red_checked",
     "zk_dist_circom_h_checked",
+    "zk_net_party", "zk_party_release", "zk_party_id", "zk_party_last_error", "zk_party_stats", "zk_party_d_fft",
+    "zk_party_d_ifft", "zk_party_deg_red", "zk_party_d_pp", "zk_party_d_msm", "zk_party_circom_h", "zk_party_groth16_prove",
 ]
 
 _lib = None
@@ -252,6 +254,20 @@ def load():
                                                      vp, vp]
     u32 = C.c_uint32
     lib.zk_pss_repair_range.argtypes = [vp, vp, ids, i32, sz, u32, u32, u32, u32, i32, vp, vp, vp, vp]
+    lib.zk_net_party.argtypes = [vp, i32, C.POINTER(vp)]
+    lib.zk_party_release.argtypes = [vp]
+    lib.zk_party_release.restype = None
+    lib.zk_party_id.argtypes = [vp]
+    lib.zk_party_last_error.argtypes = [vp, C.POINTER(i32)]
+    lib.zk_party_last_error.restype = C.c_char_p
+    lib.zk_party_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.zk_party_d_fft.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, u64, vp]
+    lib.zk_party_d_ifft.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, u64, vp]
+    lib.zk_party_deg_red.argtypes = [vp, vp, i32, vp, vp, vp, sz, u64, vp]
+    lib.zk_party_d_pp.argtypes = [vp, vp, i32, vp, vp, vp, vp, sz, u64, vp, vp]
+    lib.zk_party_d_msm.argtypes = [vp, vp, i32, i32, vp, vp, sz, vp, vp, vp, vp]
+    lib.zk_party_circom_h.argtypes = [vp, vp, vp, vp, vp, i32, vp, u64, vp, vp]
+    lib.zk_party_groth16_prove.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp]
     lib.zk_dist_d_fft_checked.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, u64, vp, vp, vp, vp]
     lib.zk_dist_d_ifft_checked.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, u64, vp, vp, vp, vp]
     lib.zk_dist_deg_red_checked.argtypes = [vp, vp, i32, vp, vp, vp, sz, u64, vp, vp, vp, vp]

@@ -3,6 +3,9 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 
@@ -18,6 +21,18 @@ struct zk_ctx {
 struct zk_net {
   zk::Net net;
   std::string last;      // message of the last failure of a raw verb
+  // the per-party entry points: made by the first zk_net_party (declared after `net`: its streams go before the net's)
+  std::mutex hub_mu;
+  std::unique_ptr<zk::PartyHub> hub;
+};
+// One party of a rank (zk_net_party).  `last` is this handle's own error string, so that k threads do not share one.  The
+// per-(party, sid) sequence numbers live in the net's hub: a party may be driven through any number of handles, one after another.
+struct zk_party {
+  zk_net* net = nullptr;
+  int local = 0, id = 0;
+  hipEvent_t ev[zk::NET_NSID] = {nullptr, nullptr, nullptr, nullptr};
+  std::mutex mu;
+  zk::Status last;
 };
 
 using zk::IEngine;
@@ -762,6 +777,185 @@ int zk_dist_groth16_prove_batch(zk_ctx* ctx, zk_net* net, const zk_crs_share* cr
   NET_OR_FAIL();
   return e->dist_finish(&net->net, e->dist_prove_batch(&net->net, crs, nproofs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m,
                              masks, seed, pi_a, pi_b, pi_c, S(stream)));
+}
+
+// ---- per-party entry points: one caller per party, the rendezvous of party_rdv.hpp per (net, sid) ----
+int zk_net_party(zk_net* net, int party_id, zk_party** out) {
+  if (!out) return ZK_ERR_BAD_INPUT;
+  *out = nullptr;
+  if (!net) return ZK_ERR_BAD_INPUT;
+  zk::Net& N = net->net;
+  const int k = N.parties_per_rank();
+  if (k < 1 || k > zk::PARTY_MAXK) return N.fail("zk_net_party: a rank drives at most 32 parties", ZK_ERR_BAD_INPUT);
+  int local = -1, ids[zk::PARTY_MAXK];
+  for (int i = 0; i < k; i++) {
+    ids[i] = N.party(N.rank, i);
+    if (ids[i] == party_id) local = i;
+  }
+  if (local < 0) return N.fail("zk_net_party: party " + std::to_string(party_id) + " is not driven by this rank", ZK_ERR_BAD_INPUT);
+  {
+    std::lock_guard<std::mutex> lk(net->hub_mu);
+    if (!net->hub) {
+      net->hub.reset(new (std::nothrow) zk::PartyHub());
+      if (!net->hub) return ZK_ERR_GENERIC;
+      net->hub->k = k;
+      for (auto& s : net->hub->slot) s.init(k, ids);
+    }
+  }
+  zk_party* p = new (std::nothrow) zk_party();
+  if (!p) return ZK_ERR_GENERIC;
+  p->net = net;
+  p->local = local;
+  p->id = party_id;
+  *out = p;
+  return ZK_OK;
+}
+void zk_party_release(zk_party* p) {
+  if (!p) return;
+  for (hipEvent_t e : p->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete p;
+}
+int zk_party_id(const zk_party* p) { return p ? p->id : -1; }
+const char* zk_party_last_error(zk_party* p, int* party) {
+  if (!p) return "null party";
+  if (party) *party = p->last.party;
+  return p->last.msg.c_str();
+}
+int zk_party_stats(zk_net* net, uint64_t stats[4]) {
+  if (!net || !stats) return ZK_ERR_BAD_INPUT;
+  std::lock_guard<std::mutex> lk(net->hub_mu);
+  for (int i = 0; i < 4; i++) stats[i] = net->hub ? net->hub->stats[i].load(std::memory_order_relaxed) : 0;
+  return ZK_OK;
+}
+
+// arrival of one party: record the event on the caller's stream, join the round, keep the round's result in the handle
+static int party_call(zk_ctx* ctx, zk_party* p, int sid, zk::PartyRec& rec, const zk_crs_share* crs, void* stream) {
+  if (!ctx || !p) return ZK_ERR_BAD_INPUT;
+  IEngine* e = ctx->eng;
+  (void)hipSetDevice(e->device);
+  auto refuse = [&](int code, const char* m) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->last.code = code, p->last.msg = m, p->last.party = p->id;
+    return code;
+  };
+  zk_net* net = p->net;
+  if (net->net.host_mode) return refuse(ZK_ERR_BAD_INPUT, "host-mode net");
+  if (sid < 0 || sid >= zk::NET_NSID) return refuse(ZK_ERR_BAD_INPUT, "bad channel id");
+  if (!p->ev[sid] && hipEventCreateWithFlags(&p->ev[sid], hipEventDisableTiming) != hipSuccess)
+    return refuse(ZK_ERR_GENERIC, "hipEventCreate");
+  rec.h[0] = (void*)S(stream);
+  rec.h[1] = (void*)p->ev[sid];
+  rec.caller = (void*)crs;
+  // what the rank call itself may wait for: the king's answer (2 x timeout + 1 s, net.hpp), its transfers, the engine's waits
+  const uint64_t to = net->net.timeout_ms;
+  const int64_t wd = e->wait_deadline_ms.load(std::memory_order_relaxed);
+  const uint64_t issue_ms = 4 * to + 2000 + (wd > 0 ? (uint64_t)wd : 3600000ull);
+  zk::PartyHub* hub = net->hub.get();
+  const uint64_t seq = hub->seq[sid][p->local].load();
+  // the event is recorded once the rendezvous has ADMITTED this caller: a second thread inside the same (party, sid) is
+  // refused before it could re-record the handle's event on another stream
+  zk::PartyResult r = hub->slot[sid].arrive(
+      p->local, seq, rec, to, issue_ms,
+      [&](const zk::PartyRec* recs) { return e->party_issue(&net->net, hub, sid, recs); },
+      [&] { return hipEventRecord(p->ev[sid], S(stream)) == hipSuccess; });
+  if (r.counted) hub->seq[sid][p->local].store(seq + 1);
+  if (r.code != ZK_OK) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->last.code = r.code, p->last.msg = r.msg, p->last.party = r.party;
+  }
+  return r.code;
+}
+static inline void party_ptrs(zk::PartyRec& rec, std::initializer_list<const void*> ps) {
+  int i = 0;
+  for (const void* q : ps) {
+    rec.ptr[i] = q;
+    if (!q) rec.null_bits |= 1ull << i;
+    i++;
+  }
+}
+static int party_fft(zk_ctx* ctx, zk_party* p, int sid, int op, void* share_d, const void* in_mask_d, const void* out_mask_d,
+                     int rearrange, int log2_m, const void* g, uint64_t seed, void* stream) {
+  zk::PartyRec rec;
+  rec.op = op, rec.rearrange = rearrange, rec.log2_m = log2_m, rec.seed = seed;
+  party_ptrs(rec, {share_d, in_mask_d, out_mask_d});
+  if (g && ctx) {
+    rec.g_len = (uint32_t)ctx->eng->fr_bytes();
+    memcpy(rec.g, g, rec.g_len);
+  }
+  return party_call(ctx, p, sid, rec, nullptr, stream);
+}
+int zk_party_d_fft(zk_ctx* ctx, zk_party* p, int sid, void* share_d, const void* in_mask_d, const void* out_mask_d, int rearrange,
+                   int log2_m, uint64_t seed, void* stream) {
+  return party_fft(ctx, p, sid, zk::PARTY_D_FFT, share_d, in_mask_d, out_mask_d, rearrange, log2_m, nullptr, seed, stream);
+}
+int zk_party_d_ifft(zk_ctx* ctx, zk_party* p, int sid, void* share_d, const void* in_mask_d, const void* out_mask_d, int rearrange,
+                    int log2_m, const void* g, uint64_t seed, void* stream) {
+  return party_fft(ctx, p, sid, zk::PARTY_D_IFFT, share_d, in_mask_d, out_mask_d, rearrange, log2_m, g, seed, stream);
+}
+int zk_party_deg_red(zk_ctx* ctx, zk_party* p, int sid, void* x_d, const void* in_mask_d, const void* out_mask_d, size_t len,
+                     uint64_t seed, void* stream) {
+  zk::PartyRec rec;
+  rec.op = zk::PARTY_DEG_RED, rec.len = len, rec.seed = seed;
+  party_ptrs(rec, {x_d, in_mask_d, out_mask_d});
+  return party_call(ctx, p, sid, rec, nullptr, stream);
+}
+int zk_party_d_pp(zk_ctx* ctx, zk_party* p, int sid, const void* num_d, const void* den_d, const void* in_mask_d,
+                  const void* out_mask_d, size_t len, uint64_t seed, void* out_d, void* stream) {
+  zk::PartyRec rec;
+  rec.op = zk::PARTY_D_PP, rec.len = len, rec.seed = seed;
+  party_ptrs(rec, {num_d, den_d, in_mask_d, out_mask_d, out_d});
+  return party_call(ctx, p, sid, rec, nullptr, stream);
+}
+int zk_party_d_msm(zk_ctx* ctx, zk_party* p, int sid, int group, const void* bases_d, const void* scalars_d, size_t len,
+                   const void* in_mask, const void* out_mask, void* out, void* stream) {
+  zk::PartyRec rec;
+  rec.op = zk::PARTY_D_MSM, rec.group = group, rec.len = len;
+  party_ptrs(rec, {bases_d, scalars_d, in_mask, out_mask, out});
+  return party_call(ctx, p, sid, rec, nullptr, stream);
+}
+static void party_mask_ptrs(zk::PartyRec& rec, int at, const zk_groth16_masks* m) {
+  for (int i = 0; i < 14; i++) {
+    const void* q = !m ? nullptr : i < 6 ? m->fft_in[i] : i < 12 ? m->fft_out[i - 6] : i == 12 ? m->degred_in : m->degred_out;
+    rec.ptr[at + i] = q;
+    if (!q) rec.null_bits |= 1ull << (at + i);
+  }
+}
+int zk_party_circom_h(zk_ctx* ctx, zk_party* p, const void* qap_a_d, const void* qap_b_d, const void* qap_c_d, int log2_m,
+                      const zk_groth16_masks* masks, uint64_t seed, void* h_d, void* stream) {
+  zk::PartyRec rec;
+  rec.op = zk::PARTY_CIRCOM_H, rec.log2_m = log2_m, rec.seed = seed;
+  party_ptrs(rec, {qap_a_d, qap_b_d, qap_c_d, h_d});
+  party_mask_ptrs(rec, 4, masks);
+  return party_call(ctx, p, 0, rec, nullptr, stream);
+}
+int zk_party_groth16_prove(zk_ctx* ctx, zk_party* p, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
+                           const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
+                           int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                           void* stream) {
+  if (!ctx || !p) return ZK_ERR_BAD_INPUT;
+  if (!crs || !r || !s) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->last.code = ZK_ERR_BAD_INPUT, p->last.msg = "null pointer", p->last.party = p->id;
+    return ZK_ERR_BAD_INPUT;
+  }
+  zk::PartyRec rec;
+  rec.op = zk::PARTY_PROVE, rec.log2_m = log2_m, rec.seed = seed;
+  rec.ext[0] = crs->len_a, rec.ext[1] = crs->len_w, rec.ext[2] = crs->len_u;
+  const size_t fr = ctx->eng->fr_bytes();
+  rec.g_len = (uint32_t)(2 * fr);
+  memcpy(rec.g, r, fr);
+  memcpy(rec.g + fr, s, fr);
+  party_ptrs(rec, {qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d});
+  party_mask_ptrs(rec, 5, masks);
+  const void* rest[18] = {crs->s_d, crs->h_d, crs->v_d, crs->w_d, crs->u_d};
+  for (int i = 0; i < 5; i++) rest[5 + i] = masks ? masks->msm_in[i] : nullptr, rest[10 + i] = masks ? masks->msm_out[i] : nullptr;
+  rest[15] = pi_a, rest[16] = pi_b, rest[17] = pi_c;
+  for (int i = 0; i < 18; i++) {
+    rec.ptr[19 + i] = rest[i];
+    if (!rest[i]) rec.null_bits |= 1ull << (19 + i);
+  }
+  return party_call(ctx, p, 0, rec, crs, stream);
 }
 
 // ---- profiling slots (bench.py roofline leg) ----

@@ -18,6 +18,7 @@
 #include "pss.hpp"
 #include "hostpool.hpp"
 #include "net.hpp"
+#include "party_rdv.hpp"
 
 namespace zk {
 
@@ -190,6 +191,8 @@ class TableRegistry {
   std::vector<std::shared_ptr<MsmTable>> v_;
 };
 
+struct PartyHub;      // the per-net state of the per-party entry points (below)
+
 // Abstract interface the C ABI dispatches to (one implementation per curve).
 class IEngine {
  public:
@@ -238,11 +241,16 @@ class IEngine {
   int l = 0, n = 0, t = 0, device = 0;
   Status last;
   std::mutex last_mu;               // host worker tasks report failures too
+  // The issuer of a per-party round (engine_party.inc.hpp) points this at a Status of its own for the duration of the rank
+  // call: up to three channels issue at once, and `last` is one string per context.  Failures raised on THIS thread are
+  // copied there as well, so that the k callers of a round report their own round's message.
+  static inline thread_local Status* fail_capture = nullptr;
   int fail(int code, const std::string& m, int party = -1) {
     std::lock_guard<std::mutex> lk(last_mu);
     last.code = code;
     last.msg = m;
     last.party = party;
+    if (fail_capture) *fail_capture = last;
     return code;
   }
   int hip_fail(hipError_t e, const char* where) {
@@ -480,6 +488,9 @@ class IEngine {
                             const void* a_share, const void* ax_share, const void* r, const void* s, int log_m,
                             const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
                             hipStream_t st) = 0;
+  // the issue callback of the per-party entry points (engine_party.inc.hpp): the k records of one round on slot `sid`, in
+  // ascending party order -> the ONE rank call of recs[0].op with the parties' rows, on the slot's own stream
+  virtual PartyResult party_issue(Net* net, PartyHub* hub, int sid, const PartyRec* recs) = 0;
 };
 
 IEngine* make_engine_bn254(int l, int device);
@@ -514,6 +525,28 @@ struct DevBuf {
     if (e == hipSuccess) bytes = b;
     return e;
   }
+};
+
+// ---- per-party entry points (zk_party_*): what a net keeps for them.  One rendezvous slot, one issue stream, one completion
+// event and one staging buffer per channel, so that channels 0..2 issue independently of each other.
+enum PartyOp { PARTY_D_FFT = 1, PARTY_D_IFFT, PARTY_DEG_RED, PARTY_D_PP, PARTY_D_MSM, PARTY_CIRCOM_H, PARTY_PROVE };
+// PartyRec::h[0] / h[1]: the caller's stream and the event it recorded there on arrival; PartyRec::caller: (prover) its CRS share
+struct PartyChan {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+  DevBuf stage;
+  ~PartyChan() {
+    if (stream) (void)hipStreamDestroy(stream);
+    if (done) (void)hipEventDestroy(done);
+  }
+};
+struct PartyHub {
+  int k = 0;
+  PartySlot slot[NET_NSID];
+  PartyChan chan[NET_NSID];
+  std::atomic<uint64_t> stats[4] = {{0}, {0}, {0}, {0}};     // rounds issued, of them zero-copy, of them staged, bytes staged
+  // rounds party i of this rank has been through on channel sid: the sequence number of its next call, whichever handle makes it
+  std::atomic<uint64_t> seq[NET_NSID][PARTY_MAXK] = {};
 };
 
 }  // namespace zk

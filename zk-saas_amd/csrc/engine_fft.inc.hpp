@@ -173,7 +173,7 @@
       const int tws = (TB >= 10 && rbits >= 4) ? 2 : 0;
       const int tws_eff = rbits >= 4 ? tws : 0;      // one value for the LDS size AND the kernel argument
       size_t lds = (size_t)(sizeof(Fr) / 16) * 16 * (TILE + ((((size_t)1 << rbits) / 2) >> tws_eff) + 1);
-      bool& attr_set = ntt_attr_set_[TB == NTT_TILE_BITS_SMALL ? 0 : 1];     // per engine, i.e. per device
+      std::atomic<bool>& attr_set = ntt_attr_set_[TB == NTT_TILE_BITS_SMALL ? 0 : 1];     // per engine, i.e. per device
       if (!attr_set) {
         ZK_HIP(hipFuncSetAttribute((const void*)ntt_pass_kernel<Fr, TB>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)((sizeof(Fr) / 16) * 16 * (TILE + TILE / 2 + 1))));
@@ -422,7 +422,7 @@
     Fr* tile_d = tile_n + ntiles;
     Fr* ctile = tile_d + ntiles;
     constexpr size_t lds = (size_t)(sizeof(Fr) / 16) * 16 * DppGeom<E>::LDS_SLOTS;
-    bool& attr_set = dpp_attr_set_[E == DPP_E_LONG ? 0 : 1];
+    std::atomic<bool>& attr_set = dpp_attr_set_[E == DPP_E_LONG ? 0 : 1];
     if (!attr_set) {
       ZK_HIP(hipFuncSetAttribute((const void*)dpp_tile_kernel<FrP, L, E>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));

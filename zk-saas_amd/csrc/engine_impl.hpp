@@ -17,6 +17,7 @@
 #include "hostpool.hpp"
 #include "points.hpp"
 #include "dpp.hpp"
+#include "rows.hpp"
 
 namespace zk {
 
@@ -388,6 +389,7 @@ class Engine : public IEngine {
 #include "engine_setup.inc.hpp"      // zk_groth16_setup_scalars: R1CS and trapdoor -> CRS scalars
 #include "engine_gao.inc.hpp"        // zk_pss_unpack_robust: the error-correcting unpack
 #include "engine_gao_points.inc.hpp" // zk_pss_unpack_points_robust, zk_pss_repair_points, zk_d_msm_checked
+#include "engine_party.inc.hpp"      // zk_party_*: the k local callers of a round -> one rank call
 
   int ensure_streams() {
     std::lock_guard<std::mutex> lk(mu_);
@@ -417,8 +419,8 @@ class Engine : public IEngine {
   int host_threads_ = 0;        // zk_ctx_set_option("host_threads"): workers of the host pool (0 = by the core count)
   hipStream_t streams_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool streams_ready_ = false;
-  bool ntt_attr_set_[2] = {false, false};
-  bool dpp_attr_set_[2] = {false, false};
+  std::atomic<bool> ntt_attr_set_[2] = {{false}, {false}};      // (atomic: the channels of a rank issue from several threads)
+  std::atomic<bool> dpp_attr_set_[2] = {{false}, {false}};
   std::map<std::string, void*> base_tables_;
   Fr* pmat_ = nullptr;
   std::vector<Fr> pmat_host_;

@@ -60,6 +60,16 @@ class StarNet:
         self.lib.zk_net_stats(self.h, st)
         return {"gathers": st[0], "scatters": st[1], "alltoalls": st[2], "bytes_sent": st[3]}
 
+    def party(self, party_id):
+        """zk_net_party: the handle of ONE of this rank's parties, for a caller thread of its own (class Party)."""
+        return Party(self, party_id)
+
+    def party_stats(self):
+        """zk_party_stats: dict(rounds, zero_copy, staged, bytes_staged) of the per-party calls on this net"""
+        st = (C.c_uint64 * 4)()
+        self.lib.zk_party_stats(self.h, st)
+        return {"rounds": st[0], "zero_copy": st[1], "staged": st[2], "bytes_staged": st[3]}
+
     def close(self):
         if self.h:
             self.lib.zk_net_destroy(self.h)
@@ -108,6 +118,83 @@ class StarNet:
 
 def _mask_ptrs(m):
     return (None, None) if m is None else (_ptr(m.in_mask), _ptr(m.out_mask))
+
+
+class Party:
+    """One party of a rank (zk_net_party): the reference's per-party call sites (mpc-net/src/multi.rs:301-328 runs one
+    task per party; dfft/mod.rs:99-111, dmsm/mod.rs:59-66, sha256.rs:316-360 take that party's own vectors) over the C ABI's
+    zk_party_* calls.  Every buffer is THIS party's row.  The calls block until the rank's other parties are inside the same
+    call, so each Party is driven by a thread of its own (plain threading.Thread: ctypes releases the GIL for the call)."""
+
+    def __init__(self, net, party_id):
+        self.net, self.pp, self.lib = net, net.pp, net.lib
+        self.h = C.c_void_p()
+        rc = self.lib.zk_net_party(net.h, int(party_id), C.byref(self.h))
+        if rc != 0:
+            raise ZkError(rc, self.lib.zk_net_last_error(net.h, None).decode(), int(party_id))
+        self.id = self.lib.zk_party_id(self.h)
+
+    def release(self):
+        if self.h:
+            self.lib.zk_party_release(self.h)
+            self.h = None
+
+    def _check(self, rc):
+        if rc != 0:
+            party = C.c_int(-1)
+            msg = self.lib.zk_party_last_error(self.h, C.byref(party)).decode()
+            raise ZkError(rc, msg, party.value)
+
+    def d_fft(self, sid, share, fft_mask, rearrange, log2_m, seed=0, stream=None):
+        im, om = _mask_ptrs(fft_mask)
+        self._check(self.lib.zk_party_d_fft(self.pp.h, self.h, sid, _ptr(share), im, om, int(rearrange), log2_m, seed, stream))
+        return share
+
+    def d_ifft(self, sid, share, fft_mask, rearrange, log2_m, g=None, seed=0, stream=None):
+        im, om = _mask_ptrs(fft_mask)
+        garr = None if g is None else self.pp.fr.encode_one(g)
+        self._check(self.lib.zk_party_d_ifft(self.pp.h, self.h, sid, _ptr(share), im, om, int(rearrange), log2_m,
+                                             None if garr is None else garr.ctypes.data, seed, stream))
+        return share
+
+    def deg_red(self, sid, x, mask, length, seed=0, stream=None):
+        im, om = _mask_ptrs(mask)
+        self._check(self.lib.zk_party_deg_red(self.pp.h, self.h, sid, _ptr(x), im, om, length, seed, stream))
+        return x
+
+    def d_pp(self, sid, num, den, mask, length, seed=0, out=None, stream=None):
+        out = out or self.pp.alloc_fr(length)
+        im, om = _mask_ptrs(mask)
+        self._check(self.lib.zk_party_d_pp(self.pp.h, self.h, sid, _ptr(num), _ptr(den), im, om, length, seed, _ptr(out), stream))
+        return out
+
+    def d_msm(self, sid, group, bases, scalars, length, in_mask=None, out_mask=None, stream=None):
+        """returns this party's output share [3 * coord limbs]; in_mask / out_mask: this party's Jacobian point or None"""
+        nl = self.pp.fq.nl * (2 if group == ZK_G2 else 1)
+        out = np.zeros(3 * nl, dtype=np.uint64)
+        im = None if in_mask is None else np.ascontiguousarray(in_mask, dtype=np.uint64)
+        om = None if out_mask is None else np.ascontiguousarray(out_mask, dtype=np.uint64)
+        self._check(self.lib.zk_party_d_msm(self.pp.h, self.h, sid, group, _ptr(bases), _ptr(scalars), length,
+                                            None if im is None else im.ctypes.data, None if om is None else om.ctypes.data,
+                                            out.ctypes.data, stream))
+        return out
+
+    def circom_h(self, qap, log2_m, masks=None, seed=0, out=None, stream=None):
+        out = out or self.pp.alloc_fr((1 << log2_m) // self.pp.l)
+        self._check(self.lib.zk_party_circom_h(self.pp.h, self.h, _ptr(qap[0]), _ptr(qap[1]), _ptr(qap[2]), log2_m,
+                                               None if masks is None else C.byref(masks), seed, out.ptr, stream))
+        return out
+
+    def prove(self, crs_ct, qap, a_share, ax_share, r, s, log2_m, masks=None, seed=0, stream=None):
+        """dsha256 for this party: crs_ct is a groth16.CrsShare over THIS party's rows.  Returns (pi_a [3nl], pi_b [6nl], pi_c [3nl])."""
+        nl = self.pp.fq.nl
+        pa, pb, pc = (np.zeros(w * nl, dtype=np.uint64) for w in (3, 6, 3))
+        rr, ss = self.pp.fr.encode_one(r), self.pp.fr.encode_one(s)
+        self._check(self.lib.zk_party_groth16_prove(self.pp.h, self.h, C.byref(crs_ct), _ptr(qap[0]), _ptr(qap[1]), _ptr(qap[2]),
+                                                    _ptr(a_share), _ptr(ax_share), rr.ctypes.data, ss.ctypes.data, log2_m,
+                                                    None if masks is None else C.byref(masks), seed, pa.ctypes.data,
+                                                    pb.ctypes.data, pc.ctypes.data, stream))
+        return pa, pb, pc
 
 
 def dist_d_fft(pp, net, sid, shares_local, fft_mask, rearrange, log2_m, seed=0, stream=None):
