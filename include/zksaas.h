@@ -548,6 +548,41 @@ int zk_pss_unpack_points_robust(zk_ctx* ctx, int group, const void* shares_d /* 
 int zk_pss_repair_points(zk_ctx* ctx, int group, void* shares_d /* [n][nchunks] affine, in place */, size_t nchunks,
                          int dimension, uint8_t* status_d /* [nchunks] */, uint32_t* errpos_d /* [nchunks], or NULL */,
                          uint64_t* summary_d /* [3 + n], or NULL */, void* stream);
+/* zk_pss_unpack_points_robust_parties: zk_pss_unpack_points_robust when only the listed parties' shares are at hand (a
+ * party that was named before, or one that never answered, is left out).  shares_d is the compact [nparties][nchunks], row i
+ * the shares of parties[i]; parties is a HOST list of ascending ids below n, NULL for 0 .. nparties - 1.  With S the listed
+ * parties, rho = n - nparties and Lambda(X) = prod over the absent a of (X - w_n^a), the word Lambda(w_n^p) Y_p on S, the
+ * identity elsewhere, has dimension `dimension + rho` on the full domain: the syndromes are
+ * S_j = sum_{p in S} Lambda(w_n^p) w_n^(-p j) Y_p, j = dimension + rho .. n - 1 -- nparties - dimension of them, all the identity
+ * exactly for a codeword -- and one wrong share E at a listed q gives S_(j+1) = w_n^(-q) S_j and
+ * E = Lambda(w_n^q)^(-1) w_n^(q (dimension + rho)) S_(dimension + rho).  The factors of Lambda sit in the scalars, no share
+ * is multiplied on its own.  CORRECTION CAPACITY: cap = 1 when nparties - dimension >= 2, cap = 0 when it is 1.
+ * status, errpos and summary_d mean what they mean in zk_pss_unpack_points_robust with nparties in place of n: errpos and
+ * the summary's per-party counts go by party ID, and an absent party is never named (a ratio that points at one is status 2).
+ * out_d is the l secrets through the Lagrange matrix of the listed points (pss.rs:170-221), which is exact for any word of
+ * dimension <= nparties; an absent party's share is not recovered.
+ * PROMISED EQUAL: with nparties == n every output and every byte written equals zk_pss_unpack_points_robust's; on a clean
+ * chunk out_d equals zk_pss_unpack2_points' with the same list wherever that call accepts the list, byte for byte (affine
+ * output is canonical).  The PRECONDITION on the shares is that call's.
+ * Errors, in this order: nparties outside 1 .. n, a list that is not strictly ascending or holds an id >= n, a dimension
+ * outside 1 .. n - 1, a bad group, NULL shares_d / status_d with nchunks > 0 -> ZK_ERR_BAD_INPUT; nparties <= dimension ->
+ * ZK_ERR_PROTOCOL, as zk_pss_unpack_robust_parties; then nchunks == 0 is ZK_OK.  The context stays usable after each.
+ * The scalars of a (list, dimension) are computed on the host per new pair and their device copy is cached; after that no
+ * host synchronisation.  Working memory from the stream's workspace.  Device engine only. */
+int zk_pss_unpack_points_robust_parties(zk_ctx* ctx, int group, const void* shares_d /* [nparties][nchunks] affine */,
+                                        const uint32_t* parties /* host, ascending, NULL = 0..nparties-1 */, int nparties,
+                                        size_t nchunks, int dimension, void* out_d /* [nchunks][l] affine, or NULL */,
+                                        uint8_t* status_d /* [nchunks] */, uint32_t* errpos_d /* [nchunks], or NULL */,
+                                        uint64_t* summary_d /* [3 + n], or NULL */, void* stream);
+/* zk_pss_repair_points_parties: the verdicts of zk_pss_unpack_points_robust_parties written back into the compact shares.
+ * status_d, errpos_d, summary_d and the error returns are exactly that call's on the same input.  WRITTEN: in a status-1 chunk
+ * the one element errpos names, at row i of parties[i], becomes Y_q - E in affine form.  NOT WRITTEN: anything else; an
+ * absent party's share is not recovered.  A second call finds the former status-1 chunks clean.  With nparties == n every
+ * byte written equals zk_pss_repair_points'. */
+int zk_pss_repair_points_parties(zk_ctx* ctx, int group, void* shares_d /* [nparties][nchunks] affine, in place */,
+                                 const uint32_t* parties, int nparties, size_t nchunks, int dimension,
+                                 uint8_t* status_d /* [nchunks] */, uint32_t* errpos_d /* [nchunks], or NULL */,
+                                 uint64_t* summary_d /* [3 + n], or NULL */, void* stream);
 /* zk_d_msm_checked: zk_d_msm with the king's word checked.  The word is c_p = msm_p + in_mask_p
  * (dist-primitives/src/dmsm/mod.rs:73-85), of degree up to 4l - 2: dimension 4l - 1, one syndrome, sum_p w_n^p c_p --
  * DETECTION ONLY, as zk_deg_red_checked.  *status (HOST, one byte) is 0 when the syndrome is the identity and 2 otherwise;
@@ -1089,6 +1124,33 @@ int zk_groth16_verify_all(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affin
  * BLS12-381 G1 phi(P) = -[x^2]P.  Fixed chains of 63 / 64 doublings: no loop bound depends on the point.
  * Returns when ok_d is written. */
 int zk_points_subgroup_check(zk_ctx* ctx, int group, const void* affine_d, size_t len, uint8_t* ok_d, void* stream);
+/* zk_groth16_reconstruct_robust: a batch of proofs from proof shares that are NOT trusted.  zk_groth16_reconstruct trusts
+ * every share: one wrong share gives a proof that fails verification, and nobody is named.  Here r and s are in the clear
+ * (oracle/groth16.py dist_prove), so a party's shares of A, B and C are fixed linear combinations of d_msm outputs and clear
+ * points: each of the three is a word of DIMENSION 2l, not 4l - 1.  With nparties listed that leaves nparties - 2l
+ * syndromes: one wrong share per element is located and corrected when nparties >= 2l + 2 (up to 2l - 2 parties may be
+ * absent at the same time); nparties == 2l + 1 detects only.
+ * pi_a / pi_c: [nproofs][nparties] Jacobian G1, pi_b: [nproofs][nparties] Jacobian G2, HOST, column i the share of parties[i]
+ * (ascending ids, NULL = 0 .. nparties - 1) -- with all parties, what zk_groth16_prove_batch / zk_groth16_batch_wait write.
+ * The shares are copied up once; per element one staging kernel writes the compact affine [nparties][nproofs] (Z == 0 is the
+ * identity), every staged share is tested with the predicate of zk_points_subgroup_check (on the curve and [r]P = O), and
+ * A SHARE THAT FAILS THE PREDICATE IS REPLACED BY THE IDENTITY BEFORE DECODING: from there on it is an ordinary wrong share,
+ * located, corrected and named in errpos like any other.  Then zk_pss_unpack_points_robust_parties runs at dimension 2l, once
+ * for A (G1), B (G2) and C (G1), chunk = proof; secret 0 of a chunk is the element.
+ *   status (host, [nproofs][3])            0, 1 or 2 for A, B, C of proof i, as that call's
+ *   errpos (host, [nproofs][3], or NULL)   bit p: party p's share of that element was corrected
+ *   proofs_affine (host, or NULL)          [nproofs] A | B | C as zk_groth16_reconstruct writes them; a failed element is (0, 0)
+ *   proofs_bytes (host, or NULL)           [nproofs][4 |Fq|] as zk_groth16_reconstruct's, through the same device codec; the
+ *                                          bytes of a proof with ANY failed element are all zero
+ * A failed element is not an error return.  Errors: the list refusals of zk_pss_unpack_points_robust_parties, then NULL status
+ * -> ZK_ERR_BAD_INPUT, then nparties <= 2l -> ZK_ERR_PROTOCOL; nproofs == 0 is then ZK_OK and nothing is written, whatever the
+ * other pointers are; NULL pi_a / pi_b / pi_c with nproofs > 0, or more than 2^32 / n proofs -> ZK_ERR_BAD_INPUT.  A context
+ * without G2 or without subgroup parameters (BLS12-377) -> ZK_ERR_BAD_INPUT.  Synchronous, like zk_groth16_reconstruct; the
+ * working memory is the context's own (one call at a time per context).  Device engine only. */
+int zk_groth16_reconstruct_robust(zk_ctx* ctx, size_t nproofs, const void* pi_a, const void* pi_b, const void* pi_c,
+                                  const uint32_t* parties, int nparties, void* proofs_affine /* host, or NULL */,
+                                  void* proofs_bytes /* host, or NULL */, uint8_t* status /* host [nproofs][3] */,
+                                  uint32_t* errpos /* host [nproofs][3], or NULL */, void* stream);
 /* CanonicalDeserialize::deserialize_compressed with validation (Validate::Yes), per element: decodes exactly as
  * zk_points_decompress does (both encodings, the same flag rules) and tests the subgroup.  A bad element does not fail
  * the call: ok_d[i] = 0 and (0, 0) is written for an encoding that does not decode; ok_d[i] = 0 and the decoded point is

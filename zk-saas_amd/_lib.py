@@ -41,6 +41,7 @@ SYMBOLS = [
     "zk_pss_repair_batch_parties", "zk_circom_h_checked_parties", "zk_groth16_prove_checked_parties",
     "zk_pss_repair_range", "zk_dist_d_fft_checked", "zk_dist_d_ifft_checked", "zk_dist_deg_red_checked",
     "zk_dist_circom_h_checked",
+    "zk_pss_unpack_points_robust_parties", "zk_pss_repair_points_parties", "zk_groth16_reconstruct_robust",
     "zk_net_party", "zk_party_release", "zk_party_id", "zk_party_last_error", "zk_party_stats", "zk_party_d_fft",
     "zk_party_d_ifft", "zk_party_deg_red", "zk_party_d_pp", "zk_party_d_msm", "zk_party_circom_h", "zk_party_groth16_prove",
 ]
@@ -244,6 +245,9 @@ def load():
     lib.zk_d_pp_checked.argtypes = [vp, vp, vp, ids, i32, vp, vp, sz, u64, vp, vp, vp, vp, vp]
     lib.zk_pss_unpack_points_robust.argtypes = [vp, i32, vp, sz, i32, vp, vp, vp, vp, vp]
     lib.zk_pss_repair_points.argtypes = [vp, i32, vp, sz, i32, vp, vp, vp, vp]
+    lib.zk_pss_unpack_points_robust_parties.argtypes = [vp, i32, vp, C.POINTER(C.c_uint32), i32, sz, i32, vp, vp, vp, vp, vp]
+    lib.zk_pss_repair_points_parties.argtypes = [vp, i32, vp, C.POINTER(C.c_uint32), i32, sz, i32, vp, vp, vp, vp]
+    lib.zk_groth16_reconstruct_robust.argtypes = [vp, sz, vp, vp, vp, C.POINTER(C.c_uint32), i32, vp, vp, vp, vp, vp]
     lib.zk_d_msm_checked.argtypes = [vp, i32, vp, vp, sz, vp, vp, vp, vp, vp]
     lib.zk_pss_repair_batch.argtypes = [vp, vp, sz, i32, sz, i32, vp, vp, vp, vp]
     lib.zk_circom_h_checked.argtypes = [vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp]

@@ -247,29 +247,45 @@ class PackedSharingParams(Context):
                                                              stream))
         return r
 
-    def unpack_points_robust(self, group, shares_d, nchunks, dimension=None, want_out=True, stream=None):
+    def unpack_points_robust(self, group, shares_d, nchunks, dimension=None, want_out=True, stream=None, parties=None):
         """zk_pss_unpack_points_robust: the robust unpack of all n parties' packed POINT shares [n][nchunks] affine (pss.rs:125-166
         over group elements).  One wrong share per chunk is located and corrected when n - dimension >= 2; at dimension
         4l - 1 the call only detects.  dimension: 2l (the default) up to 4l - 1.  Returns a RobustUnpack with status, errpos
         and summary; `out` is [nchunks][l] affine (None with want_out=False): the unpack of the clean or corrected word,
-        identities for a failed chunk."""
+        identities for a failed chunk.
+        With `parties` (ascending ids) shares_d is the compact [len(parties)][nchunks], the other parties are absent and the call
+        is zk_pss_unpack_points_robust_parties: one wrong share is corrected when len(parties) - dimension >= 2, errpos and the
+        summary go by party id."""
         k = 2 * self.l if dimension is None else int(dimension)
-        r = self._report(nchunks, k)
+        r = self._report(nchunks, k, parties)
         width = self.fq.nl * (4 if group == ZK_G2 else 2) * 8
         r.out = DeviceBuffer(self, max(1, nchunks * self.l) * width) if want_out else None
-        self._check(self.lib.zk_pss_unpack_points_robust(self.h, group, _ptr(shares_d), nchunks, k, _ptr(r.out), _ptr(r.status),
-                                                         _ptr(r.errpos), _ptr(r.summary_d), stream))
+        if parties is None:
+            self._check(self.lib.zk_pss_unpack_points_robust(self.h, group, _ptr(shares_d), nchunks, k, _ptr(r.out),
+                                                             _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
+        else:
+            arr = (C.c_uint32 * len(r.parties))(*r.parties)
+            self._check(self.lib.zk_pss_unpack_points_robust_parties(self.h, group, _ptr(shares_d), arr, len(r.parties), nchunks,
+                                                                     k, _ptr(r.out), _ptr(r.status), _ptr(r.errpos),
+                                                                     _ptr(r.summary_d), stream))
         return r
 
-    def repair_points(self, group, shares_d, nchunks, dimension=None, stream=None):
+    def repair_points(self, group, shares_d, nchunks, dimension=None, stream=None, parties=None):
         """zk_pss_repair_points: unpack_points_robust's verdicts written back into shares_d [n][nchunks] affine, in place: in a
         corrected chunk the one share errpos names becomes the honest one, every other element keeps its bytes.  Returns a
-        RobustUnpack with status, errpos and summary; `out` is shares_d."""
+        RobustUnpack with status, errpos and summary; `out` is shares_d.
+        With `parties` (ascending ids) shares_d is the compact [len(parties)][nchunks] and the call is
+        zk_pss_repair_points_parties: a named party's share is written at its row, an absent party's is not recovered."""
         k = 2 * self.l if dimension is None else int(dimension)
-        r = self._report(nchunks, k)
+        r = self._report(nchunks, k, parties)
         r.out = shares_d
-        self._check(self.lib.zk_pss_repair_points(self.h, group, _ptr(shares_d), nchunks, k, _ptr(r.status), _ptr(r.errpos),
-                                                  _ptr(r.summary_d), stream))
+        if parties is None:
+            self._check(self.lib.zk_pss_repair_points(self.h, group, _ptr(shares_d), nchunks, k, _ptr(r.status), _ptr(r.errpos),
+                                                      _ptr(r.summary_d), stream))
+        else:
+            arr = (C.c_uint32 * len(r.parties))(*r.parties)
+            self._check(self.lib.zk_pss_repair_points_parties(self.h, group, _ptr(shares_d), arr, len(r.parties), nchunks, k,
+                                                              _ptr(r.status), _ptr(r.errpos), _ptr(r.summary_d), stream))
         return r
 
     def d_msm_checked(self, group, bases_d, scalars_d, length, msm_mask=None, stream=None):

@@ -1094,6 +1094,19 @@ int zk_pss_repair_points(zk_ctx* ctx, int group, void* shares_d, size_t nchunks,
   CTX_OR_FAIL();
   return e->pss_repair_points(group, shares_d, nchunks, dimension, status_d, errpos_d, summary_d, S(stream));
 }
+int zk_pss_unpack_points_robust_parties(zk_ctx* ctx, int group, const void* shares_d, const uint32_t* parties, int nparties,
+                                        size_t nchunks, int dimension, void* out_d, uint8_t* status_d, uint32_t* errpos_d,
+                                        uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_unpack_points_robust_parties(group, shares_d, parties, nparties, nchunks, dimension, out_d, status_d, errpos_d,
+                                             summary_d, S(stream));
+}
+int zk_pss_repair_points_parties(zk_ctx* ctx, int group, void* shares_d, const uint32_t* parties, int nparties, size_t nchunks,
+                                 int dimension, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->pss_repair_points_parties(group, shares_d, parties, nparties, nchunks, dimension, status_d, errpos_d, summary_d,
+                                      S(stream));
+}
 int zk_d_msm_checked(zk_ctx* ctx, int group, const void* bases_d, const void* scalars_d, size_t len, const void* in_mask,
                      const void* out_mask, void* out, uint8_t* status, void* stream) {
   CTX_OR_FAIL();
@@ -1239,6 +1252,17 @@ int zk_groth16_verify_all(zk_ctx* ctx, const zk_vk* vk, const void* proofs_affin
                           size_t n_inputs, size_t count, const uint8_t* seed, int* all_ok, void* gt_out, void* stream) {
   PAIRING_OR_FAIL();
   return pr->verify_all(e, vk, proofs_affine, public_inputs, n_inputs, count, seed, all_ok, gt_out, S(stream));
+}
+int zk_groth16_reconstruct_robust(zk_ctx* ctx, size_t nproofs, const void* pi_a, const void* pi_b, const void* pi_c,
+                                  const uint32_t* parties, int nparties, void* proofs_affine, void* proofs_bytes,
+                                  uint8_t* status, uint32_t* errpos, void* stream) {
+  PAIRING_OR_FAIL();
+  return e->groth16_reconstruct_robust(
+      nproofs, pi_a, pi_b, pi_c, parties, nparties, proofs_affine, proofs_bytes, status, errpos,
+      [&](int group, const void* affine_d, size_t len, uint8_t* ok_d) {
+        return pr->points_subgroup_check(e, group, affine_d, len, ok_d, S(stream));
+      },
+      S(stream));
 }
 int zk_points_subgroup_check(zk_ctx* ctx, int group, const void* affine_d, size_t len, uint8_t* ok_d, void* stream) {
   PAIRING_OR_FAIL();

@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -453,6 +454,18 @@ class IEngine {
                                        uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
   virtual int pss_repair_points(int group, void* shares, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos,
                                 uint64_t* summary, hipStream_t st) = 0;
+  // the same for the compact shares [np][nchunks] of a party list (ascending ids, null: 0 .. np - 1)
+  virtual int pss_unpack_points_robust_parties(int group, const void* shares, const uint32_t* parties, int np, size_t nchunks,
+                                               int dimension, void* out, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                                               hipStream_t st) = 0;
+  virtual int pss_repair_points_parties(int group, void* shares, const uint32_t* parties, int np, size_t nchunks, int dimension,
+                                        uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  // zk_groth16_reconstruct_robust (engine_gao_points.inc.hpp); subgroup: the predicate of zk_points_subgroup_check on
+  // (group, affine_d, len) -> ok_d, which lives with the verifier's translation units and returns when ok_d is written
+  using SubgroupCheckFn = std::function<int(int group, const void* affine_d, size_t len, uint8_t* ok_d)>;
+  virtual int groth16_reconstruct_robust(size_t nproofs, const void* pi_a, const void* pi_b, const void* pi_c,
+                                         const uint32_t* parties, int np, void* proofs_affine, void* proofs_bytes,
+                                         uint8_t* status, uint32_t* errpos, const SubgroupCheckFn& subgroup, hipStream_t st) = 0;
   // d_msm with the king's word checked: status (host, one byte) is 0 or 2
   virtual int d_msm_checked(int group, const void* bases, const void* scalars, size_t len, const void* in_mask,
                             const void* out_mask, void* out, uint8_t* status, hipStream_t st) = 0;

@@ -84,6 +84,7 @@ class Engine : public IEngine {
     for (auto& kv : ucanon_) (void)hipFree(kv.second);
     if (pmc_) (void)hipFree(pmc_);
     if (gao_pt_tab_) (void)hipFree(gao_pt_tab_);
+    for (auto& kv : gao_pt_lists_) (void)hipFree(kv.second.first);
   }
 
   size_t fr_bytes() const override { return sizeof(Fr); }

@@ -19,6 +19,8 @@
 //   gao_points_chunk   n lanes, one dirty chunk (stage 2), written against the lane group of gao.hpp.  A lane takes one
 //                      candidate q, then one consistency check or one of the products the output needs; the group agrees by
 //                      ballot.  No point crosses lanes.
+// With a party list (zk_pss_unpack_points_robust_parties, zk_pss_repair_points_parties) both parts run on the word deflated by
+// the absent parties' locator, whose factors sit in a table of scalars per (list, dimension): GaoPtList, further down.
 // Stage 2 reads the syndromes stage 1 computed, as affine points: an inversion per syndrome of a dirty chunk only (the
 // identity needs none), and the decoder's products are then mixed additions on a base of two coordinates -- an XYZZ base over
 // Fq2 of BLS12-381 would be 96 registers on its own.
@@ -26,6 +28,8 @@
 // a fixed trip count, so shares outside the precondition (on the curve, in the order-r subgroup) end in a verdict that means
 // nothing, and never in a lane that spins.
 #pragma once
+#include <vector>
+
 #include "ec.hpp"
 #include "gao.hpp"
 
@@ -155,23 +159,26 @@ struct GaoPtResult {
 };
 
 // One chunk, all n lanes of the group together; a group that is not `live` takes every step with the others.
-//   syn(i)       S_(k+i) of this group's chunk, affine, i < n - k
+//   syn(i)       S_(k+i) of this group's chunk, affine, i < nsyn = n - k
 //   nfix         how many lanes produce an output (0: the verdict only)
 //   RE           zk_pss_repair_points: nfix <= 1, lane 0's output is Y_q - E, base(q, 0) = the share of party q
 //   otherwise    lane i's output is secret i of the corrected word, (secret i of the received word) - U[i][q] E:
 //                base(q, i) = what stage 1 wrote for secret i, ucoef(i, q) = U[i][q], canonical
 // The lanes' work is a list of products of a syndrome by a scalar: first the nfix multiples of S_k the outputs need, then
 // the checks w^(-q) S_(k+c) == S_(k+c+1), c = 1 .. n - k - 2; the list is walked n tasks at a time.
-template <class FrP, class Fld, class G, bool RE, class Syn, class Base, class UCoef>
-ZK_HD GaoPtResult<Fld, G> gao_points_chunk(const G& g, const GaoPtTable<Fp<FrP>>* tab, int n, int k, int nfix, bool live, Syn syn,
-                                           Base base, UCoef ucoef) {
+// k is the dimension the decoder runs at on the full domain and enters through nsyn = n - k only; the all-party form and the
+// party-list form below differ in who may be a candidate and in the error's scalar:
+//   listed(p)    party p may be named (all n parties: always)
+//   escal(q)     E = escal(q) S_k, Montgomery (all n parties: w^(q k))
+template <class FrP, class Fld, class G, bool RE, class Syn, class Base, class UCoef, class Listed, class ErrScal>
+ZK_HD GaoPtResult<Fld, G> gao_points_chunk_on(const G& g, const GaoPtTable<Fp<FrP>>* tab, int n, int nsyn, int nfix, bool live,
+                                              Syn syn, Base base, UCoef ucoef, Listed listed, ErrScal escal) {
   using Fr = Fp<FrP>;
   using A = Affine<Fld>;
   using P = XYZZ<Fld>;
   using VP = typename G::template V<P>;
   using VA = typename G::template V<A>;
   const A ident{Fld::zero(), Fld::zero()};
-  const int nsyn = n - k;
   bool ok = live && nsyn >= 2;
   int q = 0;
   VA val = g.template make<A>([&](int) { return ident; });
@@ -179,12 +186,12 @@ ZK_HD GaoPtResult<Fld, G> gao_points_chunk(const G& g, const GaoPtTable<Fp<FrP>>
     // ---- locate: lane p asks whether w^(-p) S_k == S_(k+1)
     const A s0 = syn(0), s1 = syn(1);
     const VP cand = g.template make<P>([&](int p) GAO_PT_INLINE { return gao_pt_mul<FrP, Fld>(s0, tab->winv[p]); });
-    const uint32_t m = g.ballot([&](int p) { return gao_pt_eq(g.at(cand, p), s1); });
+    const uint32_t m = g.ballot([&](int p) { return listed(p) && gao_pt_eq(g.at(cand, p), s1); });
     if (s0.is_identity() || gao_popcount(m) != 1) ok = false;
     q = ok ? gao_top_bit(m) : 0;
     // ---- the outputs' products and the consistency checks
     const int ntask = nfix + nsyn - 2;
-    const Fr es = tab->wn[(q * k) & (n - 1)];          // w^(q k)
+    const Fr es = escal(q);
     for (int t0 = 0; t0 < ntask; t0 += n) {
       const VP pr = g.template make<P>([&](int p) GAO_PT_INLINE {
         const int t = t0 + p;
@@ -215,6 +222,100 @@ ZK_HD GaoPtResult<Fld, G> gao_points_chunk(const G& g, const GaoPtTable<Fp<FrP>>
   out.val = g.template make<A>([&](int p) { return gao_pt_keep(g.at(val, p), ok); });
   return out;
 }
+// the error's scalar with all n parties: w^(q k)
+template <class F>
+ZK_HD F gao_points_err_scalar(const GaoPtTable<F>* tab, int n, int k, int q) {
+  return tab->wn[(q * k) & (n - 1)];
+}
+template <class FrP, class Fld, class G, bool RE, class Syn, class Base, class UCoef>
+ZK_HD GaoPtResult<Fld, G> gao_points_chunk(const G& g, const GaoPtTable<Fp<FrP>>* tab, int n, int k, int nfix, bool live, Syn syn,
+                                           Base base, UCoef ucoef) {
+  return gao_points_chunk_on<FrP, Fld, G, RE>(
+      g, tab, n, n - k, nfix, live, syn, base, ucoef, [](int) { return true; },
+      [&](int q) { return gao_points_err_scalar(tab, n, k, q); });
+}
+
+// ---------------------------------------------------------------- a party list (zk_pss_*_points_*_parties)
+// With the parties of a set S listed (np of them, compact rows in ascending id), rho = n - np absent and
+// Lambda(X) = prod_{a not in S} (X - w_n^a), the deflated word Y'_p = Lambda(w_n^p) Y_p for p in S, the identity otherwise, is a
+// word of dimension k' = k + rho on the full domain: gao_make_absent's device, carried into the exponent.  A lane never
+// multiplies a point by Lambda on its own -- the factor sits in the scalars it reads:
+//   syndromes  S_j = sum_{p in S} Lambda(w_n^p) w_n^(-p j) Y_p, j = k' .. n - 1: np - k rows over the compact shares
+//   one error  E at a listed q: S_(j+1) = w_n^(-q) S_j as before, E = Lambda(w_n^q)^(-1) w_n^(q k') S_k'
+// Only listed parties are candidates; a ratio that points at an absent party is status 2, as in gao.hpp.  cap = 1 when
+// np - k >= 2, else 0.  The secrets go through the l x np Lagrange matrix of the listed points at g w_2l^i, valid for any word
+// of dimension <= np.  Everything here depends on (list, k) only and is computed on the host.
+template <class F>
+struct GaoPtList {         // a view: device pointers in a kernel, host pointers in the host test
+  const uint32_t* row;     // [n] party p's row of the compact shares; 0 for an absent one, which is never named
+  const F* fix;            // [n] Lambda(w_n^q)^(-1) w_n^(q k'), Montgomery; zero for an absent q
+  const F* syn;            // [np - k][np] Lambda(w_n^p) w_n^(-p (k' + i)) at p's row, CANONICAL
+  const F* umat;           // [l][np] the Lagrange matrix, CANONICAL
+  int np, kp;              // listed parties; k' = k + rho
+  uint32_t listed;         // bit p: party p is listed
+};
+constexpr size_t GAO_PT_LIST_HEAD = GAO_MAX_N * sizeof(uint32_t);      // `row`, ahead of the scalars in one allocation
+template <class F>
+struct GaoPtListHost {
+  uint32_t row[GAO_MAX_N];
+  std::vector<F> sc;       // fix [n] | syn [np - k][np] | umat [l][np]
+  int n, l, np, kp;
+  uint32_t listed;
+  size_t bytes() const { return GAO_PT_LIST_HEAD + sc.size() * sizeof(F); }
+  // the view of a copy that starts at `base`: row, then sc
+  GaoPtList<F> view(const void* base) const {
+    const F* s = (const F*)((const char*)base + GAO_PT_LIST_HEAD);
+    return {(const uint32_t*)base, s, s + n, s + n + (size_t)(n - kp) * np, np, kp, listed};
+  }
+  GaoPtList<F> view() const { return {row, sc.data(), sc.data() + n, sc.data() + n + (size_t)(n - kp) * np, np, kp, listed}; }
+};
+// parties: np ascending ids below n = 4l (null: 0 .. np - 1), np > k
+template <class P>
+inline GaoPtListHost<Fp<P>> gao_points_make_list(int l, const uint32_t* parties, int np, int k) {
+  using F = Fp<P>;
+  const int n = 4 * l, rho = n - np, kp = k + rho, nsyn = np - k;
+  const GaoConsts<F> c = gao_make_consts<P>(l);
+  GaoPtListHost<F> t;
+  t.n = n, t.l = l, t.np = np, t.kp = kp, t.listed = 0;
+  uint32_t ids[GAO_MAX_N];
+  for (int i = 0; i < GAO_MAX_N; i++) t.row[i] = 0;
+  for (int i = 0; i < np; i++) ids[i] = parties ? parties[i] : (uint32_t)i, t.row[ids[i]] = (uint32_t)i, t.listed |= 1u << ids[i];
+  F x[GAO_MAX_N], lam[GAO_MAX_N];
+  for (int p = 0; p < n; p++) x[p] = gao_lane_pow<F, 5>(c.wpow2, p);
+  for (int p = 0; p < n; p++) {
+    lam[p] = F::one();
+    for (int a = 0; a < n; a++)
+      if (!((t.listed >> a) & 1)) lam[p] = lam[p] * (x[p] - x[a]);
+  }
+  t.sc.assign((size_t)n + (size_t)nsyn * np + (size_t)l * np, F::zero());
+  F* fix = t.sc.data();
+  F* syn = fix + n;
+  F* um = syn + (size_t)nsyn * np;
+  for (int i = 0; i < np; i++) {
+    const int q = (int)ids[i];
+    fix[q] = lam[q].inverse() * x[(q * kp) & (n - 1)];
+    for (int r = 0; r < nsyn; r++) syn[(size_t)r * np + i] = (lam[q] * x[(n - ((q * (kp + r)) & (n - 1))) & (n - 1)]).from_mont();
+    for (int s = 0; s < l; s++) {
+      F num = F::one(), den = F::one();
+      for (int j = 0; j < np; j++)
+        if (j != i) num = num * (c.sec[s] - x[ids[j]]), den = den * (x[q] - x[ids[j]]);
+      um[(size_t)s * np + i] = (num * den.inverse()).from_mont();
+    }
+  }
+  return t;
+}
+// gao_points_chunk for a party list; base and ucoef take the party id q and look its row up in lt.row
+template <class F>
+ZK_HD bool gao_points_listed(const GaoPtList<F>& lt, int p) {
+  return ((lt.listed >> p) & 1u) != 0;
+}
+template <class FrP, class Fld, class G, bool RE, class Syn, class Base, class UCoef>
+ZK_HD GaoPtResult<Fld, G> gao_points_chunk_parties(const G& g, const GaoPtTable<Fp<FrP>>* tab, const GaoPtList<Fp<FrP>>& lt, int n,
+                                                   int nfix, bool live, Syn syn, Base base, UCoef ucoef) {
+  return gao_points_chunk_on<FrP, Fld, G, RE>(
+      g, tab, n, n - lt.kp, nfix, live, syn, base, ucoef, [&](int p) { return gao_points_listed(lt, p); },
+      [&](int q) { return lt.fix[q]; });
+}
 
 #undef GAO_PT_INLINE
 
@@ -223,11 +324,12 @@ class IEngine;
 struct DevBuf;
 // zk_pss_unpack_points_robust (REPAIR = false; umat: the l x n unpack matrix, canonical, device; out may be null) and
 // zk_pss_repair_points (REPAIR = true; shares written, umat and out null) over the coordinate field Fld; tab: the device
-// copy of gao_points_make_table(l); wk: working memory
+// copy of gao_points_make_table(l); wk: working memory.  list (null: all n parties): a view of device memory for the
+// _parties forms -- shares are its np rows, the matrix is its own and umat is not read
 template <class FrP, class Fld, bool REPAIR>
 int gao_points_run(IEngine* e, DevBuf& wk, int l, std::conditional_t<REPAIR, void*, const void*> shares, size_t nchunks,
-                   int dimension, const GaoPtTable<Fp<FrP>>* tab, const Fp<FrP>* umat, void* out, uint8_t* status,
-                   uint32_t* errpos, uint64_t* summary, hipStream_t st);
+                   int dimension, const GaoPtTable<Fp<FrP>>* tab, const Fp<FrP>* umat, const GaoPtList<Fp<FrP>>* list, void* out,
+                   uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
 #endif
 
 }  // namespace zk

@@ -1,4 +1,4 @@
-// zk_pss_unpack_points_robust and zk_pss_repair_points over G1 of this curve (gao_points_impl.hpp).
+// zk_pss_unpack_points_robust, zk_pss_repair_points and their _parties forms over G1 of this curve (gao_points_impl.hpp).
 // a 12-limb base field: inline products, so that the G1 kernels keep out of scratch memory (field.hpp ZK_MUL_INLINE_LIMBS)
 #define ZK_MUL_INLINE_LIMBS 12
 #include "curves.hpp"
@@ -7,8 +7,8 @@
 namespace zk {
 #define GAO_PT_INST(FR, FLD, RE)                                                                                          \
   template int gao_points_run<FR, FLD, RE>(IEngine*, DevBuf&, int, std::conditional_t<RE, void*, const void*>, size_t, int, \
-                                           const GaoPtTable<Fp<FR>>*, const Fp<FR>*, void*, uint8_t*, uint32_t*, uint64_t*, \
-                                           hipStream_t);
+                                           const GaoPtTable<Fp<FR>>*, const Fp<FR>*, const GaoPtList<Fp<FR>>*, void*, uint8_t*,  \
+                                           uint32_t*, uint64_t*, hipStream_t);
 GAO_PT_INST(Bls377Fr, Fp<Bls377Fq>, false)
 GAO_PT_INST(Bls377Fr, Fp<Bls377Fq>, true)
 #undef GAO_PT_INST

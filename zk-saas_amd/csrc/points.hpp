@@ -329,5 +329,24 @@ __global__ __launch_bounds__(128) void points_compress_kernel(const Affine<Fld>*
   else if (larger) p[C::SIZE - 1] |= 0x80;
 }
 
+// The staging of zk_groth16_reconstruct_robust: the parties' Jacobian outputs [count][np] become the compact affine shares
+// [np][count] the robust unpack reads (Z == 0: the identity); one lane per point, one inversion each.
+template <class Fld>
+__global__ __launch_bounds__(128) void points_stage_shares_kernel(const Jacobian<Fld>* __restrict__ in, size_t count, int np,
+                                                                 Affine<Fld>* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count * (size_t)np) return;
+  const size_t i = t / (size_t)np, p = t % (size_t)np;
+  store_elem(out + p * count + i, xyzz_to_affine(jacobian_to_xyzz(load_elem(in + t))));
+}
+// pts[i] becomes the identity where ok[i] == 0
+template <class Fld>
+__global__ __launch_bounds__(128) void points_drop_failed_kernel(Affine<Fld>* __restrict__ pts, const uint8_t* __restrict__ ok,
+                                                                size_t len) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= len || ok[i]) return;
+  store_elem(pts + i, Affine<Fld>{Fld::zero(), Fld::zero()});
+}
+
 #endif  // __HIPCC__
 }  // namespace zk

@@ -637,6 +637,29 @@ def reconstruct(pp, proof, parties=None, want_bytes=True, stream=None):
     return aff, (raw.tobytes() if want_bytes else None)
 
 
+def reconstruct_robust(pp, proofs, parties=None, want_bytes=True, stream=None):
+    """zk_groth16_reconstruct_robust: a batch of proofs from shares that are not trusted.  proofs = (pi_a, pi_b, pi_c), each
+    [nproofs][nparties][...] Jacobian rows of the listed parties (all n when parties is None) -- what prove_batch returns.
+    Every share is tested for the subgroup (a share that fails counts as a wrong share), then each element is decoded at
+    dimension 2l: one wrong share per element is corrected and named when nparties >= 2l + 2.  Returns
+    (affine [nproofs][8 * |Fq| limbs], bytes: a list of nproofs byte strings or None, status uint8 [nproofs][3],
+    errpos uint32 [nproofs][3]); a failed element (status 2) is (0, 0) and the bytes of its proof are zero."""
+    nl = pp.fq.nl
+    pa, pb, pc = (np.ascontiguousarray(x, dtype=np.uint64) for x in proofs)
+    count = pp.n if parties is None else len(parties)
+    nproofs = pa.size // (count * 3 * nl)
+    assert pa.size == nproofs * count * 3 * nl and pb.size == nproofs * count * 6 * nl and pc.size == pa.size
+    aff = np.zeros((nproofs, 8 * nl), dtype=np.uint64)
+    raw = np.zeros((nproofs, 4 * pp.fq.nbytes), dtype=np.uint8)
+    status = np.zeros((nproofs, 3), dtype=np.uint8)
+    errpos = np.zeros((nproofs, 3), dtype=np.uint32)
+    ids = None if parties is None else (C.c_uint32 * count)(*parties)
+    pp._check(pp.lib.zk_groth16_reconstruct_robust(pp.h, nproofs, pa.ctypes.data, pb.ctypes.data, pc.ctypes.data, ids, count,
+                                                   aff.ctypes.data, raw.ctypes.data if want_bytes else None,
+                                                   status.ctypes.data, errpos.ctypes.data, stream))
+    return aff, ([r.tobytes() for r in raw] if want_bytes else None), status, errpos
+
+
 class ProofInFlight:
     """A proof started with prove_async (zk_groth16_prove_async); wait() joins it and returns the shares."""
 
