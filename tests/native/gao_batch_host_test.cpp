@@ -2,7 +2,7 @@
 // refusal predicate and the layout of the working memory.  Reads lines from stdin and answers each on stdout:
 //   e <nitems> <nchunks> <item> <chunk>   ->  <entry> <decoded item> <decoded chunk>
 //   f <nitems> <nchunks>                  ->  <gao_batch_fits: 0 or 1>
-//   w <n> <nitems> <nchunks>              ->  <gao_batch_head> <gao_batch_work_bytes>
+//   w <n> <nitems> <nchunks>              ->  gao_layout without tables: <list, the end of the head> <bytes>
 // tests/test_native_gao_batch.py writes the cases and checks the answers against Python integers.
 #include <cinttypes>
 #include <cstdio>
@@ -28,7 +28,8 @@ int main() {
       int n, nitems;
       uint64_t nchunks;
       if (std::scanf("%d %d %" SCNu64, &n, &nitems, &nchunks) != 3) return 2;
-      std::printf("%zu %zu\n", zk::gao_batch_head(n, nitems), zk::gao_batch_work_bytes(n, nitems, (size_t)nchunks));
+      const zk::GaoLayout w = zk::gao_layout(n, nitems, (size_t)nchunks, 0, 0);
+      std::printf("%zu %zu\n", w.list, w.bytes);
     } else {
       return 2;
     }

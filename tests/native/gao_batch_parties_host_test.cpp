@@ -1,6 +1,6 @@
 // Host-side run of zk_pss_repair_batch_parties' shared text (csrc/gao.hpp): a batch of items, each a compact matrix
 // [np][nchunks] of ONE party list, through what the two kernels of the call compile -- laid out in working memory by
-// gao_batch_parties_work (the head of a batch, the two tables of the list, the one dirty list):
+// gao_layout (the head of a batch, the two tables of the list, the one dirty list):
 //   scan    per (item, chunk), as its SP lanes run it: the load whose row is the popcount of the `listed` mask below the
 //           party and which multiplies by Lambda(w^p), the clean test at dimension k + rho; a dirty chunk is appended to the
 //           one list as gao_batch_entry(item, chunk)
@@ -13,7 +13,7 @@
 //   and prints per batch: per (item, chunk) a line  status errpos y'_0 ... y'_{np-1},  per item a line with its 3 + n summary
 //   words, and one line  tab inv list bytes sizeof(GaoAbsent) sizeof(GaoInvLambda) pad_ok.
 //   gao_batch_parties_host_test layout                reads lines  n nitems nchunks tab_size inv_size  and prints the four
-//   offsets of gao_batch_parties_work for each.
+//   offsets of gao_layout for each.
 // Built and run by tests/test_native_gao_batch_parties.py with the host compiler, once more under ASan + UBSan.
 #include <cinttypes>
 #include <cstdio>
@@ -93,7 +93,7 @@ template <class F, int L> int run() {
         }
       }
     // ---- working memory, as the driver lays it out: everything below is read and written THROUGH it
-    const GaoBatchPartiesWork lay = gao_batch_parties_work<F>(N, (int)nitems, (size_t)nchunks);
+    const GaoLayout lay = gao_layout<F>(N, (int)nitems, (size_t)nchunks, true);
     std::vector<unsigned char> work(lay.bytes, 0xEE);
     std::memset(work.data(), 0, lay.tab);                          // the one clear: the count and the items' summary words
     uint32_t count = 0;
@@ -202,7 +202,7 @@ int layout() {
   int n, nitems;
   uint64_t nchunks, tab, inv;
   while (std::scanf("%d %d %" SCNu64 " %" SCNu64 " %" SCNu64, &n, &nitems, &nchunks, &tab, &inv) == 5) {
-    const GaoBatchPartiesWork w = gao_batch_parties_work(n, nitems, (size_t)nchunks, (size_t)tab, (size_t)inv);
+    const GaoLayout w = gao_layout(n, nitems, (size_t)nchunks, (size_t)tab, (size_t)inv);
     std::printf("%zu %zu %zu %zu\n", w.tab, w.inv, w.list, w.bytes);
   }
   return 0;

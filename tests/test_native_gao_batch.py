@@ -1,6 +1,6 @@
 """The shared text of zk_pss_repair_batch in csrc/gao.hpp is host + device code: gao_batch_entry packs (item, chunk) into the
 32-bit entry of the one dirty list as item * nchunks + chunk, gao_batch_decode takes it apart again, gao_batch_fits is the
-refusal for nitems * nchunks >= 2^32 (and nitems outside 1 .. 48), gao_batch_head / gao_batch_work_bytes lay out the working
+refusal for nitems * nchunks >= 2^32 (and nitems outside 1 .. 48), gao_layout (without tables) lays out the working
 memory.  They are compiled for the host (tests/native/gao_batch_host_test.cpp) and checked against Python integers for
 nitems in 1 .. 48 and nchunks in {1, 4, 511, 512, 2^20}, at the first, last and boundary entries of every item.  The same
 stand-alone program is built once more with -fsanitize=address,undefined."""

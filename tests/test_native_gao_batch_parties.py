@@ -1,6 +1,6 @@
 """The shared text of zk_pss_repair_batch_parties in csrc/gao.hpp is host + device code.  tests/native/
 gao_batch_parties_host_test.cpp runs it over GaoHostGroup for a batch of 3 items of ONE party list, through working memory
-laid out by gao_batch_parties_work: the scan whose row of party p is the popcount of the `listed` mask, the one dirty list of
+laid out by gao_layout: the scan whose row of party p is the popcount of the `listed` mask, the one dirty list of
 gao_batch_entry(item, chunk) entries, and the repair that decodes an entry, loads through the table in working memory and
 writes into the item's compact matrix, adding to the item's summary words chunk by chunk.
   cases      gao_erasure_model.case_list_parties, grouped by (dimension, party list) and dealt round-robin to the 3 items, so
@@ -8,7 +8,9 @@ writes into the item's compact matrix, adding to the item's summary words chunk 
   yardstick  the single-word party-list text that tests/native/gao_repair_parties_host_test.cpp runs, case by case: status,
              errpos and the listed shares after the repair are equal; an item's summary words are the counts of its own
              verdicts (nothing leaks between items); the pad between two items keeps its value
-  layout     gao_batch_parties_work against Python integers, with the tables' real sizes and with made-up ones
+  layout     gao_layout against Python integers, with the tables' real sizes and with made-up ones
+  call       tests/native/gao_call_host_test.cpp, which checks itself: gao_layout against the offsets of the layouts it
+             replaced, every refusal of gao_list_check and gao_call_check, lists of length 1, n - 1 and n
 Fields: F17 at l = 1, 2, 4 and BN254 Fr at l = 1, 2, 4, 8.  The same stand-alone programs are built once more with
 -fsanitize=address,undefined."""
 import os
@@ -157,3 +159,33 @@ def test_host_working_memory_layout():
 def test_host_working_memory_layout_under_asan_ubsan():
     _need_cxx()
     _check_layout(True)
+
+
+def _check_call(sanitize):
+    rows = _run(_build("gao_call_host_test", sanitize), [], "")
+    assert rows == [["0", "failed"]], rows
+
+
+def test_host_call_layout_and_refusals():
+    _need_cxx()
+    _check_call(False)
+
+
+def test_host_call_layout_and_refusals_under_asan_ubsan():
+    _need_cxx()
+    _check_call(True)
+
+
+def _check_call(sanitize):
+    rows = _run(_build("gao_call_host_test", sanitize), [], "")
+    assert rows == [["0", "failed"]], rows
+
+
+def test_host_call_layout_and_refusals():
+    _need_cxx()
+    _check_call(False)
+
+
+def test_host_call_layout_and_refusals_under_asan_ubsan():
+    _need_cxx()
+    _check_call(True)

@@ -1,88 +1,106 @@
-// Part of class Engine<Cfg> (engine_impl.hpp includes this file INSIDE the class body): zk_pss_unpack_robust and
-// zk_pss_unpack_robust_parties, the error-correcting unpack; zk_pss_repair, zk_pss_repair_parties and the checked king rounds built on them.  Kernels and driver: gao_impl.hpp, compiled in gao_<curve>.hip.  Not a stand-alone header.
+// Part of class Engine<Cfg> (engine_impl.hpp includes this file INSIDE the class body): the error-correcting unpack and the
+// repair of packed scalar shares -- every zk_pss_unpack_robust* and zk_pss_repair* entry point builds a GaoCall (gao.hpp) for
+// the one driver gao_run (gao_impl.hpp, compiled in gao_<curve>.hip) -- and the checked king rounds built on them.  Not a
+// stand-alone header.
 
-  // ---------------------------------------------------------------- zk_pss_unpack_robust
-  // shares [n][nchunks] of all n parties; any of secrets, message, errpos, summary may be null.  Working memory is the caller
-  // stream's hwork (StreamWs); no host synchronisation.
-  int pss_unpack_robust(const void* shares, size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
-                        uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
-    return gao_unpack_robust_run<FrP>(this, ws(st)->hwork, l, shares, nchunks, dimension, secrets, message, status, errpos,
-                                      summary, st);
+  // a refusal of gao.hpp's host checks as this context's error
+  int refuse(const GaoRefusal& r) { return r.code ? fail(r.code, r.msg) : (int)ZK_OK; }
+  // One word (or one word in a range): working memory is the caller stream's hwork (StreamWs), sized here; no host
+  // synchronisation.  A call gao_run will refuse, or one of no chunks, needs none.
+  template <bool REPAIR>
+  int gao_word(const GaoCall& c, hipStream_t st) {
+    DevBuf& wk = ws(st)->hwork;
+    uint32_t ids[GAO_MAX_N];
+    if (c.nchunks && !gao_call_check(l, c, REPAIR, ids).code)
+      ZK_HIP(wk.ensure(gao_layout<Fr>(n, 1, c.nchunks, c.np < n, REPAIR).bytes));
+    return gao_run<FrP, REPAIR>(this, wk.p, l, c, st);
+  }
+  static GaoCall gao_call(const void* shares, const uint32_t* parties, int np, size_t nchunks, int dimension, uint8_t* status,
+                          uint32_t* errpos, uint64_t* summary) {
+    GaoCall c;
+    c.shares = const_cast<void*>(shares), c.ids = parties, c.np = np, c.nchunks = nchunks, c.dimension = dimension;
+    c.status = status, c.errpos = errpos, c.summary = summary;
+    return c;
   }
 
-  // ---------------------------------------------------------------- zk_pss_unpack_robust_parties
-  // shares [nparties][nchunks] of the listed parties (ascending ids; null: 0 .. nparties - 1); the rest as above
+  // ---------------------------------------------------------------- zk_pss_unpack_robust, zk_pss_unpack_robust_parties
+  // shares [nparties][nchunks] of the listed parties (ascending ids; null: 0 .. nparties - 1), all n of them in the first
+  // form; any of secrets, message, errpos, summary may be null.
+  int pss_unpack_robust(const void* shares, size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
+                        uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    return pss_unpack_robust_parties(shares, nullptr, n, nchunks, dimension, secrets, message, status, errpos, summary, st);
+  }
   int pss_unpack_robust_parties(const void* shares, const uint32_t* parties, int nparties, size_t nchunks, int dimension,
                                 void* secrets, void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary,
                                 hipStream_t st) override {
-    return gao_unpack_robust_parties_run<FrP>(this, ws(st)->hwork, l, shares, parties, nparties, nchunks, dimension, secrets,
-                                              message, status, errpos, summary, st);
+    GaoCall c = gao_call(shares, parties, nparties, nchunks, dimension, status, errpos, summary);
+    c.secrets = secrets, c.message = message;
+    return gao_word<false>(c, st);
   }
 
-  // ---------------------------------------------------------------- zk_pss_repair
-  // shares [n][nchunks] of all n parties, in place: status, errpos and summary are pss_unpack_robust's; in a corrected chunk the
-  // share of every party named in errpos becomes h(w_n^p), every other element keeps its bytes.  Same working memory, no host
-  // synchronisation.
+  // ---------------------------------------------------------------- zk_pss_repair, zk_pss_repair_parties
+  // shares [nparties][nchunks] of the listed parties, in place: status, errpos and summary are the unpack's; in a corrected
+  // chunk the element in the row of every listed party named in errpos becomes h(w_n^p), every other element keeps its bytes.
   int pss_repair(void* shares, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary,
                  hipStream_t st) override {
-    return gao_repair_run<FrP>(this, ws(st)->hwork, l, shares, nchunks, dimension, status, errpos, summary, st);
+    return pss_repair_parties(shares, nullptr, n, nchunks, dimension, status, errpos, summary, st);
+  }
+  int pss_repair_parties(void* shares, const uint32_t* parties, int nparties, size_t nchunks, int dimension, uint8_t* status,
+                         uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
+    return gao_word<true>(gao_call(shares, parties, nparties, nchunks, dimension, status, errpos, summary), st);
   }
 
-  // ---------------------------------------------------------------- zk_pss_repair_batch
-  // nitems matrices [n][nchunks], item i at shares + i * item_stride (KingBatch::stride; circom_h's W0 / W1): pss_repair of
-  // each, with ONE clear, ONE scan launch (the item on grid.y) and ONE decoder launch over one list of dirty (item, chunk)
-  // entries.  status / errpos [nitems][nchunks], summary [nitems][3 + n].  A refusal writes nothing.
+  // ---------------------------------------------------------------- the range form of zk_pss_repair_parties
+  // The word of an all-to-all king (engine_dist.inc.hpp): rg.cnt valid columns of a block [nparties][rg.stride], column c
+  // being chunk rg.chunk(c) of a word of rg.len chunks (king_range.hpp).  Only those columns are read and rewritten, status
+  // and errpos [rg.len] are written at the mapped chunks only, the summary counts the rg.cnt chunks.
+  int pss_repair_range(void* shares, const uint32_t* parties, int nparties, size_t stride, uint32_t cnt, uint32_t len,
+                       uint32_t base, uint32_t shift, int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                       hipStream_t st) override {
+    const GaoRange rg{stride, cnt, base, shift, len};
+    GaoCall c = gao_call(shares, parties, nparties, cnt, dimension, status, errpos, summary);
+    c.range = &rg;
+    return gao_word<true>(c, st);
+  }
+
+  // ---------------------------------------------------------------- zk_pss_repair_batch, zk_pss_repair_batch_parties
+  // nitems matrices [nparties][nchunks] of ONE party list (all n parties in the first form), item i at shares + i * item_stride
+  // (KingBatch::stride; circom_h's W0 / W1): the repair of each, with ONE clear, the tables of the list put into working
+  // memory once, ONE scan launch (the item on grid.y) and ONE decoder launch over one list of dirty (item, chunk) entries.
+  // status / errpos [nitems][nchunks], summary [nitems][3 + n].  A refusal writes nothing.
   static_assert(GAO_BATCH_MAX == KING_BATCH, "a repair batch takes the items of a king batch");
-  int repair_batch_check(const void* shares, size_t item_stride, int nitems, size_t nchunks, int dimension,
-                         const uint8_t* status) {
-    if (nitems < 1 || nitems > KING_BATCH) return fail(ZK_ERR_BAD_INPUT, "bad repair batch");
-    if (dimension < 1 || dimension > n - 1) return fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
-    if (nchunks == 0) return ZK_OK;
-    if (!shares || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    if (!gao_batch_fits((uint64_t)nitems, nchunks)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
-    if (item_stride < (size_t)n * nchunks) return fail(ZK_ERR_BAD_INPUT, "item stride below n * nchunks");
+  // The refusals of a batch.  list_first: zk_pss_repair_batch_parties refuses its list, dimension and too few shares ahead of
+  // a bad item count, zk_pss_repair_batch a bad item count ahead of the dimension.
+  int repair_batch_check(const GaoCall& c, bool list_first, uint32_t* ids) {
+    int rc;
+    if (list_first && (rc = refuse(gao_list_check(c.ids, c.np, c.dimension, n, ids)))) return rc;
+    if (c.nitems < 1 || c.nitems > KING_BATCH) return fail(ZK_ERR_BAD_INPUT, "bad repair batch");
+    if (!list_first && (rc = refuse(gao_list_check(c.ids, c.np, c.dimension, n, ids)))) return rc;
+    if (c.nchunks == 0) return ZK_OK;
+    if (!c.shares || !c.status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (!gao_batch_fits((uint64_t)c.nitems, c.nchunks)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
+    if (c.item_stride < (size_t)c.np * c.nchunks)
+      return fail(ZK_ERR_BAD_INPUT, c.np == n ? "item stride below n * nchunks" : "item stride below nparties * nchunks");
     return ZK_OK;
+  }
+  int repair_batch(const uint32_t* parties, int np, bool list_first, void* shares, size_t item_stride, int nitems, size_t nchunks,
+                   int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
+    GaoCall c = gao_call(shares, parties, np, nchunks, dimension, status, errpos, summary);
+    c.nitems = nitems, c.item_stride = item_stride;
+    uint32_t ids[GAO_MAX_N];
+    int rc = repair_batch_check(c, list_first, ids);
+    if (rc || !nchunks) return rc;
+    DevBuf& wk = ws(st)->hwork;
+    ZK_HIP(wk.ensure(gao_layout<Fr>(n, nitems, nchunks, np < n).bytes));
+    return gao_run<FrP, true>(this, wk.p, l, c, st);
   }
   int pss_repair_batch(void* shares, size_t item_stride, int nitems, size_t nchunks, int dimension, uint8_t* status,
                        uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
-    int rc = repair_batch_check(shares, item_stride, nitems, nchunks, dimension, status);
-    if (rc || !nchunks) return rc;
-    DevBuf& wk = ws(st)->hwork;
-    ZK_HIP(wk.ensure(gao_batch_work_bytes(n, nitems, nchunks)));
-    return gao_repair_batch_run<FrP>(this, wk.p, l, shares, item_stride, nitems, nchunks, dimension, status, errpos, summary,
-                                     st);
-  }
-
-  // ---------------------------------------------------------------- zk_pss_repair_batch_parties
-  // nitems compact matrices [nparties][nchunks] of ONE party list, item i at shares + i * item_stride: pss_repair_parties of
-  // each with the launches of pss_repair_batch and the two tables of the list, put into working memory once per call.  The
-  // refusals are pss_repair_parties' (list, dimension, too few shares) and pss_repair_batch's; a refusal writes nothing.
-  int repair_list_check(const uint32_t* parties, int np, int dimension, uint32_t* ids) {
-    if (np <= 0 || np > n) return fail(ZK_ERR_BAD_INPUT, "bad party count");
-    for (int i = 0; i < np; i++) {
-      ids[i] = parties ? parties[i] : (uint32_t)i;
-      if (ids[i] >= (uint32_t)n || (i > 0 && ids[i] <= ids[i - 1]))
-        return fail(ZK_ERR_BAD_INPUT, "party ids must be ascending and < n");
-    }
-    if (dimension < 1 || dimension > n - 1) return fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
-    if (np <= dimension) return fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
-    return ZK_OK;
+    return repair_batch(nullptr, n, false, shares, item_stride, nitems, nchunks, dimension, status, errpos, summary, st);
   }
   int pss_repair_batch_parties(void* shares, const uint32_t* parties, int np, size_t item_stride, int nitems, size_t nchunks,
                                int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
-    uint32_t ids[GAO_MAX_N];
-    int rc = repair_list_check(parties, np, dimension, ids);
-    if (rc) return rc;
-    if (np == n) return pss_repair_batch(shares, item_stride, nitems, nchunks, dimension, status, errpos, summary, st);
-    if (nitems < 1 || nitems > KING_BATCH) return fail(ZK_ERR_BAD_INPUT, "bad repair batch");
-    if (nchunks == 0) return ZK_OK;
-    if (!shares || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    if (!gao_batch_fits((uint64_t)nitems, nchunks)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
-    if (item_stride < (size_t)np * nchunks) return fail(ZK_ERR_BAD_INPUT, "item stride below nparties * nchunks");
-    DevBuf& wk = ws(st)->hwork;
-    ZK_HIP(wk.ensure(gao_batch_parties_work<Fr>(n, nitems, nchunks).bytes));
-    return gao_repair_batch_parties_run<FrP>(this, wk.p, l, shares, ids, np, item_stride, nitems, nchunks, dimension, status,
-                                             errpos, summary, st);
+    return repair_batch(parties, np, true, shares, item_stride, nitems, nchunks, dimension, status, errpos, summary, st);
   }
   // the in-mask rows of a list for up to three compact words [np][width], item_stride apart, in one launch: row r of item y
   // becomes x * k (with `scale`) + row ids[r] of masks[y]; a null mask skips the item (vec_add_list_rows_kernel, ntt.hpp)
@@ -160,28 +178,6 @@
     return deg_red_np((const Fr*)x, nullptr, nullptr, n, len, seed, (Fr*)x, (const Fr*)out_mask, st);
   }
 
-  // ---------------------------------------------------------------- zk_pss_repair_parties
-  // shares [nparties][nchunks] of the listed parties, in place: status, errpos and summary are pss_unpack_robust_parties'; in a
-  // corrected chunk the element in the row of every listed party named in errpos becomes h(w_n^p), every other element keeps
-  // its bytes.  With nparties == n this is pss_repair.
-  int pss_repair_parties(void* shares, const uint32_t* parties, int nparties, size_t nchunks, int dimension, uint8_t* status,
-                         uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
-    return gao_repair_parties_run<FrP>(this, ws(st)->hwork, l, shares, parties, nparties, nchunks, dimension, status, errpos,
-                                       summary, st);
-  }
-
-  // ---------------------------------------------------------------- the range form of zk_pss_repair_parties
-  // The word of an all-to-all king (engine_dist.inc.hpp): rg.cnt valid columns of a block [nparties][rg.stride], column c
-  // being chunk rg.chunk(c) of a word of rg.len chunks (king_range.hpp).  Only those columns are read and rewritten, status
-  // and errpos [rg.len] are written at the mapped chunks only, the summary counts the rg.cnt chunks.
-  int pss_repair_range(void* shares, const uint32_t* parties, int nparties, size_t stride, uint32_t cnt, uint32_t len,
-                       uint32_t base, uint32_t shift, int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary,
-                       hipStream_t st) override {
-    const GaoRange rg{stride, cnt, base, shift, len};
-    return gao_repair_range_run<FrP>(this, ws(st)->hwork, l, shares, parties, nparties, rg, dimension, status, errpos, summary,
-                                     st);
-  }
-
   // ---------------------------------------------------------------- checked king rounds with a party list
   // Only the listed parties' words reached the king: repair with the list at dimension 2l, cap = (np - 2l) / 2, then the
   // unchecked king with the same list (umat_for).  The refusals are pss_repair_parties' and the unchecked king's (checked_list).
@@ -201,14 +197,9 @@
   // unpack_missing_shares takes a list only with more than 2 (t + l - 1) = 4l - 2 shares (pss.rs:183-186), so a list is all n
   // parties or n - 1 of them.  Asked before anything is written: a refusal leaves the caller's buffers as they were.
   int checked_list(const uint32_t* parties, int np, int dimension, uint32_t* ids) {
-    if (np <= 0 || np > n) return fail(ZK_ERR_BAD_INPUT, "bad party count");
-    for (int i = 0; i < np; i++) {
-      ids[i] = parties ? parties[i] : (uint32_t)i;
-      if (ids[i] >= (uint32_t)n || (i > 0 && ids[i] <= ids[i - 1]))
-        return fail(ZK_ERR_BAD_INPUT, "party ids must be ascending and < n");
-    }
-    if (np <= dimension || (np < n && np <= 4 * l - 2))
-      return fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
+    int rc = refuse(gao_list_check(parties, np, dimension, n, ids));
+    if (rc) return rc;
+    if (np < n && np <= 4 * l - 2) return fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
     return ZK_OK;
   }
   // d_fft / d_ifft: shares, in_mask and the outputs are [n][m/l]; the king's word is compact, [np][m/l] in king_tmp: row i is

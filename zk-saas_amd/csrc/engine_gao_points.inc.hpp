@@ -83,12 +83,11 @@
     *out = it->second.second;
     return ZK_OK;
   }
+  // the count and the ids of gao_list_check; the dimension and too few shares are refused below, behind other refusals and
+  // with the party 0
   int points_party_list_ok(const uint32_t* parties, int np) {
-    if (np < 1 || np > n) return fail(ZK_ERR_BAD_INPUT, "bad party count");
-    for (int i = 0; parties && i < np; i++)
-      if (parties[i] >= (uint32_t)n || (i > 0 && parties[i] <= parties[i - 1]))
-        return fail(ZK_ERR_BAD_INPUT, "party ids must be ascending and < n");
-    return ZK_OK;
+    uint32_t ids[GAO_MAX_N];
+    return refuse(gao_list_check(parties, np, 0, n, ids, true));
   }
   template <bool REPAIR>
   int points_robust_parties(int group, std::conditional_t<REPAIR, void*, const void*> shares, const uint32_t* parties, int np,

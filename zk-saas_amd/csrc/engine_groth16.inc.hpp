@@ -124,14 +124,15 @@
     if (!gao_batch_fits(3, Lc)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
     const size_t vec_bytes = 6 * per * sizeof(Fr);
     static_assert(sizeof(Fr) % 32 == 0, "the repair's working memory stays aligned behind the vectors");
-    ZK_HIP(hwork.ensure(vec_bytes + gao_batch_work_bytes(n, 3, Lc)));
+    ZK_HIP(hwork.ensure(vec_bytes + gao_layout<Fr>(n, 3, Lc, false).bytes));
     Fr* W0 = (Fr*)hwork.p;
     Fr* W1 = W0 + 3 * per;
     void* gwk = (char*)hwork.p + vec_bytes;
     auto repair = [&](Fr* W, int first, int items, int dimension) {
-      return gao_repair_batch_run<FrP>(this, gwk, l, W, per, items, Lc, dimension, rep.status + first * Lc,
-                                       rep.errpos ? rep.errpos + first * Lc : nullptr,
-                                       rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr, st);
+      GaoCall c = gao_call(W, nullptr, n, Lc, dimension, rep.status + first * Lc, rep.errpos ? rep.errpos + first * Lc : nullptr,
+                           rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr);
+      c.nitems = items, c.item_stride = per;
+      return gao_run<FrP, true>(this, gwk, l, c, st);
     };
     Fr w2m = root_of_unity(log_m + 1);
     bool masked[3];
@@ -226,7 +227,7 @@
     const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
     if (!gao_batch_fits(3, Lc)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
     const size_t vec_bytes = 6 * per * sizeof(Fr);
-    ZK_HIP(hwork.ensure(vec_bytes + gao_batch_parties_work<Fr>(n, 3, Lc).bytes));
+    ZK_HIP(hwork.ensure(vec_bytes + gao_layout<Fr>(n, 3, Lc, true).bytes));
     Fr* W0 = (Fr*)hwork.p;
     Fr* W1 = W0 + 3 * per;
     void* gwk = (char*)hwork.p + vec_bytes;
@@ -238,9 +239,10 @@
       const Fr* masks[3];
       for (int k = 0; k < 3; k++) masked[k] = (masks[k] = mk ? (const Fr*)mk->fft_in[first + k] : nullptr) != nullptr;
       if ((r = add_list_rows(W0, per, masks, 3, ids, np, inverse != 0, minv, Lc, st))) return r;
-      return gao_repair_batch_parties_run<FrP>(this, gwk, l, W0, ids, np, per, 3, Lc, 2 * l, rep.status + first * Lc,
-                                               rep.errpos ? rep.errpos + first * Lc : nullptr,
-                                               rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr, st);
+      GaoCall c = gao_call(W0, ids, np, Lc, 2 * l, rep.status + first * Lc, rep.errpos ? rep.errpos + first * Lc : nullptr,
+                           rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr);
+      c.nitems = 3, c.item_stride = per;
+      return gao_run<FrP, true>(this, gwk, l, c, st);
     };
     Fr w2m = root_of_unity(log_m + 1);
     bool masked[3];

@@ -17,9 +17,13 @@
 // zk_pss_unpack_robust_parties -- the shares of a party list, the others absent -- runs the same two parts on a word made
 // full-length again: the section "absent parties" below (tests/native/gao_erasure_host_test.cpp runs that text), and
 // zk_pss_repair_parties is its repair form (tests/native/gao_repair_parties_host_test.cpp).
+// Every public form -- all parties or a list, unpack or repair, one word, a batch of words or a word in a block with padding
+// -- is ONE description of a call (GaoCall, the last section) handed to ONE host driver, gao_run<FrP, REPAIR> (gao_impl.hpp):
+// its refusals (gao_list_check, gao_call_check) and its working memory (gao_layout) are host text below.
 #pragma once
 #include <type_traits>
 
+#include "../../include/zksaas.h"
 #include "field.hpp"
 #include "king_range.hpp"
 #if defined(__HIPCC__)
@@ -509,74 +513,110 @@ ZK_HD void gao_batch_decode(uint32_t entry, uint32_t nchunks, uint32_t& item, ui
   item = entry / nchunks;
   chunk = entry - item * nchunks;
 }
-// Working memory of a batch: [0] the count of dirty chunks, shared; from byte 32 the summary words of the items, (3 + n) each,
-// when the caller passes none; the list behind this head.
-constexpr size_t gao_batch_head(int n, int nitems) { return (32 + (size_t)nitems * (3 + n) * 8 + 31) / 32 * 32; }
-constexpr size_t gao_batch_work_bytes(int n, int nitems, size_t nchunks) {
-  return gao_batch_head(n, nitems) + (size_t)nitems * nchunks * 4;
+// With a party list (zk_pss_repair_batch_parties) an item is the compact matrix [nparties][nchunks], row r the shares of
+// parties[r]; the list, and so the two tables of zk_pss_repair_parties (GaoAbsent, GaoInvLambda), are the same for every item.
+
+// ---------------------------------------------------------------- one call
+// What every form has in common and where the forms differ; gao_run<FrP, REPAIR> (gao_impl.hpp) takes one.  REPAIR is the
+// driver's template flag: false -- the unpack, `shares` read, secrets / message written; true -- the repair, `shares` written
+// in place, secrets and message unused.
+struct GaoCall {
+  void* shares = nullptr;              // device: per item a matrix [np][nchunks], rows pitch() elements apart
+  const uint32_t* ids = nullptr;       // host: np ascending party ids below n; null: 0 .. np - 1
+  int np = 0;                          // np == n: all parties, no list
+  int nitems = 1;                      // a batch: nitems matrices item_stride elements apart, ONE list of dirty chunks;
+  size_t item_stride = 0;              //   status / errpos [nitems][nchunks], summary [nitems][3 + n].  A single word: 1 and 0
+  size_t nchunks = 0;                  // chunks of an item; with a range its valid columns, range->cnt
+  const GaoRange* range = nullptr;     // the word lies in a block with padding (king_range.hpp); a repair of one word only
+  int dimension = 0;
+  void* secrets = nullptr;             // [nchunks][l] or null
+  void* message = nullptr;             // [dimension][nchunks] or null
+  uint8_t* status = nullptr;           // [nitems][nchunks]; with a range [range->len], written at range->chunk(column)
+  uint32_t* errpos = nullptr;          // as status, or null
+  uint64_t* summary = nullptr;         // [nitems][3 + n] or null
+  size_t pitch() const { return range ? range->stride : nchunks; }
+  bool batch() const { return item_stride != 0; }
+};
+
+// A refusal: the return code and the text of zk_last_error; code ZK_OK: none.
+struct GaoRefusal {
+  int code;
+  const char* msg;
+};
+// THE check of a party list: a valid count, ascending ids below n -- written to ids[GAO_MAX_N], 0 .. np - 1 for a null list --
+// a dimension in 1 .. n - 1 and more shares than the dimension (pss.rs:183-186), refused in this order.  ids_only: stop
+// behind the ids -- the point-share entry points refuse a dimension and too few shares at a place and with a text of their own.
+inline GaoRefusal gao_list_check(const uint32_t* parties, int np, int dimension, int n, uint32_t* ids, bool ids_only = false) {
+  if (np <= 0 || np > n) return {ZK_ERR_BAD_INPUT, "bad party count"};
+  for (int i = 0; i < np; i++) {
+    ids[i] = parties ? parties[i] : (uint32_t)i;
+    if (ids[i] >= (uint32_t)n || (i > 0 && ids[i] <= ids[i - 1])) return {ZK_ERR_BAD_INPUT, "party ids must be ascending and < n"};
+  }
+  if (ids_only) return {ZK_OK, nullptr};
+  if (dimension < 1 || dimension > n - 1) return {ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1"};
+  if (np <= dimension) return {ZK_ERR_PROTOCOL, "Not enough shares to reconstruct"};
+  return {ZK_OK, nullptr};
+}
+// Every refusal of a call, in the order the entry points have always tried them.  A call of no chunks is no refusal and
+// its pointers are not looked at.  (What a batch adds -- the item count, the item stride -- is its entry point's:
+// engine_gao.inc.hpp repair_batch_check.)
+inline GaoRefusal gao_call_check(int l, const GaoCall& c, bool repair, uint32_t* ids) {
+  if (const GaoRange* rg = c.range) {
+    if (!repair || c.batch()) return {ZK_ERR_BAD_INPUT, "the range form is a repair of one word"};
+    if (rg->cnt > rg->stride || rg->cnt > rg->len || rg->base >= (rg->len ? rg->len : 1) || rg->shift > rg->len ||
+        rg->stride > 0xffffffffull || c.nchunks != rg->cnt)
+      return {ZK_ERR_BAD_INPUT, "bad range: cnt <= stride < 2^32, cnt <= len, base < len, shift <= len"};
+  }
+  if (l != 1 && l != 2 && l != 4 && l != 8) return {ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8"};
+  const GaoRefusal r = gao_list_check(c.ids, c.np, c.dimension, 4 * l, ids);
+  if (r.code || c.nchunks == 0) return r;
+  if (!c.shares || !c.status) return {ZK_ERR_BAD_INPUT, "null pointer"};
+  if (c.nchunks >= ((uint64_t)1 << 32)) return {ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks"};
+  return {ZK_OK, nullptr};
 }
 
-// ---------------------------------------------------------------- a batch of words of one party list (zk_pss_repair_batch_parties)
-// Item i is a compact matrix [nparties][nchunks] at shares + i * item_stride, row r the shares of parties[r]; the list, and so
-// the two tables of zk_pss_repair_parties (GaoAbsent, GaoInvLambda), are the same for every item.  Working memory: the head of
-// a batch (the count, the items' summary words), the two tables, then the one list of (item, chunk) entries.  Byte offsets.
-struct GaoBatchPartiesWork {
+// ---------------------------------------------------------------- working memory of a call
+// [0] the count of dirty chunks; from byte 32 the summary words of the items, (3 + n) each, used when the caller passes none;
+// for a party list the table GaoAbsent and, for a repair, GaoInvLambda; then the ONE list of dirty chunks, room for every chunk
+// of every item.  Byte offsets, multiples of 32: a call clears [0, tab); without tables tab == inv == list.  A caller may
+// place this behind memory of its own (the checked h chain puts it behind its six vectors) and sizes it with `bytes`.
+struct GaoLayout {
   size_t tab, inv, list, bytes;
 };
-ZK_HD GaoBatchPartiesWork gao_batch_parties_work(int n, int nitems, size_t nchunks, size_t tab_size, size_t inv_size) {
-  GaoBatchPartiesWork w;
-  w.tab = gao_batch_head(n, nitems);
+ZK_HD GaoLayout gao_layout(int n, int nitems, size_t nchunks, size_t tab_size, size_t inv_size) {
+  GaoLayout w;
+  w.tab = (32 + (size_t)nitems * (3 + n) * 8 + 31) / 32 * 32;
   w.inv = w.tab + (tab_size + 31) / 32 * 32;
   w.list = w.inv + (inv_size + 31) / 32 * 32;
   w.bytes = w.list + (size_t)nitems * nchunks * 4;
   return w;
 }
+// with the tables' real sizes; list: the call has a party list (np < n), repair: it is one
 template <class F>
-ZK_HD GaoBatchPartiesWork gao_batch_parties_work(int n, int nitems, size_t nchunks) {
-  return gao_batch_parties_work(n, nitems, nchunks, sizeof(GaoAbsent<F>), sizeof(GaoInvLambda<F>));
+ZK_HD GaoLayout gao_layout(int n, int nitems, size_t nchunks, bool list, bool repair = true) {
+  return gao_layout(n, nitems, nchunks, list ? sizeof(GaoAbsent<F>) : 0, list && repair ? sizeof(GaoInvLambda<F>) : 0);
+}
+// The names the batch forms have for the same layout (their host tests, tests/native/gao_batch*_host_test.cpp, use them):
+// the head of a batch without tables and its size, and the layout with the two tables of a party list.
+using GaoBatchPartiesWork = GaoLayout;
+ZK_HD size_t gao_batch_head(int n, int nitems) { return gao_layout(n, nitems, 0, 0, 0).list; }
+ZK_HD size_t gao_batch_work_bytes(int n, int nitems, size_t nchunks) { return gao_layout(n, nitems, nchunks, 0, 0).bytes; }
+ZK_HD GaoLayout gao_batch_parties_work(int n, int nitems, size_t nchunks, size_t tab_size, size_t inv_size) {
+  return gao_layout(n, nitems, nchunks, tab_size, inv_size);
+}
+template <class F>
+ZK_HD GaoLayout gao_batch_parties_work(int n, int nitems, size_t nchunks) {
+  return gao_layout<F>(n, nitems, nchunks, true);
 }
 
 #if defined(__HIPCC__)
 class IEngine;
-struct DevBuf;
-// zk_pss_repair_batch_parties: nitems compact matrices [nparties][nchunks] of the party list ids[0 .. np - 1] (ascending, below
-// 4 l, dimension < np < 4 l), item_stride elements apart, in place; status and errpos [nitems][nchunks], summary
-// [nitems][3 + n] or null.  wk: working memory of gao_batch_parties_work<Fr>(4 l, nitems, nchunks).bytes bytes that the caller
-// holds; the argument checks, and the all-parties case, are the caller's (engine_gao.inc.hpp).
-template <class FrP>
-int gao_repair_batch_parties_run(IEngine* e, void* wk, int l, void* shares, const uint32_t* ids, int np, size_t item_stride,
-                                 int nitems, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos,
-                                 uint64_t* summary, hipStream_t st);
-// zk_pss_repair_batch: nitems share matrices [n][nchunks], item_stride elements apart, in place; status and errpos
-// [nitems][nchunks], summary [nitems][3 + n] or null.  wk: working memory of gao_batch_work_bytes(4 l, nitems, nchunks) bytes
-// that the caller holds (behind the words of a chain, for instance); the argument checks are the caller's (engine_gao.inc.hpp).
-template <class FrP>
-int gao_repair_batch_run(IEngine* e, void* wk, int l, void* shares, size_t item_stride, int nitems, size_t nchunks,
-                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
-// zk_pss_unpack_robust over the scalar field FrP (engine_gao.inc.hpp has the argument list); wk: working memory
-template <class FrP>
-int gao_unpack_robust_run(IEngine* e, DevBuf& wk, int l, const void* shares, size_t nchunks, int dimension, void* secrets,
-                          void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
-// zk_pss_repair: shares [n][nchunks] in place, the verdicts of the call above
-template <class FrP>
-int gao_repair_run(IEngine* e, DevBuf& wk, int l, void* shares, size_t nchunks, int dimension, uint8_t* status,
-                   uint32_t* errpos, uint64_t* summary, hipStream_t st);
-// zk_pss_unpack_robust_parties: shares [nparties][nchunks] of the listed parties (NULL: 0 .. nparties - 1)
-template <class FrP>
-int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wk, int l, const void* shares, const uint32_t* parties, int nparties,
-                                  size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
-                                  uint32_t* errpos, uint64_t* summary, hipStream_t st);
-// zk_pss_repair_parties: shares [nparties][nchunks] of the listed parties in place, the verdicts of the call above
-template <class FrP>
-int gao_repair_parties_run(IEngine* e, DevBuf& wk, int l, void* shares, const uint32_t* parties, int nparties, size_t nchunks,
-                           int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
-// the range form of zk_pss_repair_parties: a word whose rg.cnt valid columns lie in a block with padding, rows rg.stride
-// elements apart (king_range.hpp GaoRange); the shares are read and rewritten at row * rg.stride + c for c < rg.cnt only,
-// status and errpos [rg.len] are written at rg.chunk(c) and nowhere else, the summary counts the rg.cnt chunks.  With
-// stride == cnt == len, base == 0 and shift == 0 every output and byte written is gao_repair_parties_run's.
-template <class FrP>
-int gao_repair_range_run(IEngine* e, DevBuf& wk, int l, void* shares, const uint32_t* parties, int nparties, const GaoRange& rg,
-                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st);
+// The one host driver, instantiated per curve in gao_<curve>.hip: the refusals of gao_call_check, one clear of the head of
+// wk (and of the caller's summary), with a party list the launches that put its tables into wk, stage 1 and stage 2 -- no
+// host synchronisation.  wk: device memory of gao_layout<Fr>(4 l, nitems, nchunks, np < 4 l, REPAIR).bytes bytes that the
+// caller holds; a refused call and one of no chunks do not touch it.  A range of no columns clears the summary.
+template <class FrP, bool REPAIR>
+int gao_run(IEngine* e, void* wk, int l, const GaoCall& call, hipStream_t st);
 #endif
 
 }  // namespace zk

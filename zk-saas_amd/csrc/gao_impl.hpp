@@ -1,15 +1,19 @@
-// Kernels and host drivers of zk_pss_unpack_robust, zk_pss_unpack_robust_parties, zk_pss_repair, zk_pss_repair_parties,
-// zk_pss_repair_batch and zk_pss_repair_batch_parties (gao.hpp says what they compute).  Included
-// by gao_<curve>.hip only.  Each stage is one body with two kernels: the all-parties one, and the one for a party list (ER).
+// Kernels and the host driver of the error-correcting unpack and the repair over packed scalar shares (gao.hpp says what
+// they compute).  Included by gao_<curve>.hip only.  ONE driver, gao_run<FrP, REPAIR>, serves every public form from a
+// GaoCall; each stage is ONE body and ONE kernel template, instantiated for the flag sets the forms need:
 //   stage 1  one lane per chunk (two at l = 8): the n shares are loaded once, transformed in registers, coefficients k .. n - 1 tested; a
 //            clean chunk gets its secrets (and message) and status 0, a dirty one is appended to a compact list
 //   stage 2  one group of n lanes per listed chunk: Gao's decoder (gao_chunk) over the wave's cross-lane builtins.  Launched
 //            unconditionally with a grid derived from nchunks; it reads the count from device memory, strides over the list and
 //            leaves at once when the count is zero -- so the call never synchronises with the host.
-// zk_pss_repair is the all-parties form of both with no secrets and no message: stage 1 ends at the test of the coefficients
-// (SCAN: the scan kernel), stage 2 stores lane p's re-encoding over the share of a party named in errpos (REPAIR).
-// zk_pss_repair_parties is SCAN and REPAIR together with ER: the scan loads with the multiplication by Lambda(w^p) and tests
-// at k + rho, the repair divides lane p's re-encoding by Lambda(w^p) again and stores it into the party's row.
+// The flags: ER -- a party list with absent parties; SCAN (stage 1) / REPAIR (stage 2) -- the repair: stage 1 ends at the test
+// of the coefficients, stage 2 stores lane p's re-encoding over the share of a party named in errpos, no secrets and no
+// message; BATCH -- several words, one list; RANGE -- a word in a block with padding.
+//   zk_pss_unpack_robust            -                 zk_pss_unpack_robust_parties      ER
+//   zk_pss_repair                   REPAIR            zk_pss_repair_parties             ER REPAIR
+//   zk_pss_repair_batch             REPAIR BATCH      zk_pss_repair_batch_parties       ER REPAIR BATCH
+//   zk_pss_repair_range, all n      REPAIR RANGE      zk_pss_repair_range, a list       ER REPAIR RANGE
+// and a list of all n parties is the form without ER.
 #pragma once
 #include <algorithm>
 
@@ -63,6 +67,32 @@ struct GaoWork {
   uint32_t* count;
   unsigned long long* summary;       // [3 + n]: clean, corrected, failed, corrections per party
   uint32_t* list;
+};
+
+// ---------------------------------------------------------------- the arguments of both kernels
+// Filled once per call.  `ab` -- a kilobyte, read by stage 1 at compile-time indices -- is a member only with ER; every other
+// member is a word or two.  Stage 2 takes the struct by value: its instances are register for register what they were with
+// argument lists of their own (docs/gao_kernel_resources.md).  Stage 1 takes the members one by one (see its kernel).
+struct GaoNone {};
+template <class P, bool ER>
+struct GaoArgs {
+  using F = Fp<P>;
+  GaoConsts<F> c;
+  std::conditional_t<ER, GaoAbsentLoad<F>, GaoNone> ab;      // ER, stage 1
+  const GaoAbsent<F>* tab;      // ER: the device table (stage 1 of the unpack, stage 2)
+  const F* ilam;                // ER, REPAIR: the device table of the inverses
+  int n, l;
+  F* shares;                    // written by the repair only
+  size_t item_stride;           // BATCH
+  size_t nchunks;               // (RANGE: rg.cnt is read)
+  GaoRangeDev rg;               // RANGE
+  int k, rho;                   // the caller's dimension; ER: the number of absent parties
+  uint32_t listed;              // ER: bit p -- party p is listed
+  F* secrets;                   // the unpack
+  F* message;
+  uint8_t* status;
+  uint32_t* errpos;
+  GaoWork wk;
 };
 
 // ---------------------------------------------------------------- stage 1
@@ -168,73 +198,35 @@ __device__ __forceinline__ void gao_stage1_body(const GaoConsts<Fp<P>>& c, const
   __syncthreads();
   if (dirty) wk.list[wg_base + wave_off + rank] = entry0 + (uint32_t)j;
 }
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
-                                                                size_t nchunks, int k, Fp<P>* __restrict__ secrets,
-                                                                Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
-                                                                uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage1_body<P, L, false>(c, shares, nchunks, k, secrets, message, status, errpos, wk, nullptr, 0, nullptr);
-}
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_scan_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
-                                                              size_t nchunks, int k, uint8_t* __restrict__ status,
-                                                              uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage1_body<P, L, false, true>(c, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr, 0, nullptr);
-}
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_scan_parties_kernel(const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab,
-                                                                      const Fp<P>* __restrict__ shares, size_t nchunks, int k,
-                                                                      int rho, uint32_t listed, uint8_t* __restrict__ status,
-                                                                      uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage1_body<P, L, true, true>(c, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, &ab, rho, nullptr, listed);
-}
-// the range forms of the two scans above (engine_dist.inc.hpp: a rank's [np][seg] block under the all-to-all king)
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_scan_range_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
-                                                                    GaoRangeDev rg, int k, uint8_t* __restrict__ status,
-                                                                    uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage1_body<P, L, false, true, true>(c, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, nullptr, 0, nullptr, 0, 0,
-                                           rg);
-}
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_scan_parties_range_kernel(
-    const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab, const Fp<P>* __restrict__ shares, GaoRangeDev rg, int k, int rho,
-    uint32_t listed, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage1_body<P, L, true, true, true>(c, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, &ab, rho, nullptr, listed,
-                                          0, rg);
-}
-// zk_pss_repair_batch: the scan of item blockIdx.y -- its matrix, its rows of status and errpos, its summary words; the count
-// and the list are the batch's
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_scan_batch_kernel(const GaoConsts<Fp<P>> c, const Fp<P>* __restrict__ shares,
-                                                                    size_t item_stride, size_t nchunks, int k,
-                                                                    uint8_t* __restrict__ status,
-                                                                    uint32_t* __restrict__ errpos, GaoWork wk) {
-  const uint32_t item = blockIdx.y;
-  wk.summary += (size_t)item * (3 + 4 * L);
-  gao_stage1_body<P, L, false, true>(c, shares + item * item_stride, nchunks, k, nullptr, nullptr, status + item * nchunks,
-                                     errpos ? errpos + item * nchunks : nullptr, wk, nullptr, 0, nullptr, 0,
-                                     gao_batch_entry(item, 0, (uint32_t)nchunks));
-}
-// zk_pss_repair_batch_parties: the scan of item blockIdx.y of a batch of compact matrices of one party list -- the load of
-// gao_scan_parties_kernel (the row of party p is the popcount of `listed` below p), the item offsets and entry0 of the batch
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_scan_batch_parties_kernel(
-    const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab, const Fp<P>* __restrict__ shares, size_t item_stride, size_t nchunks,
-    int k, int rho, uint32_t listed, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
-  const uint32_t item = blockIdx.y;
-  wk.summary += (size_t)item * (3 + 4 * L);
-  gao_stage1_body<P, L, true, true>(c, shares + item * item_stride, nchunks, k, nullptr, nullptr, status + item * nchunks,
-                                    errpos ? errpos + item * nchunks : nullptr, wk, &ab, rho, nullptr, listed,
-                                    gao_batch_entry(item, 0, (uint32_t)nchunks));
-}
-// k: the caller's dimension
-template <class P, int L>
-__global__ __launch_bounds__(GAO_THREADS) void gao_stage1_parties_kernel(
-    const GaoConsts<Fp<P>> c, const GaoAbsentLoad<Fp<P>> ab, const GaoAbsent<Fp<P>>* __restrict__ tab,
-    const Fp<P>* __restrict__ shares, size_t nchunks, int k, int rho, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
+// BATCH: the scan of item blockIdx.y -- its matrix, its rows of status and errpos, its summary words; the count and the list
+// are the batch's.  A flag the instance does not have hands the body the constant its form always had.
+// The arguments are GaoArgs' members as PLAIN parameters, not the struct: a struct that holds pointers is passed as one value
+// and loaded whole where the kernel begins, constants and load table included, while a parameter of its own is read where it
+// is used (c, ab, rg) or re-read in place of a spill.  Taking the struct, the l = 8 scans spilled 44 to 88 scalar registers
+// (10 and 2 this way) and the l = 8 ER SCAN RANGE instance lost a wave per SIMD over one AGPR; a parameter an instance does
+// not name is never loaded and costs nothing.
+template <class P, int L, bool ER, bool SCAN, bool RANGE, bool BATCH>
+__global__ __launch_bounds__(GAO_THREADS) void gao_stage1_kernel(
+    const GaoConsts<Fp<P>> c, const std::conditional_t<ER, GaoAbsentLoad<Fp<P>>, GaoNone> abv,
+    const GaoAbsent<Fp<P>>* __restrict__ tab, const Fp<P>* __restrict__ shares, size_t item_stride, size_t nchunks_,
+    const GaoRangeDev rg, int k, int rho, uint32_t listed, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
     uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage1_body<P, L, true>(c, shares, nchunks, k, secrets, message, status, errpos, wk, &ab, rho, tab);
+  static_assert(!BATCH || (SCAN && !RANGE), "a batch is a repair of whole words");
+  size_t nchunks;
+  if constexpr (RANGE) nchunks = rg.cnt;
+  else nchunks = nchunks_;
+  uint32_t entry0 = 0;
+  if constexpr (BATCH) {
+    const uint32_t item = blockIdx.y;
+    wk.summary += (size_t)item * (3 + 4 * L);
+    shares += item * item_stride, status += item * nchunks, errpos = errpos ? errpos + item * nchunks : nullptr;
+    entry0 = gao_batch_entry(item, 0, (uint32_t)nchunks);
+  }
+  const GaoAbsentLoad<Fp<P>>* ab = nullptr;
+  if constexpr (ER) ab = &abv;
+  gao_stage1_body<P, L, ER, SCAN, RANGE>(c, shares, nchunks, k, SCAN ? nullptr : secrets, SCAN ? nullptr : message, status,
+                                         errpos, wk, ab, ER ? rho : 0, ER && !SCAN ? tab : nullptr, ER && SCAN ? listed : 0u,
+                                         entry0, RANGE ? rg : GaoRangeDev{});
 }
 
 // ---------------------------------------------------------------- stage 2
@@ -344,352 +336,112 @@ __device__ __forceinline__ void gao_stage2_body(const GaoConsts<Fp<P>>& c, int n
   if (n_status2) atomicAdd(wk.summary + 2, (unsigned long long)n_status2);
   if (n_fixed) atomicAdd(wk.summary + 3 + p, (unsigned long long)n_fixed);
 }
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_stage2_kernel(const GaoConsts<Fp<P>> c, int n, int l,
-                                                                const Fp<P>* __restrict__ shares, size_t nchunks, int k,
-                                                                Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message,
-                                                                uint8_t* __restrict__ status, uint32_t* __restrict__ errpos,
-                                                                GaoWork wk) {
-  gao_stage2_body<P, false>(c, n, l, shares, nchunks, k, secrets, message, status, errpos, wk, nullptr);
+template <class P, bool ER, bool REPAIR, bool BATCH, bool RANGE>
+__global__ __launch_bounds__(GAO_THREADS) void gao_stage2_kernel(const GaoArgs<P, ER> a) {
+  size_t nchunks;
+  if constexpr (RANGE) nchunks = a.rg.cnt;
+  else nchunks = a.nchunks;
+  gao_stage2_body<P, ER, REPAIR, BATCH, RANGE>(a.c, a.n, a.l, a.shares, nchunks, a.k, REPAIR ? nullptr : a.secrets,
+                                               REPAIR ? nullptr : a.message, a.status, a.errpos, a.wk, ER ? a.tab : nullptr,
+                                               ER && REPAIR ? a.ilam : nullptr, BATCH ? a.item_stride : 0,
+                                               RANGE ? a.rg : GaoRangeDev{});
 }
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_repair_kernel(const GaoConsts<Fp<P>> c, int n, int l, Fp<P>* shares,
-                                                                size_t nchunks, int k, uint8_t* __restrict__ status,
-                                                                uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage2_body<P, false, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr);
-}
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_repair_batch_kernel(const GaoConsts<Fp<P>> c, int n, int l, Fp<P>* shares,
-                                                                      size_t item_stride, size_t nchunks, int k,
-                                                                      uint8_t* __restrict__ status,
-                                                                      uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage2_body<P, false, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, nullptr, nullptr,
-                                        item_stride);
-}
-// the range forms of gao_repair_kernel and gao_repair_parties_kernel
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_repair_range_kernel(const GaoConsts<Fp<P>> c, int n, int l, Fp<P>* shares,
-                                                                      GaoRangeDev rg, int k, uint8_t* __restrict__ status,
-                                                                      uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage2_body<P, false, true, false, true>(c, n, l, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, nullptr, nullptr,
-                                               0, rg);
-}
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_repair_parties_range_kernel(
-    const GaoConsts<Fp<P>> c, const GaoAbsent<Fp<P>>* __restrict__ tab, const Fp<P>* __restrict__ ilam, int n, int l,
-    Fp<P>* shares, GaoRangeDev rg, int k, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage2_body<P, true, true, false, true>(c, n, l, shares, rg.cnt, k, nullptr, nullptr, status, errpos, wk, tab, ilam, 0, rg);
-}
-// k: the caller's dimension
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_stage2_parties_kernel(
-    const GaoConsts<Fp<P>> c, const GaoAbsent<Fp<P>>* __restrict__ tab, int n, int l, const Fp<P>* __restrict__ shares,
-    size_t nchunks, int k, Fp<P>* __restrict__ secrets, Fp<P>* __restrict__ message, uint8_t* __restrict__ status,
-    uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage2_body<P, true>(c, n, l, shares, nchunks, k, secrets, message, status, errpos, wk, tab);
-}
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_repair_parties_kernel(const GaoConsts<Fp<P>> c,
-                                                                        const GaoAbsent<Fp<P>>* __restrict__ tab,
-                                                                        const Fp<P>* __restrict__ ilam, int n, int l,
-                                                                        Fp<P>* shares, size_t nchunks, int k,
-                                                                        uint8_t* __restrict__ status,
-                                                                        uint32_t* __restrict__ errpos, GaoWork wk) {
-  gao_stage2_body<P, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, tab, ilam);
-}
-template <class P>
-__global__ __launch_bounds__(GAO_THREADS) void gao_repair_batch_parties_kernel(
-    const GaoConsts<Fp<P>> c, const GaoAbsent<Fp<P>>* __restrict__ tab, const Fp<P>* __restrict__ ilam, int n, int l,
-    Fp<P>* shares, size_t item_stride, size_t nchunks, int k, uint8_t* __restrict__ status, uint32_t* __restrict__ errpos,
-    GaoWork wk) {
-  gao_stage2_body<P, true, true, true>(c, n, l, shares, nchunks, k, nullptr, nullptr, status, errpos, wk, tab, ilam, item_stride);
-}
-// the table of a call, from the launch's arguments to working memory: one word per lane
-template <class F>
-__global__ __launch_bounds__(GAO_THREADS) void gao_absent_table_kernel(const GaoAbsent<F> a, GaoAbsent<F>* __restrict__ out) {
-  static_assert(sizeof(GaoAbsent<F>) % 4 == 0, "words");
+// a table of a call (GaoAbsent, GaoInvLambda), from the launch's arguments to working memory: one word per lane
+template <class T>
+__global__ __launch_bounds__(GAO_THREADS) void gao_table_kernel(const T a, T* __restrict__ out) {
+  static_assert(sizeof(T) % 4 == 0, "words");
   const uint32_t* src = (const uint32_t*)&a;
   uint32_t* dst = (uint32_t*)out;
-  for (uint32_t i = threadIdx.x; i < sizeof(GaoAbsent<F>) / 4; i += blockDim.x) dst[i] = src[i];
+  for (uint32_t i = threadIdx.x; i < sizeof(T) / 4; i += blockDim.x) dst[i] = src[i];
 }
 
-// the same for the inverses of a repair with a party list
-template <class F>
-__global__ __launch_bounds__(GAO_THREADS) void gao_inv_lambda_table_kernel(const GaoInvLambda<F> a, GaoInvLambda<F>* __restrict__ out) {
-  static_assert(sizeof(GaoInvLambda<F>) % 4 == 0, "words");
-  const uint32_t* src = (const uint32_t*)&a;
-  uint32_t* dst = (uint32_t*)out;
-  for (uint32_t i = threadIdx.x; i < sizeof(GaoInvLambda<F>) / 4; i += blockDim.x) dst[i] = src[i];
-}
-
-// ---------------------------------------------------------------- host driver
+// ---------------------------------------------------------------- the host driver
 #define GAO_HIP(expr)                                    \
   do {                                                   \
     hipError_t _e = (expr);                              \
     if (_e != hipSuccess) return e->hip_fail(_e, #expr); \
   } while (0)
 
-// REPAIR: zk_pss_repair -- the scan in place of stage 1, the repair form of stage 2, `shares` written
-template <class FrP, bool REPAIR>
-int gao_all_parties_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPAIR, void*, const void*> shares, size_t nchunks,
-                        int dimension, void* secrets, void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary,
-                        hipStream_t st, const GaoRange* rg = nullptr) {
+// fn(integral_constant<int, L>) for the packing factor l: the one place a run-time l becomes the kernels' L
+template <class Fn>
+int gao_with_l(IEngine* e, int l, Fn fn) {
+  switch (l) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 8: return fn(std::integral_constant<int, 8>{});
+    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
+  }
+}
+
+// A call that passed gao_call_check, with (ER) or without absent parties: one clear, with ER the table launches, stage 1 with
+// the item on grid.y, stage 2 over the one list.  ids: the list as gao_list_check wrote it.
+template <class FrP, bool REPAIR, bool ER>
+int gao_launch(IEngine* e, void* wkp, int l, const GaoCall& call, const uint32_t* ids, hipStream_t st) {
   using Fr = Fp<FrP>;
   const int n = 4 * l;
-  if (dimension < 1 || dimension > n - 1) return e->fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
-  if (rg && !REPAIR) return e->fail(ZK_ERR_BAD_INPUT, "the range form is a repair");
-  if (nchunks == 0) return ZK_OK;
-  if (!shares || !status) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
-  if (nchunks >= ((size_t)1 << 32)) return e->fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
-  constexpr size_t head = 320;                                       // the count, then the summary words from byte 32 on
-  static_assert(32 + (3 + GAO_MAX_N) * 8 <= head && head % 32 == 0, "layout");
-  GAO_HIP(wkbuf.ensure(head + nchunks * 4));
-  GaoWork wk;
-  wk.count = (uint32_t*)wkbuf.p;
-  wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkbuf.p + 32);
-  wk.list = (uint32_t*)((char*)wkbuf.p + head);
-  GAO_HIP(hipMemsetAsync(wkbuf.p, 0, head, st));
-  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)(3 + n) * 8, st));
-  const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
-  const size_t per_wg = GAO_THREADS / gao_split(l);                  // chunks per workgroup of stage 1
-  const dim3 blk(GAO_THREADS), grid1((unsigned)((nchunks + per_wg - 1) / per_wg));
-  std::conditional_t<REPAIR, Fr*, const Fr*> sh = (decltype(sh))shares;
-  Fr* sec = (Fr*)secrets;
-  Fr* msg = (Fr*)message;
-  if constexpr (REPAIR) {
-    if (rg) {      // the word in a block with padding: nchunks is rg->cnt (gao_repair_range_run)
-      const GaoRangeDev rd = gao_range_dev(*rg);
-      switch (l) {
-        case 1: gao_scan_range_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
-        case 2: gao_scan_range_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
-        case 4: gao_scan_range_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
-        case 8: gao_scan_range_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, sh, rd, dimension, status, errpos, wk); break;
-        default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
-      }
-      const size_t gpb_r = GAO_THREADS / n;
-      const dim3 grid_r((unsigned)std::min<size_t>((nchunks + gpb_r - 1) / gpb_r, GAO_STAGE2_GRID));
-      gao_repair_range_kernel<FrP><<<grid_r, blk, 0, st>>>(c, n, l, sh, rd, dimension, status, errpos, wk);
-      GAO_HIP(hipGetLastError());
-      return ZK_OK;
+  const size_t nchunks = call.nchunks, nitems = (size_t)call.nitems;
+  const GaoLayout lay = gao_layout<Fr>(n, call.nitems, nchunks, ER, REPAIR);
+  char* const wk = (char*)wkp;
+  GaoArgs<FrP, ER> a{};
+  a.c = gao_make_consts<FrP>(l);
+  a.n = n, a.l = l, a.k = call.dimension;
+  a.shares = (Fr*)call.shares, a.item_stride = call.item_stride, a.nchunks = nchunks;
+  if (call.range) a.rg = gao_range_dev(*call.range);
+  a.secrets = (Fr*)call.secrets, a.message = (Fr*)call.message, a.status = call.status, a.errpos = call.errpos;
+  a.wk.count = (uint32_t*)wk;
+  a.wk.summary = call.summary ? (unsigned long long*)call.summary : (unsigned long long*)(wk + 32);
+  a.wk.list = (uint32_t*)(wk + lay.list);
+  GAO_HIP(hipMemsetAsync(wk, 0, lay.tab, st));
+  if (call.summary) GAO_HIP(hipMemsetAsync(call.summary, 0, nitems * (3 + n) * 8, st));
+  const dim3 blk(GAO_THREADS);
+  if constexpr (ER) {
+    using Tab = GaoAbsent<Fr>;
+    static_assert(sizeof(Tab) + 80 <= 4096 && sizeof(a) <= 4096, "the table and the arguments travel as kernel arguments");
+    const Tab t = gao_make_absent<FrP>(a.c, l, ids, call.np, call.dimension);
+    a.ab = t.ld, a.rho = t.rho, a.listed = t.listed, a.tab = (Tab*)(wk + lay.tab);
+    gao_table_kernel<Tab><<<dim3(1), blk, 0, st>>>(t, (Tab*)(wk + lay.tab));
+    if constexpr (REPAIR) {
+      GaoInvLambda<Fr>* inv = (GaoInvLambda<Fr>*)(wk + lay.inv);
+      a.ilam = inv->v;
+      gao_table_kernel<GaoInvLambda<Fr>><<<dim3(1), blk, 0, st>>>(gao_make_inv_lambda<FrP>(t), inv);
     }
   }
-  if constexpr (REPAIR) switch (l) {
-    case 1: gao_scan_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
-    case 2: gao_scan_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
-    case 4: gao_scan_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
-    case 8: gao_scan_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, status, errpos, wk); break;
-    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
-  }
-  else switch (l) {
-    case 1: gao_stage1_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, sec, msg, status, errpos, wk); break;
-    case 2: gao_stage1_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, sec, msg, status, errpos, wk); break;
-    case 4: gao_stage1_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, sec, msg, status, errpos, wk); break;
-    case 8: gao_stage1_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, sh, nchunks, dimension, sec, msg, status, errpos, wk); break;
-    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
-  }
-  const size_t gpb = GAO_THREADS / n;
-  const dim3 grid2((unsigned)std::min<size_t>((nchunks + gpb - 1) / gpb, GAO_STAGE2_GRID));
-  if constexpr (REPAIR) gao_repair_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, nchunks, dimension, status, errpos, wk);
-  else gao_stage2_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, nchunks, dimension, sec, msg, status, errpos, wk);
-  GAO_HIP(hipGetLastError());
-  return ZK_OK;
-}
-template <class FrP>
-int gao_unpack_robust_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, size_t nchunks, int dimension, void* secrets,
-                          void* message, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
-  return gao_all_parties_run<FrP, false>(e, wkbuf, l, shares, nchunks, dimension, secrets, message, status, errpos, summary, st);
-}
-template <class FrP>
-int gao_repair_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, size_t nchunks, int dimension, uint8_t* status,
-                   uint32_t* errpos, uint64_t* summary, hipStream_t st) {
-  return gao_all_parties_run<FrP, true>(e, wkbuf, l, shares, nchunks, dimension, nullptr, nullptr, status, errpos, summary, st);
-}
-// zk_pss_repair_batch: one clear, one scan with the item on grid.y, one repair launch over the one list of all items
-template <class FrP>
-int gao_repair_batch_run(IEngine* e, void* wkp, int l, void* shares, size_t item_stride, int nitems, size_t nchunks,
-                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
-  using Fr = Fp<FrP>;
-  const int n = 4 * l;
-  const size_t head = gao_batch_head(n, nitems);
-  GaoWork wk;
-  wk.count = (uint32_t*)wkp;
-  wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkp + 32);
-  wk.list = (uint32_t*)((char*)wkp + head);
-  GAO_HIP(hipMemsetAsync(wkp, 0, head, st));
-  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)nitems * (3 + n) * 8, st));
-  const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
-  const size_t per_wg = GAO_THREADS / gao_split(l);
-  const dim3 blk(GAO_THREADS), grid1((unsigned)((nchunks + per_wg - 1) / per_wg), (unsigned)nitems);
-  Fr* sh = (Fr*)shares;
-  switch (l) {
-    case 1: gao_scan_batch_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
-    case 2: gao_scan_batch_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
-    case 4: gao_scan_batch_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
-    case 8: gao_scan_batch_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, sh, item_stride, nchunks, dimension, status, errpos, wk); break;
-    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
-  }
-  const size_t gpb = GAO_THREADS / n, total = (size_t)nitems * nchunks;
-  const dim3 grid2((unsigned)std::min<size_t>((total + gpb - 1) / gpb, GAO_STAGE2_GRID));
-  gao_repair_batch_kernel<FrP><<<grid2, blk, 0, st>>>(c, n, l, sh, item_stride, nchunks, dimension, status, errpos, wk);
-  GAO_HIP(hipGetLastError());
-  return ZK_OK;
-}
-// zk_pss_repair_batch_parties: the launches of the batch above with the two tables of the party list put into working memory
-// ahead of them, once per call: one clear, GaoAbsent, GaoInvLambda, one scan with the item on grid.y, one repair launch over
-// the one list.  ids: np ascending party ids below n, dimension < np < n (the caller's checks; np == n is the batch above).
-template <class FrP>
-int gao_repair_batch_parties_run(IEngine* e, void* wkp, int l, void* shares, const uint32_t* ids, int np, size_t item_stride,
-                                 int nitems, size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos,
-                                 uint64_t* summary, hipStream_t st) {
-  using Fr = Fp<FrP>;
-  using Tab = GaoAbsent<Fr>;
-  const int n = 4 * l;
-  static_assert(sizeof(Tab) + 80 <= 4096, "the table travels as a kernel argument");
-  const GaoBatchPartiesWork lay = gao_batch_parties_work<Fr>(n, nitems, nchunks);
-  GaoWork wk;
-  wk.count = (uint32_t*)wkp;
-  wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkp + 32);
-  wk.list = (uint32_t*)((char*)wkp + lay.list);
-  Tab* tab = (Tab*)((char*)wkp + lay.tab);
-  GaoInvLambda<Fr>* inv = (GaoInvLambda<Fr>*)((char*)wkp + lay.inv);
-  GAO_HIP(hipMemsetAsync(wkp, 0, lay.tab, st));
-  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)nitems * (3 + n) * 8, st));
-  const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
-  const Tab a = gao_make_absent<FrP>(c, l, ids, np, dimension);
-  const dim3 blk(GAO_THREADS);
-  gao_absent_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(a, tab);
-  gao_inv_lambda_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(gao_make_inv_lambda<FrP>(a), inv);
-  const size_t per_wg = GAO_THREADS / gao_split(l);
+  const size_t per_wg = GAO_THREADS / gao_split(l), gpb = GAO_THREADS / n;      // chunks per workgroup of stage 1, of stage 2
   const dim3 grid1((unsigned)((nchunks + per_wg - 1) / per_wg), (unsigned)nitems);
-  Fr* sh = (Fr*)shares;
-  const int k = dimension, rho = a.rho;
-  switch (l) {
-    case 1: gao_scan_batch_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
-    case 2: gao_scan_batch_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
-    case 4: gao_scan_batch_parties_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
-    case 8: gao_scan_batch_parties_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, sh, item_stride, nchunks, k, rho, a.listed, status, errpos, wk); break;
-    default: return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
-  }
-  const size_t gpb = GAO_THREADS / n, total = (size_t)nitems * nchunks;
-  const dim3 grid2((unsigned)std::min<size_t>((total + gpb - 1) / gpb, GAO_STAGE2_GRID));
-  gao_repair_batch_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, inv->v, n, l, sh, item_stride, nchunks, k, status, errpos, wk);
-  GAO_HIP(hipGetLastError());
-  return ZK_OK;
-}
-// With all n parties listed this is the call above; otherwise the kernels' forms for absent parties, with the table of the
-// party list (gao_make_absent, host) put into working memory by a launch of its own ahead of them.
-// REPAIR: zk_pss_repair_parties -- the scan in place of stage 1, the repair form of stage 2, `shares` written; the inverses
-// 1 / Lambda(w^p) go into a second table behind the first, by a launch of their own.
-template <class FrP, bool REPAIR>
-int gao_party_list_run(IEngine* e, DevBuf& wkbuf, int l, std::conditional_t<REPAIR, void*, const void*> shares,
-                       const uint32_t* parties, int np, size_t nchunks, int dimension, void* secrets, void* message,
-                       uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st, const GaoRange* rg = nullptr) {
-  using Fr = Fp<FrP>;
-  const int n = 4 * l;
-  if (l != 1 && l != 2 && l != 4 && l != 8) return e->fail(ZK_ERR_BAD_INPUT, "packing factor l must be 1, 2, 4 or 8");
-  if (np <= 0 || np > n) return e->fail(ZK_ERR_BAD_INPUT, "bad party count");
-  if (rg && !REPAIR) return e->fail(ZK_ERR_BAD_INPUT, "the range form is a repair");
-  uint32_t ids[GAO_MAX_N];
-  for (int i = 0; i < np; i++) {
-    ids[i] = parties ? parties[i] : (uint32_t)i;
-    if (ids[i] >= (uint32_t)n || (i > 0 && ids[i] <= ids[i - 1]))
-      return e->fail(ZK_ERR_BAD_INPUT, "party ids must be ascending and < n");
-  }
-  if (dimension < 1 || dimension > n - 1) return e->fail(ZK_ERR_BAD_INPUT, "dimension must lie in 1 .. n - 1");
-  if (np <= dimension) return e->fail(ZK_ERR_PROTOCOL, "Not enough shares to reconstruct");      // pss.rs:183-186
-  if (np == n)
-    return gao_all_parties_run<FrP, REPAIR>(e, wkbuf, l, shares, nchunks, dimension, secrets, message, status, errpos, summary,
-                                            st, rg);
-  if (nchunks == 0) return ZK_OK;
-  if (!shares || !status) return e->fail(ZK_ERR_BAD_INPUT, "null pointer");
-  if (nchunks >= ((size_t)1 << 32)) return e->fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks");
-  using Tab = GaoAbsent<Fr>;
-  constexpr size_t head = 320, tab_bytes = (sizeof(Tab) + 31) / 32 * 32;      // count, summary words, then the table
-  static_assert(sizeof(Tab) + 64 <= 4096, "the table travels as a kernel argument");
-  constexpr size_t inv_bytes = REPAIR ? sizeof(GaoInvLambda<Fr>) : 0;
-  static_assert(inv_bytes % 32 == 0, "the list stays aligned");
-  GAO_HIP(wkbuf.ensure(head + tab_bytes + inv_bytes + nchunks * 4));
-  GaoWork wk;
-  wk.count = (uint32_t*)wkbuf.p;
-  wk.summary = summary ? (unsigned long long*)summary : (unsigned long long*)((char*)wkbuf.p + 32);
-  wk.list = (uint32_t*)((char*)wkbuf.p + head + tab_bytes + inv_bytes);
-  Tab* tab = (Tab*)((char*)wkbuf.p + head);
-  GAO_HIP(hipMemsetAsync(wkbuf.p, 0, head, st));
-  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)(3 + n) * 8, st));
-  const GaoConsts<Fr> c = gao_make_consts<FrP>(l);
-  const Tab a = gao_make_absent<FrP>(c, l, ids, np, dimension);
-  const dim3 blk(GAO_THREADS);
-  gao_absent_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(a, tab);
-  [[maybe_unused]] GaoInvLambda<Fr>* inv = (GaoInvLambda<Fr>*)((char*)wkbuf.p + head + tab_bytes);
-  if constexpr (REPAIR) gao_inv_lambda_table_kernel<Fr><<<dim3(1), blk, 0, st>>>(gao_make_inv_lambda<FrP>(a), inv);
-  const size_t per_wg = GAO_THREADS / gao_split(l);
-  const dim3 grid1((unsigned)((nchunks + per_wg - 1) / per_wg));
-  std::conditional_t<REPAIR, Fr*, const Fr*> sh = (decltype(sh))shares;
-  Fr* sec = (Fr*)secrets;
-  Fr* msg = (Fr*)message;
-  const int k = dimension, rho = a.rho;
+  const dim3 grid2((unsigned)std::min<size_t>((nitems * nchunks + gpb - 1) / gpb, GAO_STAGE2_GRID));
+  // the kernels of one form: exactly the forms of the table at the head of this file are instantiated
+  auto form = [&](auto range_, auto batch_) {
+    constexpr bool RANGE = decltype(range_)::value, BATCH = decltype(batch_)::value;
+    int rc = gao_with_l(e, l, [&](auto l_) {
+      gao_stage1_kernel<FrP, decltype(l_)::value, ER, REPAIR, RANGE, BATCH><<<grid1, blk, 0, st>>>(
+          a.c, a.ab, a.tab, a.shares, a.item_stride, a.nchunks, a.rg, a.k, a.rho, a.listed, a.secrets, a.message, a.status,
+          a.errpos, a.wk);
+      return (int)ZK_OK;
+    });
+    if (rc) return rc;
+    gao_stage2_kernel<FrP, ER, REPAIR, BATCH, RANGE><<<grid2, blk, 0, st>>>(a);
+    GAO_HIP(hipGetLastError());
+    return (int)ZK_OK;
+  };
   if constexpr (REPAIR) {
-    if (rg) {      // the word in a block with padding: nchunks is rg->cnt (gao_repair_range_run)
-      const GaoRangeDev rd = gao_range_dev(*rg);
-      switch (l) {
-        case 1: gao_scan_parties_range_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
-        case 2: gao_scan_parties_range_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
-        case 4: gao_scan_parties_range_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
-        default: gao_scan_parties_range_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, sh, rd, k, rho, a.listed, status, errpos, wk); break;
-      }
-      const size_t gpb_r = GAO_THREADS / n;
-      const dim3 grid_r((unsigned)std::min<size_t>((nchunks + gpb_r - 1) / gpb_r, GAO_STAGE2_GRID));
-      gao_repair_parties_range_kernel<FrP><<<grid_r, blk, 0, st>>>(c, tab, inv->v, n, l, sh, rd, k, status, errpos, wk);
-      GAO_HIP(hipGetLastError());
-      return ZK_OK;
-    }
+    if (call.range) return form(std::true_type{}, std::false_type{});
+    if (call.batch()) return form(std::false_type{}, std::true_type{});
   }
-  if constexpr (REPAIR) switch (l) {
-    case 1: gao_scan_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
-    case 2: gao_scan_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
-    case 4: gao_scan_parties_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
-    default: gao_scan_parties_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, sh, nchunks, k, rho, a.listed, status, errpos, wk); break;
+  return form(std::false_type{}, std::false_type{});
+}
+
+template <class FrP, bool REPAIR>
+int gao_run(IEngine* e, void* wk, int l, const GaoCall& call, hipStream_t st) {
+  uint32_t ids[GAO_MAX_N];
+  const GaoRefusal r = gao_call_check(l, call, REPAIR, ids);
+  if (r.code) return e->fail(r.code, r.msg);
+  if (call.nchunks == 0) {
+    if (call.range && call.summary) GAO_HIP(hipMemsetAsync(call.summary, 0, (size_t)(3 + 4 * l) * 8, st));
+    return ZK_OK;
   }
-  else switch (l) {
-    case 1: gao_stage1_parties_kernel<FrP, 1><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
-    case 2: gao_stage1_parties_kernel<FrP, 2><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
-    case 4: gao_stage1_parties_kernel<FrP, 4><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
-    default: gao_stage1_parties_kernel<FrP, 8><<<grid1, blk, 0, st>>>(c, a.ld, tab, sh, nchunks, k, rho, sec, msg, status, errpos, wk); break;
-  }
-  const size_t gpb = GAO_THREADS / n;
-  const dim3 grid2((unsigned)std::min<size_t>((nchunks + gpb - 1) / gpb, GAO_STAGE2_GRID));
-  if constexpr (REPAIR) gao_repair_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, inv->v, n, l, sh, nchunks, k, status, errpos, wk);
-  else gao_stage2_parties_kernel<FrP><<<grid2, blk, 0, st>>>(c, tab, n, l, sh, nchunks, k, sec, msg, status, errpos, wk);
-  GAO_HIP(hipGetLastError());
-  return ZK_OK;
-}
-template <class FrP>
-int gao_unpack_robust_parties_run(IEngine* e, DevBuf& wkbuf, int l, const void* shares, const uint32_t* parties, int np,
-                                  size_t nchunks, int dimension, void* secrets, void* message, uint8_t* status,
-                                  uint32_t* errpos, uint64_t* summary, hipStream_t st) {
-  return gao_party_list_run<FrP, false>(e, wkbuf, l, shares, parties, np, nchunks, dimension, secrets, message, status, errpos,
-                                        summary, st);
-}
-template <class FrP>
-int gao_repair_parties_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, const uint32_t* parties, int np, size_t nchunks,
-                           int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
-  return gao_party_list_run<FrP, true>(e, wkbuf, l, shares, parties, np, nchunks, dimension, nullptr, nullptr, status, errpos,
-                                       summary, st);
-}
-// The range form of zk_pss_repair_parties (gao.hpp): the word's rg.cnt valid columns lie in rows rg.stride elements apart,
-// column c is chunk rg.chunk(c) of a word of rg.len chunks -- status and errpos [rg.len] are written there.  The list,
-// dimension and summary are gao_repair_parties_run's; with no valid column only the summary is cleared.
-template <class FrP>
-int gao_repair_range_run(IEngine* e, DevBuf& wkbuf, int l, void* shares, const uint32_t* parties, int np, const GaoRange& rg,
-                         int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) {
-  if (rg.cnt > rg.stride || rg.cnt > rg.len || rg.base >= (rg.len ? rg.len : 1) || rg.shift > rg.len ||
-      rg.stride > 0xffffffffull)
-    return e->fail(ZK_ERR_BAD_INPUT, "bad range: cnt <= stride < 2^32, cnt <= len, base < len, shift <= len");
-  int rc = gao_party_list_run<FrP, true>(e, wkbuf, l, shares, parties, np, rg.cnt, dimension, nullptr, nullptr, status, errpos,
-                                         summary, st, &rg);
-  if (rc || rg.cnt) return rc;
-  if (summary) GAO_HIP(hipMemsetAsync(summary, 0, (size_t)(3 + 4 * l) * 8, st));
-  return ZK_OK;
+  return call.np == 4 * l ? gao_launch<FrP, REPAIR, false>(e, wk, l, call, ids, st)
+                          : gao_launch<FrP, REPAIR, true>(e, wk, l, call, ids, st);
 }
 #undef GAO_HIP
 
