@@ -629,7 +629,8 @@ int zk_circom_h_checked(zk_ctx* ctx, const void* qap_a_d, const void* qap_b_d, c
  * COVERED: the seven king words of circom_h.  A party whose QAP shares or round-2 in-mask rows are wrong -- up to l of them
  * per chunk -- is named, and the proof is the honest proof.
  * NOT COVERED: the five d_msm rounds.  Their word has dimension 4l - 1, so checking them is detection only and costs a
- * second MSM each (zk_d_msm_checked); a caller who wants that calls it.  There is no async or batch form.
+ * second MSM each (zk_d_msm_checked); a caller who wants that calls it.  The async form is
+ * zk_groth16_prove_checked_async, the batch form zk_groth16_prove_checked_batch.
  * Errors: those of zk_groth16_prove, and a NULL status_d -> ZK_ERR_BAD_INPUT. */
 int zk_groth16_prove_checked(zk_ctx* ctx, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
                              const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
@@ -686,8 +687,9 @@ int zk_circom_h_checked_parties(zk_ctx* ctx, const uint32_t* parties /* host, as
  * They must still be readable memory, field rows must hold field elements and point rows curve points: the MSM may read
  * them under a zero coefficient.  The MSM rounds stay UNCHECKED as in zk_groth16_prove_checked: a wrong a_share / ax_share
  * row of a LISTED party still spoils the proof.  The list is read and refused as zk_circom_h_checked_parties reads it,
- * before anything is written; with nparties == n this is zk_groth16_prove_checked.  Synchronous; there is no async, batch
- * or zk_dist_* form, no list for point shares, and the absent party's share is not recovered.
+ * before anything is written; with nparties == n this is zk_groth16_prove_checked.  Synchronous (the async form is
+ * zk_groth16_prove_checked_parties_async); there is no batch or zk_dist_* form, no list for point shares, and the absent
+ * party's share is not recovered.
  * Errors: those of zk_groth16_prove_checked and of the list. */
 int zk_groth16_prove_checked_parties(zk_ctx* ctx, const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */,
                                      int nparties, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
@@ -695,6 +697,60 @@ int zk_groth16_prove_checked_parties(zk_ctx* ctx, const uint32_t* parties /* hos
                                      const void* s, int log2_m, const zk_groth16_masks* masks, uint64_t seed, void* pi_a,
                                      void* pi_b, void* pi_c, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d,
                                      void* stream);
+/* zk_circom_h_batch_checked: zk_circom_h_checked for nproofs (1..16) proofs as ONE launch chain -- what a proving service
+ * gets from the reference by running ext_wit.rs:104-181 once per concurrent dsha256 run (mpc-net/src/multi.rs:317-327), with
+ * every king word of every proof checked.  CONTRACT: proof b is zk_circom_h_checked with seed + 16 b -- the same seven words,
+ * dimensions (2l for items 0..5, 4l - 1 detection only for item 6) and verdicts; h_share_d is [nproofs][n][m/l].  The
+ * report is PROOF-MAJOR: status_d and errpos_d [nproofs][7][m/l], summary_d [nproofs][7][3 + n]; the slice of proof b holds
+ * what that single call writes, byte for byte, so one proof's report is handed out without reshuffling.  Pointer arrays are
+ * host arrays of device pointers; masks: nproofs entries or NULL.  A round of the whole batch is one word launch, ONE
+ * zk_pss_repair_batch of 3 nproofs items (48 at most: the item limit of that call) and one king launch; the report rows
+ * are gathered to their proof-major places by the last launch of the chain.  When the in-masks of a stage are not present
+ * or absent alike across the batch and a round's three words, the proofs run one by one: the same results.
+ * Errors (ZK_ERR_BAD_INPUT, nothing written): nproofs outside 1 .. 16, NULL pointers (arrays, entries, h_share_d,
+ * status_d), 3 nproofs m/l >= 2^32, and everything zk_circom_h_checked refuses.  A failed chunk is no error return.
+ * No host synchronisation.  Device engine only. */
+int zk_circom_h_batch_checked(zk_ctx* ctx, int nproofs, const void* const* qap_a_d, const void* const* qap_b_d,
+                              const void* const* qap_c_d, int log2_m, const zk_groth16_masks* masks, uint64_t seed,
+                              void* h_share_d /* [nproofs][n][m/l] */, uint8_t* status_d /* [nproofs][7][m/l] */,
+                              uint32_t* errpos_d /* [nproofs][7][m/l], or NULL */,
+                              uint64_t* summary_d /* [nproofs][7][3 + n], or NULL */, void* stream);
+/* Asynchronous forms of zk_groth16_prove_checked and zk_groth16_prove_checked_parties (what `tokio::spawn(dsha256(..))` is to
+ * the reference, mpc-net/src/multi.rs:317-327, with the kings' words checked): the arguments of the synchronous calls
+ * without the proof outputs; the handle is one of zk_groth16_prove_async's -- zk_groth16_wait joins it and writes the
+ * shares, zk_groth16_abort frees the slot, two proofs of either kind may be in flight.  The report buffers are complete when
+ * zk_groth16_wait returns.  `parties` is read before the call returns and may be freed or overwritten at once; every other
+ * input must stay valid until the join, as for zk_groth16_prove_async.  The synchronous calls are these followed by
+ * zk_groth16_wait. */
+int zk_groth16_prove_checked_async(zk_ctx* ctx, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
+                                   const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r,
+                                   const void* s, int log2_m, const zk_groth16_masks* masks, uint64_t seed, uint8_t* status_d,
+                                   uint32_t* errpos_d, uint64_t* summary_d, void* stream, int* handle);
+int zk_groth16_prove_checked_parties_async(zk_ctx* ctx, const uint32_t* parties /* host, ascending ids, NULL = 0..nparties-1 */,
+                                           int nparties, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
+                                           const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r,
+                                           const void* s, int log2_m, const zk_groth16_masks* masks, uint64_t seed,
+                                           uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream,
+                                           int* handle);
+/* zk_groth16_prove_checked_batch: zk_groth16_prove_batch (concurrent dsha256 runs, groth16/examples/sha256.rs:316-360) with
+ * h computed by the chain of zk_circom_h_batch_checked on the batch's own stream and work buffers; the report buffers
+ * (device) in that call's proof-major layout.  Proof b is the proof zk_groth16_prove_checked gives with seed + 16 b, as
+ * group elements.  The five d_msm rounds stay UNCHECKED as in the single call.  There is no party list for a batch.
+ * _async returns a handle of zk_groth16_prove_batch_async's space: zk_groth16_batch_wait joins it, after which the report
+ * is complete; checked and unchecked batches may be in flight together, three in all, each with its own scratch.
+ * Errors: those of zk_groth16_prove_batch, and a NULL status_d -> ZK_ERR_BAD_INPUT. */
+int zk_groth16_prove_checked_batch(zk_ctx* ctx, const zk_crs_share* crs, int nproofs, const void* const* qap_a_d,
+                                   const void* const* qap_b_d, const void* const* qap_c_d, const void* const* a_share_d,
+                                   const void* const* ax_share_d, const void* r, const void* s, int log2_m,
+                                   const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                                   uint8_t* status_d /* [nproofs][7][m/l] */, uint32_t* errpos_d /* or NULL */,
+                                   uint64_t* summary_d /* [nproofs][7][3 + n], or NULL */, void* stream);
+int zk_groth16_prove_checked_batch_async(zk_ctx* ctx, const zk_crs_share* crs, int nproofs, const void* const* qap_a_d,
+                                         const void* const* qap_b_d, const void* const* qap_c_d,
+                                         const void* const* a_share_d, const void* const* ax_share_d, const void* r,
+                                         const void* s, int log2_m, const zk_groth16_masks* masks, uint64_t seed,
+                                         uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream,
+                                         int* handle);
 int zk_fr_to_bytes(zk_ctx* ctx, const void* x_d, size_t len, void* bytes_out_d, void* stream);
 int zk_fr_from_bytes(zk_ctx* ctx, const void* bytes_d, size_t len, void* x_out_d, void* stream);
 /* Vectors of group elements in ark-serialize's COMPRESSED form (what CRS shares / MSM results look like on an mpc-net

@@ -41,6 +41,8 @@ SYMBOLS = [
     "zk_pss_repair_batch_parties", "zk_circom_h_checked_parties", "zk_groth16_prove_checked_parties",
     "zk_pss_repair_range", "zk_dist_d_fft_checked", "zk_dist_d_ifft_checked", "zk_dist_deg_red_checked",
     "zk_dist_circom_h_checked",
+    "zk_circom_h_batch_checked", "zk_groth16_prove_checked_async", "zk_groth16_prove_checked_parties_async",
+    "zk_groth16_prove_checked_batch", "zk_groth16_prove_checked_batch_async",
     "zk_pss_unpack_points_robust_parties", "zk_pss_repair_points_parties", "zk_groth16_reconstruct_robust",
     "zk_net_party", "zk_party_release", "zk_party_id", "zk_party_last_error", "zk_party_stats", "zk_party_d_fft",
     "zk_party_d_ifft", "zk_party_deg_red", "zk_party_d_pp", "zk_party_d_msm", "zk_party_circom_h", "zk_party_groth16_prove",
@@ -256,6 +258,16 @@ def load():
     lib.zk_circom_h_checked_parties.argtypes = [vp, ids, i32, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp]
     lib.zk_groth16_prove_checked_parties.argtypes = [vp, ids, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp,
                                                      vp, vp]
+    pv = C.POINTER(vp)
+    lib.zk_circom_h_batch_checked.argtypes = [vp, i32, pv, pv, pv, i32, vp, u64, vp, vp, vp, vp, vp]
+    lib.zk_groth16_prove_checked_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp, vp,
+                                                   C.POINTER(i32)]
+    lib.zk_groth16_prove_checked_parties_async.argtypes = [vp, ids, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, u64, vp, vp, vp,
+                                                           vp, C.POINTER(i32)]
+    lib.zk_groth16_prove_checked_batch.argtypes = [vp, vp, i32, pv, pv, pv, pv, pv, vp, vp, i32, vp, u64, vp, vp, vp, vp, vp, vp,
+                                                   vp]
+    lib.zk_groth16_prove_checked_batch_async.argtypes = [vp, vp, i32, pv, pv, pv, pv, pv, vp, vp, i32, vp, u64, vp, vp, vp, vp,
+                                                         C.POINTER(i32)]
     u32 = C.c_uint32
     lib.zk_pss_repair_range.argtypes = [vp, vp, ids, i32, sz, u32, u32, u32, u32, i32, vp, vp, vp, vp]
     lib.zk_net_party.argtypes = [vp, i32, C.POINTER(vp)]

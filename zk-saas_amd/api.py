@@ -469,6 +469,62 @@ def circom_h(pp, wit_or_bufs, masks=None, seed=0, check=False, log2_m=None, stre
     return h, rep
 
 
+def h_batch_reports(pp, nproofs, log2_m):
+    """the report buffers of zk_circom_h_batch_checked / zk_groth16_prove_checked_batch: status and errpos [nproofs][7][m/l],
+    summary [nproofs][7][3 + n], proof-major.  Returns (whole, reports): `whole` owns the buffers the call is given,
+    reports[b] is proof b's slice as windows into them, shaped exactly like h_report's."""
+    lc = (1 << log2_m) // pp.l
+    rows = H_ITEMS * lc
+    whole = pp._report(nproofs * rows, 2 * pp.l, words=nproofs * H_ITEMS)
+    whole.nitems = nproofs * H_ITEMS
+    reports = []
+    for b in range(nproofs):
+        r = RobustUnpack(pp, rows, 2 * pp.l)
+        r.status = whole.status.view(b * rows, rows)
+        r.errpos = whole.errpos.view(4 * b * rows, 4 * rows)
+        sw = 8 * (3 + pp.n) * H_ITEMS
+        r.summary_d = whole.summary_d.view(b * sw, sw)
+        r.nitems = H_ITEMS
+        reports.append(r)
+    return whole, reports
+
+
+def circom_h_batch_checked(pp, wits_or_bufs, masks=None, seed=0, log2_m=None, stream=None, errpos=True, summary=True):
+    """zk_circom_h_batch_checked: the checked h chain of len(wits_or_bufs) proofs (1..16) as one launch chain.  Each entry is a
+    Witness (`.qap`, `.log_m`) or three device buffers [n][m/l] with log2_m given; masks: one zk_groth16_masks (or an object
+    holding one as `.ct`) per proof, or None.  Proof b is circom_h(check=True) with seed + 16 b.  Returns (hs, reports):
+    hs[b] a window [n][m/l] into one buffer, reports[b] as h_report's (errpos=False / summary=False pass NULL for that
+    buffer: the slices are then not written)."""
+    nb = len(wits_or_bufs)
+    qaps = []
+    for w in wits_or_bufs:
+        if hasattr(w, "qap"):
+            qaps.append(w.qap)
+            log2_m = w.log_m
+        else:
+            qaps.append(list(w))
+    if log2_m is None or any(len(q) != 3 for q in qaps):
+        raise ValueError("three QAP share vectors per proof and log2_m")
+    if masks is not None and len(masks) != nb:
+        raise ValueError("one mask set per proof")
+    mk = None
+    if masks is not None:
+        ct = [getattr(m, "ct", m) for m in masks]
+        mk = (type(ct[0]) * nb)()
+        for b, m in enumerate(ct):
+            C.memmove(C.byref(mk, b * C.sizeof(m)), C.byref(m), C.sizeof(m))
+    per = pp.n * ((1 << log2_m) // pp.l)
+    h = pp.alloc_fr(max(1, nb) * per)
+    whole, reports = h_batch_reports(pp, max(1, nb), log2_m)
+    arr = lambda k: (C.c_void_p * max(1, nb))(*[_ptr(q[k]) for q in qaps])
+    pp._check(pp.lib.zk_circom_h_batch_checked(pp.h, nb, arr(0), arr(1), arr(2), log2_m,
+                                               None if mk is None else C.cast(mk, C.c_void_p), seed, h.ptr, _ptr(whole.status),
+                                               _ptr(whole.errpos) if errpos else None,
+                                               _ptr(whole.summary_d) if summary else None, stream))
+    esz = h.nbytes // (max(1, nb) * per)
+    return [h.view(b * per * esz, per * esz) for b in range(nb)], reports
+
+
 def deal_masks(pp, nproofs, log2_m, g1_gen_affine, g2_gen_affine, seed, masks_ct, stream=None):
     """zk_groth16_deal_masks: fills the destination buffers named by `masks_ct` (a ctypes array of nproofs
     zk_groth16_masks, or one struct when nproofs == 1) with the twelve masks of every proof; proof b is dealt what the

@@ -1211,6 +1211,49 @@ int zk_groth16_prove_checked_parties(zk_ctx* ctx, const uint32_t* parties, int n
   return e->groth16_prove_checked_parties(parties, nparties, crs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m,
                                           masks, seed, pi_a, pi_b, pi_c, status_d, errpos_d, summary_d, S(stream));
 }
+int zk_circom_h_batch_checked(zk_ctx* ctx, int nproofs, const void* const* qap_a_d, const void* const* qap_b_d,
+                              const void* const* qap_c_d, int log2_m, const zk_groth16_masks* masks, uint64_t seed,
+                              void* h_share_d, uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->circom_h_batch_checked(nproofs, qap_a_d, qap_b_d, qap_c_d, log2_m, masks, seed, h_share_d, status_d, errpos_d,
+                                   summary_d, S(stream));
+}
+int zk_groth16_prove_checked_async(zk_ctx* ctx, const zk_crs_share* crs, const void* qap_a_d, const void* qap_b_d,
+                                   const void* qap_c_d, const void* a_share_d, const void* ax_share_d, const void* r,
+                                   const void* s, int log2_m, const zk_groth16_masks* masks, uint64_t seed, uint8_t* status_d,
+                                   uint32_t* errpos_d, uint64_t* summary_d, void* stream, int* handle) {
+  CTX_OR_FAIL();
+  return e->groth16_prove_checked_async(crs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m, masks, seed,
+                                        status_d, errpos_d, summary_d, S(stream), handle);
+}
+int zk_groth16_prove_checked_parties_async(zk_ctx* ctx, const uint32_t* parties, int nparties, const zk_crs_share* crs,
+                                           const void* qap_a_d, const void* qap_b_d, const void* qap_c_d,
+                                           const void* a_share_d, const void* ax_share_d, const void* r, const void* s,
+                                           int log2_m, const zk_groth16_masks* masks, uint64_t seed, uint8_t* status_d,
+                                           uint32_t* errpos_d, uint64_t* summary_d, void* stream, int* handle) {
+  CTX_OR_FAIL();
+  return e->groth16_prove_checked_parties_async(parties, nparties, crs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s,
+                                                log2_m, masks, seed, status_d, errpos_d, summary_d, S(stream), handle);
+}
+int zk_groth16_prove_checked_batch(zk_ctx* ctx, const zk_crs_share* crs, int nproofs, const void* const* qap_a_d,
+                                   const void* const* qap_b_d, const void* const* qap_c_d, const void* const* a_share_d,
+                                   const void* const* ax_share_d, const void* r, const void* s, int log2_m,
+                                   const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
+                                   uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream) {
+  CTX_OR_FAIL();
+  return e->groth16_prove_checked_batch(crs, nproofs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m, masks,
+                                        seed, pi_a, pi_b, pi_c, status_d, errpos_d, summary_d, S(stream));
+}
+int zk_groth16_prove_checked_batch_async(zk_ctx* ctx, const zk_crs_share* crs, int nproofs, const void* const* qap_a_d,
+                                         const void* const* qap_b_d, const void* const* qap_c_d,
+                                         const void* const* a_share_d, const void* const* ax_share_d, const void* r,
+                                         const void* s, int log2_m, const zk_groth16_masks* masks, uint64_t seed,
+                                         uint8_t* status_d, uint32_t* errpos_d, uint64_t* summary_d, void* stream,
+                                         int* handle) {
+  CTX_OR_FAIL();
+  return e->groth16_prove_checked_batch_async(crs, nproofs, qap_a_d, qap_b_d, qap_c_d, a_share_d, ax_share_d, r, s, log2_m,
+                                              masks, seed, status_d, errpos_d, summary_d, S(stream), handle);
+}
 
 // ---- the verifier (pairing.hpp): the kernels are compiled per curve in pairing_<curve>.hip ----
 #define PAIRING_OR_FAIL()                                                                       \

@@ -501,6 +501,32 @@ class IEngine {
                             const void* a_share, const void* ax_share, const void* r, const void* s, int log_m,
                             const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
                             hipStream_t st) = 0;
+  // circom_h_checked of nb proofs as one launch chain; the report proof-major: status / errpos [nb][7][m/l], summary
+  // [nb][7][3 + n], proof b's slice what circom_h_checked with seed + 16 b writes (engine_groth16.inc.hpp)
+  virtual int circom_h_batch_checked(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
+                                     const zk_groth16_masks* masks, uint64_t seed, void* h, uint8_t* status, uint32_t* errpos,
+                                     uint64_t* summary, hipStream_t st) = 0;
+  // the asynchronous forms of the two checked provers: groth16_wait joins them, the report is complete when it returns
+  virtual int groth16_prove_checked_async(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc,
+                                          const void* a_share, const void* ax_share, const void* r, const void* s, int log_m,
+                                          const zk_groth16_masks* masks, uint64_t seed, uint8_t* status, uint32_t* errpos,
+                                          uint64_t* summary, hipStream_t st, int* handle) = 0;
+  virtual int groth16_prove_checked_parties_async(const uint32_t* parties, int nparties, const zk_crs_share* crs,
+                                                  const void* qa, const void* qb, const void* qc, const void* a_share,
+                                                  const void* ax_share, const void* r, const void* s, int log_m,
+                                                  const zk_groth16_masks* masks, uint64_t seed, uint8_t* status,
+                                                  uint32_t* errpos, uint64_t* summary, hipStream_t st, int* handle) = 0;
+  // groth16_prove_batch on the checked h chain of a batch; groth16_batch_wait joins the asynchronous form
+  virtual int groth16_prove_checked_batch(const zk_crs_share* crs, int nb, const void* const* qa, const void* const* qb,
+                                          const void* const* qc, const void* const* a_share, const void* const* ax_share,
+                                          const void* r, const void* s, int log_m, const zk_groth16_masks* masks,
+                                          uint64_t seed, void* pi_a, void* pi_b, void* pi_c, uint8_t* status,
+                                          uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
+  virtual int groth16_prove_checked_batch_async(const zk_crs_share* crs, int nb, const void* const* qa,
+                                                const void* const* qb, const void* const* qc, const void* const* a_share,
+                                                const void* const* ax_share, const void* r, const void* s, int log_m,
+                                                const zk_groth16_masks* masks, uint64_t seed, uint8_t* status,
+                                                uint32_t* errpos, uint64_t* summary, hipStream_t st, int* handle) = 0;
   // the issue callback of the per-party entry points (engine_party.inc.hpp): the k records of one round on slot `sid`, in
   // ascending party order -> the ONE rank call of recs[0].op with the parties' rows, on the slot's own stream
   virtual PartyResult party_issue(Net* net, PartyHub* hub, int sid, const PartyRec* recs) = 0;

@@ -348,6 +348,154 @@
     return deg_red_batch(W0, db, nb, nullptr, n, Lc, seed + 6, h, st, 0, 0, W0 + per, W0 + 2 * per);
   }
 
+  // ---------------------------------------------------------------- the checked h chain of a batch
+  // (zk_circom_h_batch_checked, zk_groth16_prove_checked_batch) circom_h_batch with every king word of every proof repaired
+  // before its king reads it: proof b is circom_h_checked_ws with seed + PROOF_SEED_STEP * b, its report slice
+  // rep.status + b * 7 * m/l (errpos alike, summary + b * 7 * (3 + n)) what that call writes.  One chain for the batch:
+  //   fft1_src over 3 nb vectors; h_words_batch_kernel (h_batch.hpp) puts the 1 / m and the in-masks into all 3 nb words;
+  //   ONE gao_run of 3 nb items (a full batch is exactly GAO_BATCH_MAX); the batched king with null in-masks;
+  //   the same for the forward round; h_mulsub_batch_kernel writes the nb words a*b - c (+ degred_in) into W1, which the
+  //   second king has read; ONE gao_run of nb items at dimension 4l - 1; deg_red_batch on the ready words (null in-masks,
+  //   no mul_b / sub_c: the form that takes a word as it is).
+  // The repair indexes status and errpos by item, so a round's rows are contiguous: the three repairs write a round-major
+  // staging report behind the repair's working memory in hwork (h_batch.hpp staging_row) and h_report_gather_kernel, the last
+  // launch of the chain, moves the rows to the caller's proof-major buffers.  hwork: 6 per nb vectors, gao_layout(n, 3 nb,
+  // m/l), the staging status, errpos and summary rows.
+  // The in-masks of a stage must be present or absent alike across the batch and a round's three words (circom_h_batch's
+  // condition); otherwise circom_h_checked_ws proof by proof on the stream -- the same results.
+  static_assert(H_BATCH_MAX == DEGRED_BATCH && H_BATCH_ITEMS == KING_BATCH && H_BATCH_ITEMS == GAO_BATCH_MAX,
+                "one round of a full batch is one king launch and one repair call");
+  static HReport report_slice(const HReport& rep, int b, size_t Lc, int n_) {
+    return HReport{rep.status + (size_t)b * H_REPORT_ROWS * Lc, rep.errpos ? rep.errpos + (size_t)b * H_REPORT_ROWS * Lc : nullptr,
+                   rep.summary ? rep.summary + (size_t)b * H_REPORT_ROWS * (3 + n_) : nullptr};
+  }
+  // every refusal of the batched chain, before anything is written
+  int h_batch_checked_check(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
+                            const void* h, const HReport& rep) {
+    int log_l = ilog2(l);
+    if (nb < 1 || nb > H_BATCH_MAX) return fail(ZK_ERR_BAD_INPUT, "batch size must be in 1.." + std::to_string(H_BATCH_MAX));
+    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
+    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
+    if (!qa || !qb || !qc || !h || !rep.status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    for (int b = 0; b < nb; b++)
+      if (!qa[b] || !qb[b] || !qc[b]) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    if (!gao_batch_fits(3 * (uint64_t)nb, ((size_t)1 << log_m) / l))
+      return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
+    return ZK_OK;
+  }
+  int circom_h_batch_checked(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
+                             const zk_groth16_masks* mk, uint64_t seed, void* h, uint8_t* status, uint32_t* errpos,
+                             uint64_t* summary, hipStream_t st) override {
+    return circom_h_batch_checked_ws(nb, qa, qb, qc, log_m, mk, seed, (Fr*)h, HReport{status, errpos, summary}, ws(st)->hwork, st);
+  }
+  int circom_h_batch_checked_ws(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
+                                const zk_groth16_masks* mk, uint64_t seed, Fr* h, const HReport& rep, DevBuf& hwork,
+                                hipStream_t st) {
+    int rc = h_batch_checked_check(nb, qa, qb, qc, log_m, h, rep);
+    if (rc) return rc;
+    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
+    bool uniform = true;
+    if (mk)
+      for (int k = 0; k < 6 && uniform; k++)
+        for (int b = 1; b < nb; b++)
+          if ((mk[b].fft_in[k] != nullptr) != (mk[0].fft_in[k] != nullptr)) uniform = false;
+    if (mk && uniform)
+      for (int k = 0; k < 6 && uniform; k += 3)
+        if ((mk[0].fft_in[k] != nullptr) != (mk[0].fft_in[k + 1] != nullptr) ||
+            (mk[0].fft_in[k] != nullptr) != (mk[0].fft_in[k + 2] != nullptr))
+          uniform = false;
+    if (!uniform) {
+      for (int b = 0; b < nb; b++) {
+        rc = circom_h_checked_ws(qa[b], qb[b], qc[b], log_m, &mk[b], seed + (uint64_t)PROOF_SEED_STEP * b, h + b * per,
+                                 report_slice(rep, b, Lc, n), hwork, st);
+        if (rc) return rc;
+      }
+      return ZK_OK;
+    }
+    // ---- working memory: vectors | repair | staging status | staging errpos | staging summary, each at a multiple of 32
+    auto up32 = [](size_t v) { return (v + 31) / 32 * 32; };
+    const size_t rows = (size_t)H_REPORT_ROWS * nb, sumw = (size_t)(3 + n);
+    const size_t vec_bytes = 6 * per * nb * sizeof(Fr);
+    const size_t off_st = vec_bytes + up32(gao_layout<Fr>(n, 3 * nb, Lc, false).bytes);
+    const size_t off_ep = off_st + up32(rows * Lc);
+    const size_t off_sm = off_ep + up32(rep.errpos ? rows * Lc * 4 : 0);
+    ZK_HIP(hwork.ensure(off_sm + (rep.summary ? rows * sumw * 8 : 0)));
+    Fr* W0 = (Fr*)hwork.p;
+    Fr* W1 = W0 + 3 * per * nb;
+    void* gwk = (char*)hwork.p + vec_bytes;
+    uint8_t* s_st = (uint8_t*)hwork.p + off_st;
+    uint32_t* s_ep = rep.errpos ? (uint32_t*)((char*)hwork.p + off_ep) : nullptr;
+    uint64_t* s_sm = rep.summary ? (uint64_t*)((char*)hwork.p + off_sm) : nullptr;
+    // the repair of a round into its staging rows
+    auto repair = [&](Fr* W, int round, int dimension) {
+      const size_t first = staging_round_first((uint32_t)nb, (uint32_t)round);
+      GaoCall c = gao_call(W, nullptr, n, Lc, dimension, s_st + first * Lc, s_ep ? s_ep + first * Lc : nullptr,
+                           s_sm ? s_sm + first * sumw : nullptr);
+      c.nitems = (int)staging_round_items((uint32_t)nb, (uint32_t)round), c.item_stride = per;
+      return gao_run<FrP, true>(this, gwk, l, c, st);
+    };
+    // the words of a round in place (item 3 b + k at W + (3 b + k) * per) and whether they carry in-masks
+    const Fr minv = Fr::from_u64((uint64_t)1 << log_m).inverse();
+    auto words = [&](Fr* W, int first, int inverse, bool* masked) {
+      *masked = mk && mk[0].fft_in[first];
+      if (!*masked) return (int)ZK_OK;
+      HWordMasks<Fr> hm{};
+      for (int b = 0; b < nb; b++)
+        for (int k = 0; k < 3; k++) hm.mask[3 * b + k] = (const Fr*)mk[b].fft_in[first + k];
+      h_words_batch_kernel<Fr><<<h_batch_grid(per, 3 * nb), dim3(256), 0, st>>>(W, per, hm, inverse, minv, per);
+      ZK_HIP(hipGetLastError());
+      return (int)ZK_OK;
+    };
+    const Fr* U = nullptr;
+    if ((rc = umat_for(nullptr, n, &U))) return rc;
+    auto king = [&](const Fr* in, int first, int inverse, const void* g, int scale, int rearrange, uint64_t sd, Fr* out) {
+      KingBatch<Fr> kb{};
+      kb.stride = per;
+      kb.items_per = 3;
+      kb.seed_step = PROOF_SEED_STEP;
+      for (int b = 0; b < nb; b++)
+        for (int k = 0; k < 3; k++) kb.out_mask[3 * b + k] = mk ? (const Fr*)mk[b].fft_out[first + k] : nullptr;
+      return king_dispatch_batch(in, kb, 3 * nb, n, log_m, inverse, U, g, scale, rearrange, sd, out, false, st);
+    };
+    Fr w2m = root_of_unity(log_m + 1);
+    NttSrc<Fr> src{};
+    src.per = (uint32_t)n;
+    for (int b = 0; b < nb; b++) {
+      src.p[3 * b] = (const Fr*)qa[b];
+      src.p[3 * b + 1] = (const Fr*)qb[b];
+      src.p[3 * b + 2] = (const Fr*)qc[b];
+    }
+    bool masked = false;
+    // round 1: 3 nb x d_ifft(rearrange = true, g = w_2m); the 1 / m is in the word where there is a mask
+    if ((rc = fft1_src(W0, log_m, 1, 3 * (size_t)n * nb, nullptr, st, src))) return rc;
+    if ((rc = words(W0, 0, 1, &masked))) return rc;
+    if ((rc = repair(W0, 0, 2 * l))) return rc;
+    if ((rc = king(W0, 0, 1, &w2m, masked ? 0 : 1, 1, seed, W1))) return rc;
+    // round 2: 3 nb x d_fft(rearrange = false)
+    if ((rc = fft1(W1, log_m, 0, 3 * (size_t)n * nb, nullptr, st))) return rc;
+    if ((rc = words(W1, 3, 0, &masked))) return rc;
+    if ((rc = repair(W1, 1, 2 * l))) return rc;
+    if ((rc = king(W1, 3, 0, nullptr, 0, 0, seed + 3, W0))) return rc;
+    // the nb words a*b - c + in_mask at W1 + b * per, detection at dimension 4l - 1, then deg_red on the ready words
+    HProdMasks<Fr> pm{};
+    DegredBatch<Fr> db{};
+    for (int b = 0; b < nb; b++) {
+      pm.mask[b] = mk ? (const Fr*)mk[b].degred_in : nullptr;
+      db.out_mask[b] = mk ? (const Fr*)mk[b].degred_out : nullptr;
+    }
+    h_mulsub_batch_kernel<Fr><<<h_batch_grid(per, nb), dim3(256), 0, st>>>(W1, per, W0, 3 * per, pm, per);
+    ZK_HIP(hipGetLastError());
+    if ((rc = repair(W1, 2, 4 * l - 1))) return rc;
+    db.in_step = per;
+    db.out_step = per;
+    db.seed_step = PROOF_SEED_STEP;
+    if ((rc = deg_red_batch(W1, db, nb, nullptr, n, Lc, seed + 6, h, st))) return rc;
+    h_report_gather_kernel<<<h_batch_grid(Lc, (int)rows), dim3(256), 0, st>>>(
+        (uint32_t)nb, (uint32_t)Lc, (uint32_t)sumw, s_st, s_ep, s_sm, rep.status, rep.errpos, rep.summary);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+  }
+
   // ---------------------------------------------------------------- prover (prove.rs, sha256.rs:32-129)
   // Everything the host contributes to a proof (scalar multiples of CRS constants, of the out-masks and of the in-mask
   // sums, MSM window folds) is a task of the context's persistent pool, submitted when the proof starts and running
@@ -416,6 +564,11 @@
     std::atomic<int> sorted_cnt{0};     // witness MSMs of this proof whose sort has been enqueued and recorded (MsmGate)
     int k = 0;
     uint32_t cmask3 = 0;
+    // a checked proof (zk_groth16_prove_checked*_async): where its report goes and the validated party list -- the job's own
+    // copies, so that nothing it reads after the call has returned belongs to the caller (report.ids points at report_ids)
+    bool checked = false;
+    HReport report{};
+    uint32_t report_ids[GAO_MAX_N] = {};
   };
   ProveJob jobs_[NJOBS];
   // A batch of proofs against one CRS in flight (zk_groth16_prove_batch_async).  Each batch slot has its own MSM
@@ -1002,17 +1155,27 @@
     return groth16_wait(h, pi_a, pi_b, pi_c);
   }
   // zk_groth16_prove_checked: the proof above with circom_h's seven king words checked (circom_h_checked_ws).  The five d_msm
-  // rounds stay unchecked.  Synchronous: the join orders the report buffers.
+  // rounds stay unchecked.  The asynchronous form followed by the join, which orders the report buffers.
   int groth16_prove_checked(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
                             const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk,
                             uint64_t seed, void* pi_a, void* pi_b, void* pi_c, uint8_t* status, uint32_t* errpos,
                             uint64_t* summary, hipStream_t st) override {
     if (!pi_a || !pi_b || !pi_c || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    const HReport report{status, errpos, summary};
     int h = -1;
-    int rc = prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, &h, &report);
+    int rc = groth16_prove_checked_async(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, status, errpos, summary,
+                                         st, &h);
     if (rc) return rc;
     return groth16_wait(h, pi_a, pi_b, pi_c);
+  }
+  // zk_groth16_prove_checked_async: the report descriptor goes into the job (prove_start); zk_groth16_wait joins it like any
+  // proof -- the h chain runs ahead of the U-MSM on the job's stream, so the report is complete when the join returns
+  int groth16_prove_checked_async(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
+                                  const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk,
+                                  uint64_t seed, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st,
+                                  int* handle) override {
+    if (!status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    const HReport report{status, errpos, summary};
+    return prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, handle, &report);
   }
   // zk_groth16_prove_checked_parties: the checked proof from the words and MSM contributions of a party list -- the h chain
   // of circom_h_checked_parties, the list's coefficients in the five MSM rounds and the host in-mask terms (prove_begin_impl)
@@ -1023,16 +1186,27 @@
     uint32_t ids[GAO_MAX_N];
     int rc = checked_list(parties, np, 2 * l, ids);
     if (rc) return rc;
-    if (np == n)
-      return groth16_prove_checked(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, pi_a, pi_b, pi_c, status, errpos,
-                                   summary, st);
     if (!pi_a || !pi_b || !pi_c || !status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    HReport report{status, errpos, summary};
-    report.ids = ids, report.np = np;
     int h = -1;
-    rc = prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, &h, &report);
+    rc = groth16_prove_checked_parties_async(parties, np, crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, status,
+                                             errpos, summary, st, &h);
     if (rc) return rc;
     return groth16_wait(h, pi_a, pi_b, pi_c);
+  }
+  // zk_groth16_prove_checked_parties_async: the list is validated here and copied into the job by prove_start; `parties` is
+  // not read after the call returns
+  int groth16_prove_checked_parties_async(const uint32_t* parties, int np, const zk_crs_share* crs, const void* qa,
+                                          const void* qb, const void* qc, const void* a_share, const void* ax_share,
+                                          const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk, uint64_t seed,
+                                          uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st,
+                                          int* handle) override {
+    uint32_t ids[GAO_MAX_N];
+    int rc = checked_list(parties, np, 2 * l, ids);
+    if (rc) return rc;
+    if (!status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    HReport report{status, errpos, summary};
+    if (np < n) report.ids = ids, report.np = np;
+    return prove_start(crs, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, handle, &report);
   }
   int groth16_prove_async(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
                           const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk,
@@ -1048,6 +1222,15 @@
     ProveJob* j = free_job(jobs_);
     if (!j) return fail(ZK_ERR_BAD_INPUT, "too many proofs in flight (zk_groth16_wait one first)");
     Fr r = Fr::from_limbs((const uint32_t*)r_), s = Fr::from_limbs((const uint32_t*)s_);
+    // the job's own copy of the report descriptor and of the list
+    if ((j->checked = report != nullptr)) {
+      j->report = *report;
+      if (report->np > 0) {
+        std::copy(report->ids, report->ids + report->np, j->report_ids);
+        j->report.ids = j->report_ids;
+      }
+      report = &j->report;
+    }
     rc = prove_begin(*j, crs, qa, qb, qc, a_share, ax_share, r, s, log_m, mk, seed, true, 0, n, st, false, report);
     if (rc) return rc;
     *handle = j->slot;
@@ -1093,6 +1276,35 @@
                                 const void* const* qc, const void* const* a_share, const void* const* ax_share,
                                 const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk, uint64_t seed,
                                 hipStream_t st, int* handle) override {
+    return batch_start(crs_in, nb, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, handle, nullptr);
+  }
+  // zk_groth16_prove_checked_batch: the batch above on the checked h chain of a batch (circom_h_batch_checked_ws) with the
+  // batch's own hwork, and so its own staging report; the five d_msm rounds stay unchecked as in the single call.  The
+  // report (proof-major, [nb][7]) is complete when zk_groth16_batch_wait returns.
+  int groth16_prove_checked_batch(const zk_crs_share* crs, int nb, const void* const* qa, const void* const* qb,
+                                  const void* const* qc, const void* const* a_share, const void* const* ax_share,
+                                  const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk, uint64_t seed,
+                                  void* pi_a, void* pi_b, void* pi_c, uint8_t* status, uint32_t* errpos, uint64_t* summary,
+                                  hipStream_t st) override {
+    if (!pi_a || !pi_b || !pi_c) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    int h = -1;
+    int rc = groth16_prove_checked_batch_async(crs, nb, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, status, errpos,
+                                               summary, st, &h);
+    if (rc) return rc;
+    return groth16_batch_wait(h, pi_a, pi_b, pi_c);
+  }
+  int groth16_prove_checked_batch_async(const zk_crs_share* crs, int nb, const void* const* qa, const void* const* qb,
+                                        const void* const* qc, const void* const* a_share, const void* const* ax_share,
+                                        const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk, uint64_t seed,
+                                        uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st,
+                                        int* handle) override {
+    if (!status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
+    const HReport report{status, errpos, summary};
+    return batch_start(crs, nb, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, handle, &report);
+  }
+  int batch_start(const zk_crs_share* crs_in, int nb, const void* const* qa, const void* const* qb, const void* const* qc,
+                  const void* const* a_share, const void* const* ax_share, const void* r_, const void* s_, int log_m,
+                  const zk_groth16_masks* mk, uint64_t seed, hipStream_t st, int* handle, const HReport* report) {
     if (!qa || !qb || !qc || !handle) return fail(ZK_ERR_BAD_INPUT, "null pointer");
     if (nb >= 1 && nb <= MAX_PROOF_BATCH)
       for (int b = 0; b < nb; b++)
@@ -1102,7 +1314,8 @@
     if (rc) return rc;
     // ---- circom_h of the whole batch and the U-MSM behind it
     const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    rc = circom_h_batch(nb, qa, qb, qc, log_m, mk, seed, (Fr*)B->hshare.p, B->hwork, B->st[5]);
+    if (report) rc = circom_h_batch_checked_ws(nb, qa, qb, qc, log_m, mk, seed, (Fr*)B->hshare.p, *report, B->hwork, B->st[5]);
+    else rc = circom_h_batch(nb, qa, qb, qc, log_m, mk, seed, (Fr*)B->hshare.p, B->hwork, B->st[5]);
     if (!rc) rc = batch_launch_u(*B, (const Fr*)B->hshare.p, per, B->st[5]);
     if (rc) return bail(*B, rc);
     *handle = B->slot;

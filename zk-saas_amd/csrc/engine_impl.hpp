@@ -18,6 +18,7 @@
 #include "points.hpp"
 #include "dpp.hpp"
 #include "rows.hpp"
+#include "h_batch.hpp"
 
 namespace zk {
 

@@ -576,10 +576,11 @@ def prove(pp, crs, wit, r, s, masks=None, seed=0, stream=None, check=False, part
 
 class BatchInFlight:
     """A batch started with prove_batch_async (zk_groth16_prove_batch_async); wait() joins it and returns the list of
-    (pi_a, pi_b, pi_c)."""
+    (pi_a, pi_b, pi_c) -- for a checked batch (check=True, zk_groth16_prove_checked_batch_async) that list and the list of
+    the proofs' reports, complete once the join has returned."""
 
-    def __init__(self, pp, handle, nb, keep):
-        self.pp, self.handle, self.nb, self._keep = pp, handle, nb, keep
+    def __init__(self, pp, handle, nb, keep, reports=None):
+        self.pp, self.handle, self.nb, self._keep, self._reports = pp, handle, nb, keep, reports
 
     def wait(self):
         pp, nb, nl = self.pp, self.nb, self.pp.fq.nl
@@ -588,17 +589,21 @@ class BatchInFlight:
         pc = np.zeros((nb, pp.n, 3 * nl), dtype=np.uint64)
         pp._check(pp.lib.zk_groth16_batch_wait(pp.h, self.handle, pa.ctypes.data, pb.ctypes.data, pc.ctypes.data))
         self._keep = None
-        return [(pa[b], pb[b], pc[b]) for b in range(nb)]
+        proofs = [(pa[b], pb[b], pc[b]) for b in range(nb)]
+        return proofs if self._reports is None else (proofs, self._reports)
 
 
-def prove_batch(pp, crs, wits, rs, ss, masks=None, seed=0, stream=None):
+def prove_batch(pp, crs, wits, rs, ss, masks=None, seed=0, stream=None, check=False):
     """zk_groth16_prove_batch: len(wits) proofs against one CRS in one pass (each witness with its own r, s and
-    masks).  Returns a list of (pi_a, pi_b, pi_c) as prove() gives them."""
-    return prove_batch_async(pp, crs, wits, rs, ss, masks=masks, seed=seed, stream=stream).wait()
+    masks).  Returns a list of (pi_a, pi_b, pi_c) as prove() gives them.
+    check=True: zk_groth16_prove_checked_batch -- (proofs, reports), reports[b] shaped like the report of prove(check=True)
+    and holding what that call reports with seed + 16 b."""
+    return prove_batch_async(pp, crs, wits, rs, ss, masks=masks, seed=seed, stream=stream, check=check).wait()
 
 
-def prove_batch_async(pp, crs, wits, rs, ss, masks=None, seed=0, stream=None):
-    """zk_groth16_prove_batch_async: enqueue a batch and return at once; up to two batches may be in flight."""
+def prove_batch_async(pp, crs, wits, rs, ss, masks=None, seed=0, stream=None, check=False):
+    """zk_groth16_prove_batch_async: enqueue a batch and return at once; up to three batches, checked (check=True,
+    zk_groth16_prove_checked_batch_async) or not, may be in flight."""
     nb = len(wits)
     assert len(rs) == nb and len(ss) == nb and (masks is None or len(masks) == nb)
     rr = np.ascontiguousarray(np.stack([pp.fr.encode_one(v) for v in rs]))
@@ -613,6 +618,14 @@ def prove_batch_async(pp, crs, wits, rs, ss, masks=None, seed=0, stream=None):
             src = m.ct if isinstance(m, ProofMasks) else m
             C.memmove(C.byref(mk, b * C.sizeof(Masks)), C.byref(src), C.sizeof(Masks))
     h = C.c_int(-1)
+    if check:
+        whole, reports = api.h_batch_reports(pp, nb, wits[0].log_m)
+        pp._check(pp.lib.zk_groth16_prove_checked_batch_async(
+            pp.h, C.byref(crs.ct), nb, arr(lambda w: w.qap[0].ptr), arr(lambda w: w.qap[1].ptr), arr(lambda w: w.qap[2].ptr),
+            arr(lambda w: w.a_share.ptr), arr(lambda w: w.ax_share.ptr), rr.ctypes.data, sv.ctypes.data, wits[0].log_m,
+            None if mk is None else C.cast(mk, C.c_void_p), seed, whole.status.ptr, whole.errpos.ptr, whole.summary_d.ptr,
+            stream, C.byref(h)))
+        return BatchInFlight(pp, h.value, nb, (crs, wits, masks, mk, whole), reports)
     pp._check(pp.lib.zk_groth16_prove_batch_async(
         pp.h, C.byref(crs.ct), nb, arr(lambda w: w.qap[0].ptr), arr(lambda w: w.qap[1].ptr), arr(lambda w: w.qap[2].ptr),
         arr(lambda w: w.a_share.ptr), arr(lambda w: w.ax_share.ptr), rr.ctypes.data, sv.ctypes.data, wits[0].log_m,
@@ -661,10 +674,11 @@ def reconstruct_robust(pp, proofs, parties=None, want_bytes=True, stream=None):
 
 
 class ProofInFlight:
-    """A proof started with prove_async (zk_groth16_prove_async); wait() joins it and returns the shares."""
+    """A proof started with prove_async (zk_groth16_prove_async); wait() joins it and returns the shares -- for a checked
+    proof (check=True) the pair (shares, report), the report complete once the join has returned."""
 
-    def __init__(self, pp, handle, keep):
-        self.pp, self.handle, self._keep = pp, handle, keep
+    def __init__(self, pp, handle, keep, report=None):
+        self.pp, self.handle, self._keep, self._report = pp, handle, keep, report
 
     def wait(self):
         pp = self.pp
@@ -674,16 +688,32 @@ class ProofInFlight:
         pc = np.zeros((pp.n, 3 * nl), dtype=np.uint64)
         pp._check(pp.lib.zk_groth16_wait(pp.h, self.handle, pa.ctypes.data, pb.ctypes.data, pc.ctypes.data))
         self._keep = None
-        return pa, pb, pc
+        return (pa, pb, pc) if self._report is None else ((pa, pb, pc), self._report)
 
 
-def prove_async(pp, crs, wit, r, s, masks=None, seed=0, stream=None):
-    """zk_groth16_prove_async: enqueue one proof and return at once; up to two may be in flight per context."""
+def prove_async(pp, crs, wit, r, s, masks=None, seed=0, stream=None, check=False, parties=None):
+    """zk_groth16_prove_async: enqueue one proof and return at once; up to two may be in flight per context.
+    check=True: zk_groth16_prove_checked_async -- wait() returns (proof, report) as prove(check=True) does; with parties
+    zk_groth16_prove_checked_parties_async (the id list is copied by the call)."""
+    if parties is not None and not check:
+        raise ValueError("a party list needs check=True (the unchecked prover takes all n parties)")
     rr, ss = pp.fr.encode_one(r), pp.fr.encode_one(s)
     assert crs.len_a == wit.len_a and crs.len_w == wit.len_w
     keep = (crs, wit, masks, rr, ss)
     mk = masks.ct if isinstance(masks, ProofMasks) else masks
     h = C.c_int(-1)
+    if check:
+        rep = api.h_report(pp, wit.log_m)
+        tail = (rr.ctypes.data, ss.ctypes.data, wit.log_m, None if mk is None else C.byref(mk), seed, rep.status.ptr,
+                rep.errpos.ptr, rep.summary_d.ptr, stream, C.byref(h))
+        head = (C.byref(crs.ct), wit.qap[0].ptr, wit.qap[1].ptr, wit.qap[2].ptr, wit.a_share.ptr, wit.ax_share.ptr)
+        if parties is None:
+            pp._check(pp.lib.zk_groth16_prove_checked_async(pp.h, *head, *tail))
+        else:
+            rep.parties = list(parties)
+            ids = parties if isinstance(parties, C.Array) else (C.c_uint32 * len(rep.parties))(*rep.parties)
+            pp._check(pp.lib.zk_groth16_prove_checked_parties_async(pp.h, ids, len(rep.parties), *head, *tail))
+        return ProofInFlight(pp, h.value, keep, rep)
     pp._check(pp.lib.zk_groth16_prove_async(pp.h, C.byref(crs.ct), wit.qap[0].ptr, wit.qap[1].ptr, wit.qap[2].ptr,
                                             wit.a_share.ptr, wit.ax_share.ptr, rr.ctypes.data, ss.ctypes.data,
                                             wit.log_m, None if mk is None else C.byref(mk), seed, stream, C.byref(h)))
