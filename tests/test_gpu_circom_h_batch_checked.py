@@ -10,6 +10,9 @@ and then states the report it expects in numbers.
                   chunk, every other row of every proof is clean
   two liars       p0 in proof 0, p2 in proof 2: each report names its own liar (an item / proof mix-up in the gather)
   masks           none at all; in-masks in round 1 only; mask sets that differ between the proofs (the proof-by-proof route)
+  partial masks   nb = 2, on every proof the in-masks of items 1, 3 and 4 absent: alike across the batch, not within a round,
+                  so the proofs run one by one and their kings item by item; clean and with one liar; bn254 l = 2 and l = 8
+                  at m/l = 4 (one partial workgroup of the scan) and 512 (two per item, four at l = 8)
   optional        errpos_d and summary_d NULL: same statuses, same h
   refusals        nb = 0, nb = 17, null pointers: ZK_ERR_BAD_INPUT, the report buffers keep their sentinel bytes
 Sizes: m/l half of, and twice, the number of chunks one workgroup of the repair's scan takes (GAO_THREADS of gao_impl.hpp at
@@ -79,7 +82,8 @@ def _copy_masks(ct):
 
 def _mask_set(pp, Lc, b, which):
     """the zk_groth16_masks of proof b (None: no masks).  The dealt buffers are shared among the tests and never written.
-    all: all twelve masks; round1: no in-masks in the d_fft round; mixed: proof 1 lacks the in-mask of item 0"""
+    all: all twelve masks; round1: no in-masks in the d_fft round; mixed: proof 1 lacks the in-mask of item 0; partial: every
+    proof lacks those of items 1, 3 and 4 (the set of test_gpu_circom_h_checked.py)"""
     if which == "none":
         return None
     key = (pp.curve, pp.l, Lc, b % NSETS)
@@ -91,6 +95,9 @@ def _mask_set(pp, Lc, b, which):
             mk.fft_in[k] = None
     if which == "mixed" and b == 1:
         mk.fft_in[0] = None
+    if which == "partial":
+        for k in (1, 3, 4):                     # round 1: a and c masked; round 2: c only
+            mk.fft_in[k] = None
     return mk
 
 
@@ -191,6 +198,14 @@ def test_mask_sets(curve, l, Lc, which):
     _batch(pp, Lc, 3, which)
     _batch(pp, Lc, 3, which, {1: pp.n - 2})
     _batch(pp, Lc, 3, which, {0: 1, 2: pp.n - 1})
+
+
+@pytest.mark.parametrize("Lc", [4, 512])
+@pytest.mark.parametrize("l", [2, 8])
+def test_masks_partial_within_a_round_alike_across_the_batch(l, Lc):
+    pp = ctx("bn254", l)
+    _batch(pp, Lc, 2, "partial")
+    _batch(pp, Lc, 2, "partial", {1: pp.n - 2})
 
 
 @pytest.mark.parametrize("Lc", SIZES)

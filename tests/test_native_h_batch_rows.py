@@ -6,6 +6,9 @@ for every batch size 1 .. 16:
   * staging_row is a bijection onto 0 .. 7 nb - 1,
   * a round's rows are contiguous and in the item order of its repair,
   * the gather, replayed on host buffers, gives every report row the bytes of its own (proof, item).
+and the layout of the chain's work buffer (h_layout, the one place that computes it) for every form of the chain at nb 1 .. 16,
+n in {4, 8, 16, 32}, m/l in {1, 4, 512, 2^17}: regions aligned, in order and disjoint, the totals those the four forms asked for
+before (written out in the test), no staging for one proof.
 Built and run once plain and once with -fsanitize=address,undefined.  The counts are restated here in Python."""
 import os
 import subprocess
@@ -32,6 +35,8 @@ def _run(sanitize):
     lines = r.stdout.splitlines()
     assert lines[-1] == "0 violations", r.stdout[-4000:]
     assert lines[-2] == "batches %d rows %d" % (16, sum(7 * nb for nb in range(1, 17)))
+    # per field, n and m/l: one proof in 9 forms (unchecked; checked x errpos x summary, with a list and without), a batch in 5
+    assert lines[-3] == "layouts %d" % (2 * 4 * 4 * (9 + 15 * 5))
 
 
 def test_staging_rows_are_a_bijection_and_rounds_are_contiguous():

@@ -476,7 +476,7 @@ class IEngine {
   virtual int pss_repair_batch_parties(void* shares, const uint32_t* parties, int nparties, size_t item_stride, int nitems,
                                        size_t nchunks, int dimension, uint8_t* status, uint32_t* errpos, uint64_t* summary,
                                        hipStream_t st) = 0;
-  // circom_h_checked when only the listed parties' words reach the kings (engine_groth16.inc.hpp)
+  // circom_h_checked when only the listed parties' words reach the kings (engine_h.inc.hpp)
   virtual int circom_h_checked_parties(const uint32_t* parties, int nparties, const void* qa, const void* qb, const void* qc,
                                        int log_m, const zk_groth16_masks* masks, uint64_t seed, void* h, uint8_t* status,
                                        uint32_t* errpos, uint64_t* summary, hipStream_t st) = 0;
@@ -502,7 +502,7 @@ class IEngine {
                             const zk_groth16_masks* masks, uint64_t seed, void* pi_a, void* pi_b, void* pi_c,
                             hipStream_t st) = 0;
   // circom_h_checked of nb proofs as one launch chain; the report proof-major: status / errpos [nb][7][m/l], summary
-  // [nb][7][3 + n], proof b's slice what circom_h_checked with seed + 16 b writes (engine_groth16.inc.hpp)
+  // [nb][7][3 + n], proof b's slice what circom_h_checked with seed + 16 b writes (engine_h.inc.hpp)
   virtual int circom_h_batch_checked(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
                                      const zk_groth16_masks* masks, uint64_t seed, void* h, uint8_t* status, uint32_t* errpos,
                                      uint64_t* summary, hipStream_t st) = 0;

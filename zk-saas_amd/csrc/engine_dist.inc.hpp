@@ -259,7 +259,7 @@
   }
   // NOT CHECKED: at dimension 4l - 1 a list of n - 1 parties has no redundancy left (deg_red with a rank absent)
   bool dist_not_checked(int dimension, int np) const { return dimension == 4 * l - 1 && np < n; }
-  // item `item` of an h report as the check of one round ([7][m/l] / [7][3 + n], engine_groth16.inc.hpp HReport)
+  // item `item` of an h report as the check of one round ([7][m/l] / [7][3 + n], engine_h.inc.hpp HReport)
   DistCheck dist_check_item(Net* net, uint32_t mask, const HReport& rep, int item, size_t Lc, int dimension) {
     DistCheck ck;
     ck.status = rep.status + (size_t)item * Lc;

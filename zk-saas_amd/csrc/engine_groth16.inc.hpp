@@ -1,500 +1,5 @@
-// Part of class Engine<Cfg> (engine_impl.hpp includes this file INSIDE the class body): circom_h / libsnark_h, the Groth16 prover (one proof, two in flight) and the batch prover.
+// Part of class Engine<Cfg> (engine_impl.hpp includes this file INSIDE the class body): the Groth16 prover (one proof, two in flight) and the batch prover (the h chain: engine_h.inc.hpp).
 // Split out of engine_impl.hpp in round 5 (one 3 400-line class body had stopped being navigable); not a stand-alone header.
-
-  // ---------------------------------------------------------------- circom_h (ext_wit.rs:104-181)
-  // the king step of three d_fft / d_ifft (a, b, c at in + k * per; masks mk->fft_*[first + k]; randomness seed + k):
-  // one batched launch when the in-masks are all present or all absent, three launches otherwise
-  int king3(const Fr* in, const zk_groth16_masks* mk, int first, int log_m, int inverse, const void* g, int scale,
-            int rearrange, uint64_t seed, Fr* out, size_t per, hipStream_t st) {
-    const Fr* U = nullptr;
-    int rc = umat_for(nullptr, n, &U);
-    if (rc) return rc;
-    KingBatch<Fr> kb{};
-    kb.stride = per;
-    bool any = false, all = true;
-    for (int k = 0; k < 3; k++) {
-      kb.in_mask[k] = mk ? (const Fr*)mk->fft_in[first + k] : nullptr;
-      kb.out_mask[k] = mk ? (const Fr*)mk->fft_out[first + k] : nullptr;
-      any = any || kb.in_mask[k];
-      all = all && kb.in_mask[k];
-    }
-    if (any == all)
-      return king_dispatch_batch(in, kb, 3, n, log_m, inverse, U, g, scale, rearrange, seed, out, false, st);
-    for (int k = 0; k < 3; k++) {
-      rc = king_dispatch(in + k * per, kb.in_mask[k], n, log_m, inverse, U, g, scale, rearrange, seed + k,
-                         out + k * per, kb.out_mask[k], false, st);
-      if (rc) return rc;
-    }
-    return ZK_OK;
-  }
-  int circom_h(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* mk, uint64_t seed,
-               void* h, hipStream_t st) override {
-    return circom_h_ws(qa, qb, qc, log_m, mk, seed, h, ws(st)->hwork, st);
-  }
-  int circom_h_ws(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* mk, uint64_t seed,
-                  void* h, DevBuf& hwork, hipStream_t st) {
-    int log_l = ilog2(l);
-    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
-    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
-    if (!qa || !qb || !qc || !h) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    size_t Lc = ((size_t)1 << log_m) / l;
-    size_t per = (size_t)n * Lc;
-    ZK_HIP(hwork.ensure(6 * per * sizeof(Fr)));
-    Fr* W0 = (Fr*)hwork.p;
-    Fr* W1 = W0 + 3 * per;
-    Fr w2m = root_of_unity(log_m + 1);     // Radix2EvaluationDomain::new(2m).element(1), ext_wit.rs:120-125
-    // 3 x d_ifft(rearrange = true, g = w_2m)   (ext_wit.rs:127-159); the first pass reads the caller's vectors (no copy)
-    int rc = fft1_src(W0, log_m, 1, 3 * (size_t)n, nullptr, st,
-                      NttSrc<Fr>{{(const Fr*)qa, (const Fr*)qb, (const Fr*)qc}, (uint32_t)n});
-    if (rc) return rc;
-    rc = king3(W0, mk, 0, log_m, 1, &w2m, 1, 1, seed, W1, per, st);
-    if (rc) return rc;
-    // 3 x d_fft(rearrange = false)             (ext_wit.rs:161-170)
-    rc = fft1(W1, log_m, 0, 3 * (size_t)n, nullptr, st);
-    if (rc) return rc;
-    rc = king3(W1, mk, 3, log_m, 0, nullptr, 0, 0, seed + 3, W0, per, st);
-    if (rc) return rc;
-    // h = a*b - c share-wise, then deg_red     (ext_wit.rs:173-179): the product is formed at deg_red's load
-    return deg_red_np(W0, mk ? (const Fr*)mk->degred_in : nullptr, nullptr, n, Lc, seed + 6, (Fr*)h,
-                      mk ? (const Fr*)mk->degred_out : nullptr, st, 0, 0, W0 + per, W0 + 2 * per);
-  }
-
-  // ---------------------------------------------------------------- the checked h chain (zk_circom_h_checked)
-  // circom_h with each of its seven king words repaired before the king reads it.  Items 0..2: the d_ifft words of a, b, c;
-  // 3..5: the d_fft words; 6: the deg_red word.  The words are those of the single-word checked calls (engine_gao.inc.hpp
-  // d_fft_checked, deg_red_checked; ext_wit.rs:127-179): fft1(x) / m + in_mask (without a mask fft1(x), the 1 / m in the
-  // king's table), fft1(x) + in_mask, a*b - c + in_mask.  Each is materialised in W0 / W1, so the kings run with null
-  // in-masks; a round's three words are repaired by ONE pss_repair_batch.  Item 6 has dimension 4l - 1: detection only.
-  // The repair's working memory lies behind the six vectors of the work buffer.
-  struct HReport {
-    uint8_t* status;        // [7][m/l]
-    uint32_t* errpos;       // [7][m/l] or null
-    uint64_t* summary;      // [7][3 + n] or null
-    const uint32_t* ids = nullptr;      // zk_*_checked_parties: the party list (checked_list has passed it), np < n of them;
-    int np = 0;                         // 0: all n parties
-  };
-  // the words of a round in place: W + k * per is fft1 of vector k; masked[k]: item k has an in-mask
-  int h_round_words(Fr* W, const zk_groth16_masks* mk, int first, int log_m, int inverse, size_t per, bool* masked,
-                    hipStream_t st) {
-    int nm = 0, rc;
-    for (int k = 0; k < 3; k++) nm += masked[k] = mk && mk->fft_in[first + k];
-    if (inverse && nm) {
-      const Fr minv = Fr::from_u64((uint64_t)1 << log_m).inverse();
-      if (nm == 3) {
-        if ((rc = vec_scale(W, &minv, 3 * per, st))) return rc;
-      } else {
-        for (int k = 0; k < 3; k++)
-          if (masked[k] && (rc = vec_scale(W + k * per, &minv, per, st))) return rc;
-      }
-    }
-    for (int k = 0; k < 3; k++)
-      if (masked[k] && (rc = vec_add(W + k * per, mk->fft_in[first + k], per, st))) return rc;
-    return ZK_OK;
-  }
-  // king3 on materialised words: no in-masks, so one batched launch unless the 1 / m is in some words and not in others
-  int king3_checked(const Fr* in, const zk_groth16_masks* mk, int first, int log_m, int inverse, const void* g, int rearrange,
-                    uint64_t seed, Fr* out, size_t per, const bool* masked, hipStream_t st) {
-    const Fr* U = nullptr;
-    int rc = umat_for(nullptr, n, &U);
-    if (rc) return rc;
-    KingBatch<Fr> kb{};
-    kb.stride = per;
-    for (int k = 0; k < 3; k++) kb.out_mask[k] = mk ? (const Fr*)mk->fft_out[first + k] : nullptr;
-    if (!inverse || (masked[0] == masked[1] && masked[1] == masked[2]))
-      return king_dispatch_batch(in, kb, 3, n, log_m, inverse, U, g, inverse && !masked[0] ? 1 : 0, rearrange, seed, out, false,
-                                 st);
-    for (int k = 0; k < 3; k++) {
-      rc = king_dispatch(in + k * per, nullptr, n, log_m, inverse, U, g, masked[k] ? 0 : 1, rearrange, seed + k, out + k * per,
-                         kb.out_mask[k], false, st);
-      if (rc) return rc;
-    }
-    return ZK_OK;
-  }
-  int circom_h_checked(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* mk, uint64_t seed,
-                       void* h, uint8_t* status, uint32_t* errpos, uint64_t* summary, hipStream_t st) override {
-    return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, h, HReport{status, errpos, summary}, ws(st)->hwork, st);
-  }
-  int circom_h_checked_ws(const void* qa, const void* qb, const void* qc, int log_m, const zk_groth16_masks* mk, uint64_t seed,
-                          void* h, const HReport& rep, DevBuf& hwork, hipStream_t st) {
-    int log_l = ilog2(l);
-    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
-    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
-    if (!qa || !qb || !qc || !h || !rep.status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    if (!gao_batch_fits(3, Lc)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
-    const size_t vec_bytes = 6 * per * sizeof(Fr);
-    static_assert(sizeof(Fr) % 32 == 0, "the repair's working memory stays aligned behind the vectors");
-    ZK_HIP(hwork.ensure(vec_bytes + gao_layout<Fr>(n, 3, Lc, false).bytes));
-    Fr* W0 = (Fr*)hwork.p;
-    Fr* W1 = W0 + 3 * per;
-    void* gwk = (char*)hwork.p + vec_bytes;
-    auto repair = [&](Fr* W, int first, int items, int dimension) {
-      GaoCall c = gao_call(W, nullptr, n, Lc, dimension, rep.status + first * Lc, rep.errpos ? rep.errpos + first * Lc : nullptr,
-                           rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr);
-      c.nitems = items, c.item_stride = per;
-      return gao_run<FrP, true>(this, gwk, l, c, st);
-    };
-    Fr w2m = root_of_unity(log_m + 1);
-    bool masked[3];
-    // round 1: 3 x d_ifft(rearrange = true, g = w_2m)   (ext_wit.rs:127-159)
-    int rc = fft1_src(W0, log_m, 1, 3 * (size_t)n, nullptr, st,
-                      NttSrc<Fr>{{(const Fr*)qa, (const Fr*)qb, (const Fr*)qc}, (uint32_t)n});
-    if (rc) return rc;
-    if ((rc = h_round_words(W0, mk, 0, log_m, 1, per, masked, st))) return rc;
-    if ((rc = repair(W0, 0, 3, 2 * l))) return rc;
-    if ((rc = king3_checked(W0, mk, 0, log_m, 1, &w2m, 1, seed, W1, per, masked, st))) return rc;
-    // round 2: 3 x d_fft(rearrange = false)             (ext_wit.rs:161-170)
-    if ((rc = fft1(W1, log_m, 0, 3 * (size_t)n, nullptr, st))) return rc;
-    if ((rc = h_round_words(W1, mk, 3, log_m, 0, per, masked, st))) return rc;
-    if ((rc = repair(W1, 3, 3, 2 * l))) return rc;
-    if ((rc = king3_checked(W1, mk, 3, log_m, 0, nullptr, 0, seed + 3, W0, per, masked, st))) return rc;
-    // a*b - c + in_mask, then deg_red               (ext_wit.rs:173-179)
-    // (into W1, which the second king has read: the kernel's pointers do not alias)
-    if ((rc = vec_mul_sub(W1, W0, W0 + per, W0 + 2 * per, per, st))) return rc;
-    if (mk && mk->degred_in && (rc = vec_add(W1, mk->degred_in, per, st))) return rc;
-    if ((rc = repair(W1, 6, 1, 4 * l - 1))) return rc;
-    return deg_red_np(W1, nullptr, nullptr, n, Lc, seed + 6, (Fr*)h, mk ? (const Fr*)mk->degred_out : nullptr, st);
-  }
-
-  // ---------------------------------------------------------------- the checked h chain with a party list
-  // (zk_circom_h_checked_parties) circom_h_checked when only the words of the listed parties reach the kings: all n parties
-  // (the chain above) or n - 1 of them (checked_list).  A round's three words are COMPACT, [np][m/l] at W + k * per: the
-  // first NTT pass reads one pointer per listed row, the in-mask rows of the list come from one add_list_rows launch, one
-  // pss_repair_batch_parties of 3 items runs at dimension 2l, and the kings take the list (umat_for(ids, np)).  The batched
-  // king reads np rows at the row pitch m/l from in + k * stride and writes n rows at out + k * stride, so the compact layout
-  // at the stride of the full one goes through ONE batched launch, under the same condition as king3_checked.
-  // At l <= 4 a round's 3 np row pointers go into one NttSrc as 3 n - 1 <= 47 vectors: vector k n + r is listed row r of
-  // word k, and the one row of an item beyond its np -- never read by the repair or the king -- transforms listed row 0 once
-  // more, so the three words of a round stay one set of NTT launches.  At l = 8 (93 pointers) one word per call.
-  // Item 6: with n - 1 parties the dimension 4l - 1 leaves no redundancy -- NOT CHECKED: the compact word goes to deg_red with
-  // the list unrepaired, its status and errpos bytes are 0 and its summary row is all zeros (no chunk checked; a clean
-  // item reads [m/l, 0, 0, ..]).
-  int h_list_words(Fr* W, const Fr* const* src, int log_m, int inverse, size_t per, const uint32_t* ids, int np,
-                   hipStream_t st) {
-    const size_t Lc = ((size_t)1 << log_m) / l;
-    int rc;
-    if (3 * n - 1 <= NTT_SRC_MAX) {
-      NttSrc<Fr> s{};
-      s.per = 1;
-      for (int k = 0; k < 3; k++)
-        for (int r = 0; r < n && k * n + r < 3 * n - 1; r++) s.p[k * n + r] = src[k] + (size_t)ids[r < np ? r : 0] * Lc;
-      return fft1_src(W, log_m, inverse, (size_t)(3 * n - 1), nullptr, st, s);
-    }
-    static_assert(GAO_MAX_N <= NTT_SRC_MAX, "one pointer per listed row");
-    for (int k = 0; k < 3; k++) {
-      NttSrc<Fr> s{};
-      s.per = 1;
-      for (int r = 0; r < np; r++) s.p[r] = src[k] + (size_t)ids[r] * Lc;
-      if ((rc = fft1_src(W + k * per, log_m, inverse, (size_t)np, nullptr, st, s))) return rc;
-    }
-    return ZK_OK;
-  }
-  int king3_list(const Fr* in, const zk_groth16_masks* mk, int first, int log_m, int inverse, const void* g, int rearrange,
-                 uint64_t seed, Fr* out, size_t per, const bool* masked, const uint32_t* ids, int np, hipStream_t st) {
-    const Fr* U = nullptr;
-    int rc = umat_for(ids, np, &U);
-    if (rc) return rc;
-    KingBatch<Fr> kb{};
-    kb.stride = per;
-    for (int k = 0; k < 3; k++) kb.out_mask[k] = mk ? (const Fr*)mk->fft_out[first + k] : nullptr;
-    if (!inverse || (masked[0] == masked[1] && masked[1] == masked[2]))
-      return king_dispatch_batch(in, kb, 3, np, log_m, inverse, U, g, inverse && !masked[0] ? 1 : 0, rearrange, seed, out, false,
-                                 st);
-    for (int k = 0; k < 3; k++) {
-      rc = king_dispatch(in + k * per, nullptr, np, log_m, inverse, U, g, masked[k] ? 0 : 1, rearrange, seed + k, out + k * per,
-                         kb.out_mask[k], false, st);
-      if (rc) return rc;
-    }
-    return ZK_OK;
-  }
-  int circom_h_checked_parties(const uint32_t* parties, int np, const void* qa, const void* qb, const void* qc, int log_m,
-                               const zk_groth16_masks* mk, uint64_t seed, void* h, uint8_t* status, uint32_t* errpos,
-                               uint64_t* summary, hipStream_t st) override {
-    return circom_h_checked_parties_ws(parties, np, qa, qb, qc, log_m, mk, seed, h, HReport{status, errpos, summary},
-                                       ws(st)->hwork, st);
-  }
-  int circom_h_checked_parties_ws(const uint32_t* parties, int np, const void* qa, const void* qb, const void* qc, int log_m,
-                                  const zk_groth16_masks* mk, uint64_t seed, void* h, const HReport& rep, DevBuf& hwork,
-                                  hipStream_t st) {
-    uint32_t ids[GAO_MAX_N];
-    int rc = checked_list(parties, np, 2 * l, ids);
-    if (rc) return rc;
-    if (np == n) return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, h, rep, hwork, st);
-    int log_l = ilog2(l);
-    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
-    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
-    if (!qa || !qb || !qc || !h || !rep.status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    if (!gao_batch_fits(3, Lc)) return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
-    const size_t vec_bytes = 6 * per * sizeof(Fr);
-    ZK_HIP(hwork.ensure(vec_bytes + gao_layout<Fr>(n, 3, Lc, true).bytes));
-    Fr* W0 = (Fr*)hwork.p;
-    Fr* W1 = W0 + 3 * per;
-    void* gwk = (char*)hwork.p + vec_bytes;
-    const Fr minv = Fr::from_u64((uint64_t)1 << log_m).inverse();
-    // the words of a round in W0: the transform of the listed rows of src[0..2], the list's in-mask rows, the repair
-    auto round = [&](const Fr* const* src, int first, int inverse, bool* masked) {
-      int r = h_list_words(W0, src, log_m, inverse, per, ids, np, st);
-      if (r) return r;
-      const Fr* masks[3];
-      for (int k = 0; k < 3; k++) masked[k] = (masks[k] = mk ? (const Fr*)mk->fft_in[first + k] : nullptr) != nullptr;
-      if ((r = add_list_rows(W0, per, masks, 3, ids, np, inverse != 0, minv, Lc, st))) return r;
-      GaoCall c = gao_call(W0, ids, np, Lc, 2 * l, rep.status + first * Lc, rep.errpos ? rep.errpos + first * Lc : nullptr,
-                           rep.summary ? rep.summary + (size_t)first * (3 + n) : nullptr);
-      c.nitems = 3, c.item_stride = per;
-      return gao_run<FrP, true>(this, gwk, l, c, st);
-    };
-    Fr w2m = root_of_unity(log_m + 1);
-    bool masked[3];
-    // round 1: 3 x d_ifft(rearrange = true, g = w_2m)   (ext_wit.rs:127-159)
-    const Fr* q3[3] = {(const Fr*)qa, (const Fr*)qb, (const Fr*)qc};
-    if ((rc = round(q3, 0, 1, masked))) return rc;
-    if ((rc = king3_list(W0, mk, 0, log_m, 1, &w2m, 1, seed, W1, per, masked, ids, np, st))) return rc;
-    // round 2: 3 x d_fft(rearrange = false)             (ext_wit.rs:161-170): out of place, W1's listed rows into W0
-    const Fr* w3[3] = {W1, W1 + per, W1 + 2 * per};
-    if ((rc = round(w3, 3, 0, masked))) return rc;
-    if ((rc = king3_list(W0, mk, 3, log_m, 0, nullptr, 0, seed + 3, W1, per, masked, ids, np, st))) return rc;
-    // a*b - c + in_mask over the listed rows, compact in W0, then deg_red with the list   (ext_wit.rs:173-179): the one
-    // absent party e splits the rows into those below it and those above, which move up by one
-    const uint32_t e = ids[np - 1] == (uint32_t)np - 1 ? (uint32_t)np : [&] {
-      uint32_t r = 0;
-      while (ids[r] == r) r++;
-      return r;
-    }();
-    if ((rc = vec_mul_sub(W0, W1, W1 + per, W1 + 2 * per, e * Lc, st))) return rc;
-    const size_t up = (size_t)(e + 1) * Lc;
-    if ((rc = vec_mul_sub(W0 + e * Lc, W1 + up, W1 + per + up, W1 + 2 * per + up, ((size_t)np - e) * Lc, st))) return rc;
-    const Fr* dmask[1] = {mk ? (const Fr*)mk->degred_in : nullptr};
-    if ((rc = add_list_rows(W0, per, dmask, 1, ids, np, false, minv, Lc, st))) return rc;
-    ZK_HIP(hipMemsetAsync(rep.status + 6 * Lc, 0, Lc, st));
-    if (rep.errpos) ZK_HIP(hipMemsetAsync(rep.errpos + 6 * Lc, 0, Lc * 4, st));
-    if (rep.summary) ZK_HIP(hipMemsetAsync(rep.summary + (size_t)6 * (3 + n), 0, (size_t)(3 + n) * 8, st));
-    return deg_red_np(W0, nullptr, ids, np, Lc, seed + 6, (Fr*)h, mk ? (const Fr*)mk->degred_out : nullptr, st);
-  }
-
-  // circom_h of `nb` proofs as ONE launch chain (zk_groth16_prove_batch): the 3 nb vectors go through every NTT pass,
-  // king and deg_red launch together (grid.y), so the chain's dozen dependent launches are paid once per batch.
-  // q*[b]: [n][Lc]; mk: nb mask sets or nullptr; h: [nb][n][Lc]; proof b draws the randomness a single circom_h with
-  // seed + PROOF_SEED_STEP * b draws.
-  static constexpr uint32_t PROOF_SEED_STEP = 16;
-  int circom_h_batch(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
-                     const zk_groth16_masks* mk, uint64_t seed, Fr* h, DevBuf& hwork, hipStream_t st) {
-    int log_l = ilog2(l);
-    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
-    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
-    if (nb < 1 || 3 * nb > KING_BATCH || nb > DEGRED_BATCH) return fail(ZK_ERR_BAD_INPUT, "bad batch size");
-    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    // one launch needs the in-masks of a stage all present or all absent across the batch; otherwise proof by proof
-    bool uniform = true;
-    if (mk)
-      for (int k = 0; k < 6 && uniform; k++)
-        for (int b = 1; b < nb; b++)
-          if ((mk[b].fft_in[k] != nullptr) != (mk[0].fft_in[k] != nullptr)) uniform = false;
-    if (mk && uniform)
-      for (int k = 0; k < 6 && uniform; k += 3)
-        if ((mk[0].fft_in[k] != nullptr) != (mk[0].fft_in[k + 1] != nullptr) ||
-            (mk[0].fft_in[k] != nullptr) != (mk[0].fft_in[k + 2] != nullptr))
-          uniform = false;
-    if (!uniform) {
-      for (int b = 0; b < nb; b++) {
-        int rc = circom_h_ws(qa[b], qb[b], qc[b], log_m, &mk[b], seed + (uint64_t)PROOF_SEED_STEP * b, h + b * per, hwork, st);
-        if (rc) return rc;
-      }
-      return ZK_OK;
-    }
-    ZK_HIP(hwork.ensure(6 * per * nb * sizeof(Fr)));
-    Fr* W0 = (Fr*)hwork.p;
-    Fr* W1 = W0 + 3 * per * nb;
-    Fr w2m = root_of_unity(log_m + 1);
-    NttSrc<Fr> src{};
-    src.per = (uint32_t)n;
-    for (int b = 0; b < nb; b++) {
-      if (!qa[b] || !qb[b] || !qc[b]) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-      src.p[3 * b] = (const Fr*)qa[b];
-      src.p[3 * b + 1] = (const Fr*)qb[b];
-      src.p[3 * b + 2] = (const Fr*)qc[b];
-    }
-    int rc = fft1_src(W0, log_m, 1, 3 * (size_t)n * nb, nullptr, st, src);
-    if (rc) return rc;
-    const Fr* U = nullptr;
-    rc = umat_for(nullptr, n, &U);
-    if (rc) return rc;
-    auto king = [&](const Fr* in, int first, int inverse, const void* g, int scale, int rearrange, uint64_t sd, Fr* out) {
-      KingBatch<Fr> kb{};
-      kb.stride = per;
-      kb.items_per = 3;
-      kb.seed_step = PROOF_SEED_STEP;
-      for (int b = 0; b < nb; b++)
-        for (int k = 0; k < 3; k++) {
-          kb.in_mask[3 * b + k] = mk ? (const Fr*)mk[b].fft_in[first + k] : nullptr;
-          kb.out_mask[3 * b + k] = mk ? (const Fr*)mk[b].fft_out[first + k] : nullptr;
-        }
-      return king_dispatch_batch(in, kb, 3 * nb, n, log_m, inverse, U, g, scale, rearrange, sd, out, false, st);
-    };
-    rc = king(W0, 0, 1, &w2m, 1, 1, seed, W1);
-    if (rc) return rc;
-    rc = fft1(W1, log_m, 0, 3 * (size_t)n * nb, nullptr, st);
-    if (rc) return rc;
-    rc = king(W1, 3, 0, nullptr, 0, 0, seed + 3, W0);
-    if (rc) return rc;
-    DegredBatch<Fr> db{};
-    for (int b = 0; b < nb; b++) {
-      db.in_mask[b] = mk ? (const Fr*)mk[b].degred_in : nullptr;
-      db.out_mask[b] = mk ? (const Fr*)mk[b].degred_out : nullptr;
-    }
-    db.in_step = 3 * per;
-    db.out_step = per;
-    db.seed_step = PROOF_SEED_STEP;
-    return deg_red_batch(W0, db, nb, nullptr, n, Lc, seed + 6, h, st, 0, 0, W0 + per, W0 + 2 * per);
-  }
-
-  // ---------------------------------------------------------------- the checked h chain of a batch
-  // (zk_circom_h_batch_checked, zk_groth16_prove_checked_batch) circom_h_batch with every king word of every proof repaired
-  // before its king reads it: proof b is circom_h_checked_ws with seed + PROOF_SEED_STEP * b, its report slice
-  // rep.status + b * 7 * m/l (errpos alike, summary + b * 7 * (3 + n)) what that call writes.  One chain for the batch:
-  //   fft1_src over 3 nb vectors; h_words_batch_kernel (h_batch.hpp) puts the 1 / m and the in-masks into all 3 nb words;
-  //   ONE gao_run of 3 nb items (a full batch is exactly GAO_BATCH_MAX); the batched king with null in-masks;
-  //   the same for the forward round; h_mulsub_batch_kernel writes the nb words a*b - c (+ degred_in) into W1, which the
-  //   second king has read; ONE gao_run of nb items at dimension 4l - 1; deg_red_batch on the ready words (null in-masks,
-  //   no mul_b / sub_c: the form that takes a word as it is).
-  // The repair indexes status and errpos by item, so a round's rows are contiguous: the three repairs write a round-major
-  // staging report behind the repair's working memory in hwork (h_batch.hpp staging_row) and h_report_gather_kernel, the last
-  // launch of the chain, moves the rows to the caller's proof-major buffers.  hwork: 6 per nb vectors, gao_layout(n, 3 nb,
-  // m/l), the staging status, errpos and summary rows.
-  // The in-masks of a stage must be present or absent alike across the batch and a round's three words (circom_h_batch's
-  // condition); otherwise circom_h_checked_ws proof by proof on the stream -- the same results.
-  static_assert(H_BATCH_MAX == DEGRED_BATCH && H_BATCH_ITEMS == KING_BATCH && H_BATCH_ITEMS == GAO_BATCH_MAX,
-                "one round of a full batch is one king launch and one repair call");
-  static HReport report_slice(const HReport& rep, int b, size_t Lc, int n_) {
-    return HReport{rep.status + (size_t)b * H_REPORT_ROWS * Lc, rep.errpos ? rep.errpos + (size_t)b * H_REPORT_ROWS * Lc : nullptr,
-                   rep.summary ? rep.summary + (size_t)b * H_REPORT_ROWS * (3 + n_) : nullptr};
-  }
-  // every refusal of the batched chain, before anything is written
-  int h_batch_checked_check(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
-                            const void* h, const HReport& rep) {
-    int log_l = ilog2(l);
-    if (nb < 1 || nb > H_BATCH_MAX) return fail(ZK_ERR_BAD_INPUT, "batch size must be in 1.." + std::to_string(H_BATCH_MAX));
-    if (log_m < log_l) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
-    if (log_m + 1 > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "domain too large for this field");
-    if (!qa || !qb || !qc || !h || !rep.status) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    for (int b = 0; b < nb; b++)
-      if (!qa[b] || !qb[b] || !qc[b]) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    if (!gao_batch_fits(3 * (uint64_t)nb, ((size_t)1 << log_m) / l))
-      return fail(ZK_ERR_BAD_INPUT, "more than 2^32 - 1 chunks in the batch");
-    return ZK_OK;
-  }
-  int circom_h_batch_checked(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
-                             const zk_groth16_masks* mk, uint64_t seed, void* h, uint8_t* status, uint32_t* errpos,
-                             uint64_t* summary, hipStream_t st) override {
-    return circom_h_batch_checked_ws(nb, qa, qb, qc, log_m, mk, seed, (Fr*)h, HReport{status, errpos, summary}, ws(st)->hwork, st);
-  }
-  int circom_h_batch_checked_ws(int nb, const void* const* qa, const void* const* qb, const void* const* qc, int log_m,
-                                const zk_groth16_masks* mk, uint64_t seed, Fr* h, const HReport& rep, DevBuf& hwork,
-                                hipStream_t st) {
-    int rc = h_batch_checked_check(nb, qa, qb, qc, log_m, h, rep);
-    if (rc) return rc;
-    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    bool uniform = true;
-    if (mk)
-      for (int k = 0; k < 6 && uniform; k++)
-        for (int b = 1; b < nb; b++)
-          if ((mk[b].fft_in[k] != nullptr) != (mk[0].fft_in[k] != nullptr)) uniform = false;
-    if (mk && uniform)
-      for (int k = 0; k < 6 && uniform; k += 3)
-        if ((mk[0].fft_in[k] != nullptr) != (mk[0].fft_in[k + 1] != nullptr) ||
-            (mk[0].fft_in[k] != nullptr) != (mk[0].fft_in[k + 2] != nullptr))
-          uniform = false;
-    if (!uniform) {
-      for (int b = 0; b < nb; b++) {
-        rc = circom_h_checked_ws(qa[b], qb[b], qc[b], log_m, &mk[b], seed + (uint64_t)PROOF_SEED_STEP * b, h + b * per,
-                                 report_slice(rep, b, Lc, n), hwork, st);
-        if (rc) return rc;
-      }
-      return ZK_OK;
-    }
-    // ---- working memory: vectors | repair | staging status | staging errpos | staging summary, each at a multiple of 32
-    auto up32 = [](size_t v) { return (v + 31) / 32 * 32; };
-    const size_t rows = (size_t)H_REPORT_ROWS * nb, sumw = (size_t)(3 + n);
-    const size_t vec_bytes = 6 * per * nb * sizeof(Fr);
-    const size_t off_st = vec_bytes + up32(gao_layout<Fr>(n, 3 * nb, Lc, false).bytes);
-    const size_t off_ep = off_st + up32(rows * Lc);
-    const size_t off_sm = off_ep + up32(rep.errpos ? rows * Lc * 4 : 0);
-    ZK_HIP(hwork.ensure(off_sm + (rep.summary ? rows * sumw * 8 : 0)));
-    Fr* W0 = (Fr*)hwork.p;
-    Fr* W1 = W0 + 3 * per * nb;
-    void* gwk = (char*)hwork.p + vec_bytes;
-    uint8_t* s_st = (uint8_t*)hwork.p + off_st;
-    uint32_t* s_ep = rep.errpos ? (uint32_t*)((char*)hwork.p + off_ep) : nullptr;
-    uint64_t* s_sm = rep.summary ? (uint64_t*)((char*)hwork.p + off_sm) : nullptr;
-    // the repair of a round into its staging rows
-    auto repair = [&](Fr* W, int round, int dimension) {
-      const size_t first = staging_round_first((uint32_t)nb, (uint32_t)round);
-      GaoCall c = gao_call(W, nullptr, n, Lc, dimension, s_st + first * Lc, s_ep ? s_ep + first * Lc : nullptr,
-                           s_sm ? s_sm + first * sumw : nullptr);
-      c.nitems = (int)staging_round_items((uint32_t)nb, (uint32_t)round), c.item_stride = per;
-      return gao_run<FrP, true>(this, gwk, l, c, st);
-    };
-    // the words of a round in place (item 3 b + k at W + (3 b + k) * per) and whether they carry in-masks
-    const Fr minv = Fr::from_u64((uint64_t)1 << log_m).inverse();
-    auto words = [&](Fr* W, int first, int inverse, bool* masked) {
-      *masked = mk && mk[0].fft_in[first];
-      if (!*masked) return (int)ZK_OK;
-      HWordMasks<Fr> hm{};
-      for (int b = 0; b < nb; b++)
-        for (int k = 0; k < 3; k++) hm.mask[3 * b + k] = (const Fr*)mk[b].fft_in[first + k];
-      h_words_batch_kernel<Fr><<<h_batch_grid(per, 3 * nb), dim3(256), 0, st>>>(W, per, hm, inverse, minv, per);
-      ZK_HIP(hipGetLastError());
-      return (int)ZK_OK;
-    };
-    const Fr* U = nullptr;
-    if ((rc = umat_for(nullptr, n, &U))) return rc;
-    auto king = [&](const Fr* in, int first, int inverse, const void* g, int scale, int rearrange, uint64_t sd, Fr* out) {
-      KingBatch<Fr> kb{};
-      kb.stride = per;
-      kb.items_per = 3;
-      kb.seed_step = PROOF_SEED_STEP;
-      for (int b = 0; b < nb; b++)
-        for (int k = 0; k < 3; k++) kb.out_mask[3 * b + k] = mk ? (const Fr*)mk[b].fft_out[first + k] : nullptr;
-      return king_dispatch_batch(in, kb, 3 * nb, n, log_m, inverse, U, g, scale, rearrange, sd, out, false, st);
-    };
-    Fr w2m = root_of_unity(log_m + 1);
-    NttSrc<Fr> src{};
-    src.per = (uint32_t)n;
-    for (int b = 0; b < nb; b++) {
-      src.p[3 * b] = (const Fr*)qa[b];
-      src.p[3 * b + 1] = (const Fr*)qb[b];
-      src.p[3 * b + 2] = (const Fr*)qc[b];
-    }
-    bool masked = false;
-    // round 1: 3 nb x d_ifft(rearrange = true, g = w_2m); the 1 / m is in the word where there is a mask
-    if ((rc = fft1_src(W0, log_m, 1, 3 * (size_t)n * nb, nullptr, st, src))) return rc;
-    if ((rc = words(W0, 0, 1, &masked))) return rc;
-    if ((rc = repair(W0, 0, 2 * l))) return rc;
-    if ((rc = king(W0, 0, 1, &w2m, masked ? 0 : 1, 1, seed, W1))) return rc;
-    // round 2: 3 nb x d_fft(rearrange = false)
-    if ((rc = fft1(W1, log_m, 0, 3 * (size_t)n * nb, nullptr, st))) return rc;
-    if ((rc = words(W1, 3, 0, &masked))) return rc;
-    if ((rc = repair(W1, 1, 2 * l))) return rc;
-    if ((rc = king(W1, 3, 0, nullptr, 0, 0, seed + 3, W0))) return rc;
-    // the nb words a*b - c + in_mask at W1 + b * per, detection at dimension 4l - 1, then deg_red on the ready words
-    HProdMasks<Fr> pm{};
-    DegredBatch<Fr> db{};
-    for (int b = 0; b < nb; b++) {
-      pm.mask[b] = mk ? (const Fr*)mk[b].degred_in : nullptr;
-      db.out_mask[b] = mk ? (const Fr*)mk[b].degred_out : nullptr;
-    }
-    h_mulsub_batch_kernel<Fr><<<h_batch_grid(per, nb), dim3(256), 0, st>>>(W1, per, W0, 3 * per, pm, per);
-    ZK_HIP(hipGetLastError());
-    if ((rc = repair(W1, 2, 4 * l - 1))) return rc;
-    db.in_step = per;
-    db.out_step = per;
-    db.seed_step = PROOF_SEED_STEP;
-    if ((rc = deg_red_batch(W1, db, nb, nullptr, n, Lc, seed + 6, h, st))) return rc;
-    h_report_gather_kernel<<<h_batch_grid(Lc, (int)rows), dim3(256), 0, st>>>(
-        (uint32_t)nb, (uint32_t)Lc, (uint32_t)sumw, s_st, s_ep, s_sm, rep.status, rep.errpos, rep.summary);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
-  }
 
   // ---------------------------------------------------------------- prover (prove.rs, sha256.rs:32-129)
   // Everything the host contributes to a proof (scalar multiples of CRS constants, of the out-masks and of the in-mask
@@ -916,12 +421,8 @@
     };
     // report (zk_groth16_prove_checked): the checked h chain on the same stream with the same work buffers, its report into
     // the caller's buffers -- complete once the job's join has waited for the U chain; nothing else of the proof differs
-    auto h_chain = [&](hipStream_t hs) {
-      if (listed)
-        return circom_h_checked_parties_ws(report->ids, report->np, qa, qb, qc, log_m, mk, seed, J->hshare.p, *report, J->hwork,
-                                           hs);
-      if (report) return circom_h_checked_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, *report, J->hwork, hs);
-      return circom_h_ws(qa, qb, qc, log_m, mk, seed, J->hshare.p, J->hwork, hs);
+    auto h_run = [&](hipStream_t hs) {
+      return h_chain(HChain{1, &qa, &qb, &qc, log_m, mk, seed, (Fr*)J->hshare.p, report, &J->hwork, hs});
     };
     // ---- one bucket set for C.  C needs r*H + W + U only as a sum, and bucket accumulation is linear: where the launches
     // of H (the second vector of the S+H launch), W and U have the same bucket geometry -- with the registered SHA-256 CRS
@@ -955,7 +456,7 @@
     if (full && gated) {
       hipError_t he = j.hshare.ensure((size_t)n * Lc * sizeof(Fr));
       if (he != hipSuccess) return hip_fail(he, "h share buffer");
-      rc = h_chain(streams_[5]);
+      rc = h_run(streams_[5]);
       if (rc) return rc;
       rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
                                       cu, crs->len_u, streams_[5], &j.msm[ROLE_U], nullptr, u_gate(j));
@@ -984,7 +485,7 @@
       hipStream_t hs = streams_[5];
       hipError_t he = j.hshare.ensure((size_t)n * Lc * sizeof(Fr));
       if (he != hipSuccess) return hip_fail(he, "h share buffer");
-      rc = h_chain(hs);
+      rc = h_run(hs);
       if (rc) return rc;
       host_span(PROF_HOST_H);
       rc = msm_.template launch_t<Fq_>(this, j.ws0 + ROLE_U, crs->u_d, j.hshare.p, (size_t)n * crs->len_u,
@@ -1154,7 +655,7 @@
     if (prof.on) prof.host_add(PROF_HOST_LAUNCH, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return groth16_wait(h, pi_a, pi_b, pi_c);
   }
-  // zk_groth16_prove_checked: the proof above with circom_h's seven king words checked (circom_h_checked_ws).  The five d_msm
+  // zk_groth16_prove_checked: the proof above with circom_h's seven king words checked (engine_h.inc.hpp h_chain with a report).  The five d_msm
   // rounds stay unchecked.  The asynchronous form followed by the join, which orders the report buffers.
   int groth16_prove_checked(const zk_crs_share* crs, const void* qa, const void* qb, const void* qc, const void* a_share,
                             const void* ax_share, const void* r_, const void* s_, int log_m, const zk_groth16_masks* mk,
@@ -1278,7 +779,7 @@
                                 hipStream_t st, int* handle) override {
     return batch_start(crs_in, nb, qa, qb, qc, a_share, ax_share, r_, s_, log_m, mk, seed, st, handle, nullptr);
   }
-  // zk_groth16_prove_checked_batch: the batch above on the checked h chain of a batch (circom_h_batch_checked_ws) with the
+  // zk_groth16_prove_checked_batch: the batch above on the checked h chain of a batch (h_chain with a report) with the
   // batch's own hwork, and so its own staging report; the five d_msm rounds stay unchecked as in the single call.  The
   // report (proof-major, [nb][7]) is complete when zk_groth16_batch_wait returns.
   int groth16_prove_checked_batch(const zk_crs_share* crs, int nb, const void* const* qa, const void* const* qb,
@@ -1314,8 +815,7 @@
     if (rc) return rc;
     // ---- circom_h of the whole batch and the U-MSM behind it
     const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    if (report) rc = circom_h_batch_checked_ws(nb, qa, qb, qc, log_m, mk, seed, (Fr*)B->hshare.p, *report, B->hwork, B->st[5]);
-    else rc = circom_h_batch(nb, qa, qb, qc, log_m, mk, seed, (Fr*)B->hshare.p, B->hwork, B->st[5]);
+    rc = h_chain(HChain{nb, qa, qb, qc, log_m, mk, seed, (Fr*)B->hshare.p, report, &B->hwork, B->st[5]});
     if (!rc) rc = batch_launch_u(*B, (const Fr*)B->hshare.p, per, B->st[5]);
     if (rc) return bail(*B, rc);
     *handle = B->slot;
@@ -1705,38 +1205,3 @@
     if (rc) return rc;
     return pss_pack_count((const Fr*)w + ni, nvars - ni, seed + 4, (Fr*)ax_share, st);
   }
-
-  // ---------------------------------------------------------------- libsnark_h (ext_wit.rs:14-102)
-  // 3 x d_ifft with the coset shift g = F::GENERATOR (rearranged) -> 3 x d_fft (rearranged) -> (a*b - c) / Z(g) ->
-  // d_ifft with g^-1.  Seven masks (or NULL arrays for FftMask::zero).
-  int libsnark_h(const void* qa, const void* qb, const void* qc, int log_m, const void* const* fft_in,
-                 const void* const* fft_out, uint64_t seed, void* h, hipStream_t st) override {
-    if (log_m < ilog2(l) || log_m > FrP::TWO_ADICITY) return fail(ZK_ERR_BAD_INPUT, "Mismatch of size in FFT");
-    if (!qa || !qb || !qc || !h) return fail(ZK_ERR_BAD_INPUT, "null pointer");
-    const size_t Lc = ((size_t)1 << log_m) / l, per = (size_t)n * Lc;
-    DevBuf& hwork_ = ws(st)->hwork;
-    ZK_HIP(hwork_.ensure(6 * per * sizeof(Fr)));
-    Fr* W0 = (Fr*)hwork_.p;
-    Fr* W1 = W0 + 3 * per;
-    const void* q[3] = {qa, qb, qc};
-    for (int k = 0; k < 3; k++) ZK_HIP(hipMemcpyAsync(W0 + k * per, q[k], per * sizeof(Fr), hipMemcpyDeviceToDevice, st));
-    Fr g = generator();
-    auto mi = [&](int k) { return fft_in ? fft_in[k] : nullptr; };
-    auto mo = [&](int k) { return fft_out ? fft_out[k] : nullptr; };
-    int rc;
-    for (int k = 0; k < 3; k++) {
-      rc = d_fft(W0 + k * per, mi(k), mo(k), 1, log_m, 1, &g, seed + k, W1 + k * per, st);
-      if (rc) return rc;
-      rc = d_fft(W1 + k * per, mi(3 + k), mo(3 + k), 1, log_m, 0, nullptr, seed + 3 + k, W0 + k * per, st);
-      if (rc) return rc;
-    }
-    rc = vec_mul_sub(W1, W0, W0 + per, W0 + 2 * per, per, st);
-    if (rc) return rc;
-    // 1 / Z(g), Z(x) = x^m - 1  (ext_wit.rs:78-81)
-    Fr zinv = (g.pow_u64((uint64_t)1 << log_m) - Fr::one()).inverse();
-    rc = vec_scale(W1, &zinv, per, st);
-    if (rc) return rc;
-    Fr ginv = g.inverse();
-    return d_fft(W1, mi(6), mo(6), 0, log_m, 1, &ginv, seed + 6, h, st);
-  }
-

@@ -386,7 +386,8 @@ class Engine : public IEngine {
   // ---- the class body continues in four fragments, by primitive (round 5) ----
 #include "engine_fft.inc.hpp"        // PSS, fft1, king of d_fft, deg_red, d_pp
 #include "engine_points.inc.hpp"     // MSM entry points, group-element PSS / deg_red, front end, wire formats, options
-#include "engine_groth16.inc.hpp"    // circom_h / libsnark_h, prover, batch prover
+#include "engine_h.inc.hpp"          // circom_h in every form (HChain, h_chain), libsnark_h
+#include "engine_groth16.inc.hpp"    // prover, batch prover
 #include "engine_dist.inc.hpp"       // zk_dist_*: per-rank collective forms
 #include "engine_setup.inc.hpp"      // zk_groth16_setup_scalars: R1CS and trapdoor -> CRS scalars
 #include "engine_gao.inc.hpp"        // zk_pss_unpack_robust: the error-correcting unpack

@@ -1,5 +1,6 @@
-// The batched checked h chain (engine_groth16.inc.hpp circom_h_batch_checked): where the report rows of a batch lie while
-// the chain runs, and the three launches the chain adds to circom_h_batch's.
+// The h chain (engine_h.inc.hpp h_chain): the layout of its work buffer, where the report rows of a checked batch lie while
+// the chain runs, and the three launches the checked chain adds to the unchecked one's.
+//   - h_layout: the byte offsets of the regions of the work buffer, for every form of the chain.  Plain integers only.
 //   - staging_row: the repair of a round indexes status and errpos by item * nchunks + chunk (gao_impl.hpp), so the rows of
 //     one ROUND are contiguous; the caller's report is proof-major, [nb][7].  The three repairs write a round-major staging
 //     report and ONE gather launch at the end of the chain moves every row to its place.  Plain integers only: this part
@@ -33,6 +34,26 @@ ZK_HB_HD uint32_t staging_row(uint32_t nb, uint32_t b, uint32_t k) {
 // the first staging row of a round (0, 1: the d_ifft / d_fft words; 2: the deg_red words) and its number of items
 ZK_HB_HD uint32_t staging_round_first(uint32_t nb, uint32_t round) { return round < 2 ? 3 * nb * round : 6 * nb; }
 ZK_HB_HD uint32_t staging_round_items(uint32_t nb, uint32_t round) { return round < 2 ? 3 * nb : nb; }
+
+// The work buffer of an h chain (h_chain's hwork) in byte offsets, a region's start a multiple of 32: W0 at 0 and W1, 3 nb vectors
+// [n][nchunks] of `elem` bytes an element each; the checked chain: the repair's working memory, gao_bytes =
+// gao_layout<Fr>(n, 3 nb, nchunks, listed).bytes of them (0: the unchecked chain); a checked batch (nb > 1): the round-major
+// staging status, errpos and summary rows.  A region that the form does not have is empty and lies at the end.
+struct HLayout {
+  size_t w1, gao, status, errpos, summary, bytes;
+};
+ZK_HB_HD HLayout h_layout(size_t n, size_t nb, size_t nchunks, size_t elem, size_t gao_bytes, bool errpos, bool summary) {
+  const size_t rows = gao_bytes && nb > 1 ? H_REPORT_ROWS * nb : 0;
+  HLayout w;
+  w.w1 = 3 * n * nchunks * nb * elem;
+  w.gao = 2 * w.w1;
+  w.status = w.bytes = w.gao + gao_bytes;
+  if (rows) w.status = (w.status + 31) / 32 * 32;
+  w.errpos = w.status + (rows * nchunks + 31) / 32 * 32;
+  w.summary = w.errpos + ((errpos ? rows * nchunks * 4 : 0) + 31) / 32 * 32;
+  if (rows) w.bytes = w.summary + (summary ? rows * (3 + n) * 8 : 0);
+  return w;
+}
 
 }  // namespace zk
 
